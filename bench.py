@@ -1,11 +1,16 @@
 """Headline benchmark: SDE steps/sec (batch x timesteps / sec) of the fixed-step hot path.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets the workload up, warms it up, times the K steps, writes what the last of them computed if
+`--dump-outputs DIR` is given (DIR/<name>.npy, float32 or float64, at most 64 MB in all: see _dump_outputs) and prints the result
+line. Everything else below -- `roofline`, `stepwise`, `configs3`, `all_gather_ms_per_solve`, `cpu_baseline` and the side
+measurements -- is measured only with `--full` (null in a plain line).
 
 N > 1 runs one rank per GPU over RCCL, either way it is started: under the driver's `python -m torch.distributed.run
 --nproc-per-node N ... bench.py --gpus N`, or as the plain command above, in which case bench.py starts the N ranks
 itself (and refuses, exit code 3, when the node has fewer than N GPUs). The line reports what the process group
-really was (`ranks_seen`, `rank_devices`, `collective_backend`) and the all-gather's own time per solve.
+really was (`ranks_seen`, `rank_devices`, `collective_backend`) and, with --full, the all-gather's own time per solve.
 
 One bench "step" = one full solve of the workload: BASELINE.json configs[1], diagonal-noise Ito Euler-Maruyama, batch
 65536 x state 64, 1000 fixed solver steps (dyadic dt = 2^-10 so the count is exact in float32), geometric Brownian
@@ -13,14 +18,14 @@ motion f = mu*y, g = sigma*y as an UNCHANGED user module of plain torch code, ha
 drop-in call. torchsde_amd/recognise.py interprets f and g at every solve, finds them per-channel affine, and the solve
 is one launch of the trajectory kernel (state in registers, increments from the counter RNG). The same job on the
 STEPWISE route (user f, g as torch kernels between the per-step kernels; the route of every SDE that is not a
-per-channel expression) is measured right after and reported inside the line as `stepwise`. Inputs are resident in HBM
+per-channel expression) is measured right after, with --full, and reported inside the line as `stepwise`. Inputs are resident in HBM
 before the timed region. N > 1: every rank solves its own rows (weak scaling; RNG rows are global, so results are the
 rows an unsharded run would produce) and the final states are all-gathered once per solve over RCCL.
 BASELINE configs[3] (Stratonovich midpoint, 262144 x 64 sharded over 8 GPUs) is
 `--gpus 8 --workload c4_midpoint_diag_default_route_b32768_d64` (stepwise: `c4_midpoint_diag_b32768_d64`): 32768 rows per GPU.
 
-The LAST stdout line (rank 0) is the headline JSON, under 4 KB; the side measurements are printed before it, one short
-line per workload, and written whole to bench_also.json:
+The LAST stdout line (rank 0) is the headline JSON, under 4 KB; with --full the side measurements are printed before it,
+one short line per workload, and written whole to bench_also.json:
 
 * `value` = trajectory-steps/s over the K timed solves (barrier + synchronize on both sides, max over ranks);
   `median_ms_per_step` / `value_median` restate it from the median of the per-solve times (HIP events recorded
@@ -38,7 +43,7 @@ line per workload, and written whole to bench_also.json:
   `traffic` (HBM bytes per launch from rocprofv3 PMC passes, tools/profile_traffic.sh) and `kernel_us_rocprofv3` are
   taken from profiles/traffic_latest.json ONLY when that file was collected on the kernel sources this run uses;
 * `cpu_baseline`: the oracle's port of the reference's CPU algorithm, timed on this host's cores on a bounded sample;
-* side measurements (single-GPU default run; `also` lines + bench_also.json): every other BASELINE configuration at its
+* side measurements (single-GPU default workload with --full; `also` lines + bench_also.json): every other BASELINE configuration at its
   single-GPU size on the stepwise path (configs[2] Euler-general and the Milstein-general extension, the configs[3]
   shard, configs[4] sdeint_adjoint), each with ms per solve (median of 5) and the same kernel-level measurement, bytes,
   fractions and counter traffic; then the default-route and closed-form variants. Not part of `value`; `--no-also` skips them, `--also-budget S` (default 100 s; 0 = no limit) bounds their total time.
@@ -156,11 +161,11 @@ _TRAJECTORY_SOURCES = _COMMON_SOURCES + ("trajectory.hip", "capi.hip")
 
 
 def _reference_package():
-    """The REAL reference (google-research/torchsde) if this host has it: /root/reference (or $TORCHSDE_REFERENCE) with
-    the `trampoline` stand-in of tests/golden/_ref_shim ahead of it on the path. None elsewhere -- the
-    GPU box has no /root/reference -- and then the baseline is the oracle's port (`kind: "port"`)."""
-    root = os.environ.get("TORCHSDE_REFERENCE", "/root/reference")
-    if not os.path.isdir(os.path.join(root, "torchsde")):
+    """The REAL reference (google-research/torchsde) when $TORCHSDE_REFERENCE names a checkout of it, with the
+    `trampoline` stand-in of tests/golden/_ref_shim ahead of it on the path. None otherwise, and then the
+    baseline is the oracle's port (`kind: "port"`)."""
+    root = os.environ.get("TORCHSDE_REFERENCE")
+    if not root or not os.path.isdir(os.path.join(root, "torchsde")):
         return None
     sys.dont_write_bytecode = True       # the reference tree is read-only
     for path in (root, os.path.join(ROOT, "tests", "golden", "_ref_shim")):
@@ -259,7 +264,9 @@ class Job:
         self._sdeint, self._sdeint_adjoint = torchsde_amd.sdeint, torchsde_amd.sdeint_adjoint
         self._BM = torchsde_amd.BrownianInterval
 
-    def solve(self, i, graph=None):
+    def solve(self, i, graph=None, keep=False):
+        """`keep`: hold on to the arrays a caller of this solve receives (`self.kept`, name -> tensor) for
+        `--dump-outputs`."""
         c = self.cfg
         graph = self.use_graph if graph is None else graph
         bm = self._BM(t0=0.0, t1=c["nsteps"] * c["dt"], size=(c["B"], c["m"]), dtype=torch.float32, device=self.dev,
@@ -281,6 +288,8 @@ class Job:
                     if c.get("logqp"):
                         # (ys, log-ratio (T - 1, B)): a latent-SDE user's loss has a term of the path and the KL term
                         states, log_ratio = ys
+                        if keep:
+                            self.kept = {"ys": states.detach(), "log_ratio": log_ratio.detach()}
                         ys = torch.cat([states[-1], log_ratio.sum(0).unsqueeze(-1)], dim=1).unsqueeze(0)
                     if plain and not type(ys.grad_fn).__name__.startswith(("_MlpAdjointFn", "ReversibleHeunFn")) \
                             and self._prepared:
@@ -288,12 +297,19 @@ class Job:
                 else:
                     ys = self._sdeint(self.sde, self.y0, self.ts, bm=bm, method=c["method"], dt=c["dt"],
                                       options=dict(extra_options) or None)
+                if keep and not c.get("logqp"):
+                    self.kept = {"ys": ys.detach()}
                 self.y0.grad = None
                 self.sde.zero_grad()
                 (ys.sum() if c.get("output_every_step") else ys[-1].sum()).backward()
             if self.dist is not None:
                 from torchsde_amd import sharding
                 sharding.all_reduce_gradients(list(self.sde.parameters()))
+            if keep:
+                self.kept["y0_grad"] = self.y0.grad
+                for pname, p in self.sde.named_parameters():
+                    if p.grad is not None:
+                        self.kept["grad_" + pname.replace(".", "_")] = p.grad
             return self.y0.grad
         with torch.no_grad():
             # (a recognised workload is the drop-in call: no options at all)
@@ -312,7 +328,11 @@ class Job:
                 self._pending.append((work, ys))
                 while len(self._pending) > 1:
                     self._pending.pop(0)[0].wait()
+                if keep:
+                    self.kept = {"final_states_gathered": out}
                 return out
+            if keep:
+                self.kept = {"ys": ys}
             return ys[-1]
 
     def finish(self):
@@ -956,6 +976,35 @@ def _emit_also(also):
     return written
 
 
+DUMP_LIMIT = 64 << 20      # bytes --dump-outputs may write in all
+
+
+def _dump_outputs(kept, directory, seed=20240601):
+    """`--dump-outputs DIR`: the arrays the last timed solve handed its caller, one `DIR/<name>.npy` each, in float32 (or
+    float64 where the solve computed in it). Over DUMP_LIMIT in all, every array is cut to its share of the limit by a
+    fixed, seeded sample of its rows (last axis kept whole) and saved as `<name>_sample.npy`: the same arguments give the
+    same files, so two builds can be compared output for output."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    arrays = {}
+    for name, t in kept.items():
+        if t is None:
+            continue
+        t = t.detach()
+        arrays[name] = (t.double() if t.dtype == torch.float64 else t.float()).cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    written = []
+    for name, a in arrays.items():
+        if total > DUMP_LIMIT and a.ndim >= 1:
+            rows = a.reshape(-1, a.shape[-1]) if a.ndim > 1 else a.reshape(-1, 1)
+            k = max(1, rows.shape[0] * DUMP_LIMIT // total)
+            pick = np.sort(np.random.default_rng(seed).choice(rows.shape[0], size=k, replace=False))
+            a, name = np.ascontiguousarray(rows[pick]), name + "_sample"
+        np.save(os.path.join(directory, name + ".npy"), a)
+        written.append(f"{name} {a.dtype} {tuple(a.shape)}")
+    print(f"[bench] outputs of the last timed step in {directory}: {'; '.join(written)}", file=sys.stderr)
+
+
 def _print_headline(line):
     """The LAST stdout line: the headline with `roofline` and `cpu_baseline`, under HEADLINE_LIMIT bytes. Prose is
     dropped before numbers if a future field ever pushes it over."""
@@ -973,9 +1022,10 @@ def _print_headline(line):
     print(text, flush=True)
 
 
-def _what_the_ranks_saw(job, dev, dist, share_gpu):
+def _what_the_ranks_saw(job, dev, dist, share_gpu, time_gather=True):
     """What a reader needs to believe an N-rank line: how many ranks the process group really had, which device each
-    one ran on, the backend, and what the one collective of a solve (the all-gather of final states) costs by itself."""
+    one ran on, the backend, and (`time_gather`) what the one collective of a solve (the all-gather of final states)
+    costs by itself."""
     name = torch.cuda.get_device_name(dev)
     if dist is None:
         return {"ranks_seen": 1, "rank_devices": [f"rank 0: cuda:{dev.index} {name}"], "collective_backend": None,
@@ -983,7 +1033,7 @@ def _what_the_ranks_saw(job, dev, dist, share_gpu):
     seen = [None] * dist.get_world_size()
     dist.all_gather_object(seen, f"rank {dist.get_rank()}: cuda:{dev.index} {name} (pid {os.getpid()})")
     gather_ms = None
-    if job.gathered is not None and not (job.adjoint or job.train):
+    if time_gather and job.gathered is not None and not (job.adjoint or job.train):
         local = torch.zeros((job.cfg["B"], job.cfg["d"]), device=dev)
         for _ in range(3):
             dist.all_gather_into_tensor(job.gathered[0], local)
@@ -1038,6 +1088,12 @@ def main():
     ap.add_argument("--no-stepwise", action="store_true",
                     help="skip the stepwise solve of the same workload reported beside a recognised headline")
     ap.add_argument("--eager", action="store_true", help="issue every solve eagerly instead of replaying a HIP graph")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else this file measures: roofline, the stepwise solve beside it, "
+                         "configs[3] beside a multi-GPU run, the all-gather's own time, the side measurements and the CPU "
+                         "baseline (the --no-* and --also-budget options apply here)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (the arrays its caller receives) as DIR/<name>.npy")
     ap.add_argument("--profile-steps", type=int, default=0,
                     help="tools/profile_traffic.sh only: solve this many solver steps of the workload and print a line "
                          "marked profile_run (per-launch counters do not need the full 1000 steps); NOT a measurement")
@@ -1098,11 +1154,12 @@ def main():
     for i in range(args.warmup):
         job.solve(i)
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
+    keep = args.steps - 1 if args.dump_outputs else -1
     barrier()
     t_start = time.perf_counter()
     for i in range(args.steps):
         marks[i].record()
-        out = job.solve(1000 + i)
+        out = job.solve(1000 + i, keep=i == keep)
     marks[args.steps].record()
     barrier()
     elapsed = time.perf_counter() - t_start
@@ -1114,35 +1171,36 @@ def main():
         elapsed, median_ms = t[0].item(), t[1].item()
     assert torch.isfinite(out).all()
     value = world * B * nsteps * args.steps / elapsed
-    ranks = _what_the_ranks_saw(job, dev, dist if use_dist else None, share_gpu)
+    if args.dump_outputs and rank == 0:
+        _dump_outputs(job.kept, args.dump_outputs)
+    ranks = _what_the_ranks_saw(job, dev, dist if use_dist else None, share_gpu, time_gather=args.full)
 
-    if job.trajectory:
-        k_ms, k_launches = job.bracket_dominant_kernel()
-        roofline = job.roofline(value, k_ms, k_launches)
-        if roofline is not None and roofline.get("bound") == "hbm" and cfg.get("kernel_match"):
+    # a plain run ends here; --full measures the rest
+    roofline = config3 = stepwise = also = cpu = None
+    if args.full:
+        if job.trajectory:
+            k_ms, k_launches = job.bracket_dominant_kernel()
+            roofline = job.roofline(value, k_ms, k_launches)
+            if roofline is not None and roofline.get("bound") == "hbm" and cfg.get("kernel_match"):
+                _attach_offline_traffic(roofline, args.workload)
+        else:
+            roofline = job.roofline_stepwise(value, job.back_to_back_us(job.live_state(out)))
             _attach_offline_traffic(roofline, args.workload)
-    else:
-        roofline = job.roofline_stepwise(value, job.back_to_back_us(job.live_state(out)))
-        _attach_offline_traffic(roofline, args.workload)
 
-    config3 = None
-    if world > 1 and args.workload == HEADLINE and use_dist:
-        try:
-            config3 = _config3_beside(dev, rank, world, dist, args)
-        except Exception as e:           # (never takes the headline down with it -- but every rank must fail alike)
-            config3 = {"workload": CONFIG3, "error": f"{type(e).__name__}: {e}"}
-    stepwise = None
-    if world == 1 and cfg.get("stepwise") and not args.no_stepwise:
-        stepwise = _stepwise_beside(dev, cfg["stepwise"], args)
-    also = None
-    if world == 1 and not args.no_also and args.workload == HEADLINE:
-        del job
-        torch.cuda.empty_cache()
-        also = _side_measurements(dev, args.also_budget)
-    if rank == 0:
-        cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if world > 1 and args.workload == HEADLINE and use_dist:
+            try:
+                config3 = _config3_beside(dev, rank, world, dist, args)
+            except Exception as e:           # (never takes the headline down with it -- but every rank must fail alike)
+                config3 = {"workload": CONFIG3, "error": f"{type(e).__name__}: {e}"}
+        if world == 1 and cfg.get("stepwise") and not args.no_stepwise:
+            stepwise = _stepwise_beside(dev, cfg["stepwise"], args)
+        if world == 1 and not args.no_also and args.workload == HEADLINE:
+            del job
+            torch.cuda.empty_cache()
+            also = _side_measurements(dev, args.also_budget)
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
             cpu = _cpu_baseline(cfg)
+    if rank == 0:
         trajectory, adjoint, train = cfg.get("trajectory", False), cfg.get("adjoint", False), cfg.get("train", False)
         line = {
             "metric": "SDE steps/sec (batch x timesteps / sec)", "value": value, "unit": "trajectory-steps/s",

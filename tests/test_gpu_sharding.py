@@ -107,7 +107,7 @@ def test_bench_multi_rank_logic_on_one_gpu(workload, launcher):
         sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
         "127.0.0.1", "--master-port", str(_free_port())]
     cmd = head + [os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2",
-                  "--warmup", "1"] + ([] if workload is None else ["--workload", workload])
+                  "--warmup", "1", "--full"] + ([] if workload is None else ["--workload", workload])
     proc = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert proc.returncode == 0, proc.stderr[-3000:]
     lines = [line for line in proc.stdout.splitlines() if line.startswith("{")]
@@ -170,7 +170,8 @@ def test_bench_one_rank_over_rccl_matches_the_plain_run():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     for key in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR", "TSDE_BENCH_SHARE_GPU"):
         env.pop(key, None)
-    tail = [os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "2", "--no-also", "--no-cpu-baseline"]
+    tail = [os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "2", "--full", "--no-also",
+            "--no-cpu-baseline"]
     dist = _run_bench([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                        "--master-addr", "127.0.0.1", "--master-port", str(_free_port())] + tail, env, root)
     plain = _run_bench([sys.executable] + tail, env, root)

@@ -651,6 +651,38 @@ def test_bench_offline_counters_follow_the_sources_of_the_kernels_they_measured(
     assert all("skipped" in also[w] for w in bench.ALSO[3:])
 
 
+def test_bench_dump_outputs_writes_float_arrays_within_the_limit(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR`: every array the last timed solve returned as DIR/<name>.npy in float32 (float64
+    kept), whole under the limit; over it, a seeded sample of rows that is the same from run to run and keeps the total
+    under the limit."""
+    import importlib
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    bench = importlib.import_module("bench")
+    gen = torch.Generator().manual_seed(0)
+    kept = {"ys": torch.randn(2, 300, 8, generator=gen), "y0_grad": torch.randn(300, 8, generator=gen).double(),
+            "grad_w": torch.randn(8, generator=gen).bfloat16(), "absent": None}
+    bench._dump_outputs(kept, str(tmp_path / "whole"))
+    assert sorted(os.listdir(tmp_path / "whole")) == ["grad_w.npy", "y0_grad.npy", "ys.npy"]
+    ys = np.load(tmp_path / "whole" / "ys.npy")
+    assert ys.dtype == np.float32 and np.array_equal(ys, kept["ys"].numpy())
+    assert np.load(tmp_path / "whole" / "y0_grad.npy").dtype == np.float64
+    assert np.load(tmp_path / "whole" / "grad_w.npy").dtype == np.float32
+    limit = 20000
+    monkeypatch.setattr(bench, "DUMP_LIMIT", limit)
+    for run in ("a", "b"):
+        bench._dump_outputs(kept, str(tmp_path / run))
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["grad_w_sample.npy", "y0_grad_sample.npy", "ys_sample.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / n) - 128 for n in names) <= limit
+    sample = np.load(tmp_path / "a" / "ys_sample.npy")
+    assert sample.shape[1] == 8 and 0 < sample.shape[0] < 600
+    assert all(np.array_equal(np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)) for n in names)
+    rows = {tuple(r) for r in kept["ys"].numpy().reshape(-1, 8)}
+    assert all(tuple(r) in rows for r in sample)
+
+
 _FINGERPRINT_GLOBAL_SCALE = 1.5
 
 

@@ -8,7 +8,7 @@ OUT=$R/gpurun_out/round_$TAG
 mkdir -p $OUT
 cd $R
 # 1. the default bench line (what the driver runs), on its own
-python bench.py > $OUT/bench_c2_default.json 2> $OUT/bench_c2_default.err
+python bench.py --full > $OUT/bench_c2_default.json 2> $OUT/bench_c2_default.err
 # 2. default bench under rocprofv3: kernel trace + stats
 tools/profile.sh $TAG > $OUT/bench_c2_rocprofv3_summary.txt 2>&1
 cp gpurun_out/prof_$TAG/bench_under_trace.json $OUT/bench_c2_under_trace.json 2>/dev/null
@@ -29,7 +29,7 @@ done
 # 4. matrix-core kernels: MFMA busy / LDS counters (sampling kernel; adjoint kernel)
 tools/profile_mlp.sh $TAG > $OUT/mlp_sampling_kernel_rocprofv3.txt 2>&1
 ( cd /tmp && export TMPDIR=/tmp
-  CMD="python $R/bench.py --workload c5_adjoint_mlp_b32768_d128_s500 --steps 2 --warmup 1 --no-cpu-baseline"
+  CMD="python $R/bench.py --workload c5_adjoint_mlp_b32768_d128_s500 --steps 2 --warmup 1 --full --no-cpu-baseline"
   rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAIT_INST_ANY --kernel-trace --output-format csv -d $OUT/pmc_adjoint -o bench -- $CMD > /dev/null 2> $OUT/pmc_adjoint.log
   python - "$OUT" > $OUT/mlp_adjoint_kernel_pmc.txt <<'PY'
 import csv, glob, os, sys

@@ -16,11 +16,11 @@ for STAGE in "$@"; do
   case $STAGE in
     bench)      # the default bench line (what the driver runs), on its own; bench_also.json beside it
       T0=$SECONDS
-      python bench.py > $OUT/bench_c2_default.json 2> $OUT/bench_c2_default.err
+      python bench.py --full > $OUT/bench_c2_default.json 2> $OUT/bench_c2_default.err
       echo "bench.py wall seconds: $((SECONDS - T0))" | tee -a $OUT/bench_c2_default.err
       cp bench_also.json $OUT/bench_also_default_budget.json 2>/dev/null ;;
     also)       # every side measurement, without the default run's time budget
-      python bench.py --also-budget 0 --no-cpu-baseline > $OUT/bench_c2_all_side_measurements.json 2> $OUT/bench_also.err
+      python bench.py --full --also-budget 0 --no-cpu-baseline > $OUT/bench_c2_all_side_measurements.json 2> $OUT/bench_also.err
       cp bench_also.json $OUT/bench_also.json 2>/dev/null ;;
     trace)      # the default bench under rocprofv3 (kernel trace + stats), at the shipped sources
       tools/profile.sh $TAG > $OUT/bench_c2_rocprofv3_summary.txt 2>&1

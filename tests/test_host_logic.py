@@ -897,3 +897,166 @@ def test_pure_call_counters_are_told_from_state_that_reaches_the_dynamics():
 
 def _helper_that_reads_the_counter(sde):
     return 1.0 if sde._nfe < 10 else 2.0
+
+
+# ---- the trust ledger of the recognised routes (trust.py) ----------------------------------------------------------------
+class _LedgerSolver:
+    """What `trust.open_book` reads of a solver: its SDE object and options (no device, no kernel)."""
+
+    def __init__(self, sde, options=None):
+        self.sde, self.options = sde, dict(options or {})
+
+
+class _Form:
+    def __init__(self, structure):
+        self._structure = structure
+
+    def structure(self):
+        return self._structure
+
+
+def test_ledger_caps_refusals_at_16_and_verdicts_at_32_with_their_counter_rates_and_solve_counts(monkeypatch):
+    from torchsde_amd import trust
+    monkeypatch.setattr(solvers, "VERIFY_EVERY", 5)
+    sde = problems.make("gbm_ito", d=4)
+    solver = _LedgerSolver(sde, {"assume_pure": True})
+    for i in range(16):
+        trust.open_book(solver, who=f"route {i}").refuse(f"reason {i}")
+    book = getattr(sde, trust.ATTR)
+    assert len(book["refused"]) == 16 and (("assumed pure",), (), "route 15") in book["refused"]
+    trust.open_book(solver, who="route 16").refuse("reason 16")
+    assert book["refused"] == {(("assumed pure",), (), "route 16"): "reason 16"}
+    ledger = trust.open_book(solver)
+    y0 = torch.zeros(8, 4)
+    keys = [ledger.key(_Form(("form", i)), y0) for i in range(33)]
+    assert keys[0] == (("form", 0), (), "_LedgerSolver", sde.sde_type, 4, torch.float32, 8)
+    for key in keys[:32]:
+        ledger.file(key, True, counter_rate={"_nfe": 2})
+        assert ledger.verdict(key) == (True, False)
+    assert len(book["trusted"]) == len(book["counter_rate"]) == len(book["solves"]) == 32
+    assert ledger.counter_rate(keys[0]) == {"_nfe": 2}
+    ledger.file(keys[32], "the trajectory kernel did not reproduce the stepwise solve")
+    assert book["trusted"] == {keys[32]: "the trajectory kernel did not reproduce the stepwise solve"}
+    assert book["counter_rate"] == {} and book["solves"] == {} and ledger.counter_rate(keys[0]) is None
+
+
+def test_ledger_reverifies_every_nth_solve_and_raises_when_that_fails(monkeypatch):
+    from torchsde_amd import trust
+    sde = problems.make("gbm_ito", d=4)
+    ledger = trust.open_book(_LedgerSolver(sde))
+    key = ledger.key(_Form(("form",)), torch.zeros(8, 4), "autograd")
+    ledger.file(key, True)
+    monkeypatch.setattr(solvers, "VERIFY_EVERY", 0)
+    assert [ledger.verdict(key) for _ in range(4)] == [(True, False)] * 4           # 0: never again
+    monkeypatch.setattr(solvers, "VERIFY_EVERY", 3)
+    assert [ledger.verdict(key) for _ in range(6)] == [(True, False), (True, False), (None, True)] * 2
+    ledger.file(key, True, reverify=True)
+    assert ledger.recorded(key) is True
+    with pytest.raises(RuntimeError, match="re-verification"):
+        ledger.file(key, "the trajectory kernel did not reproduce the stepwise solve", reverify=True)
+    assert ledger.verdict(key) == ("the trajectory kernel did not reproduce the stepwise solve", False)
+
+
+def test_ledger_takes_no_fingerprint_on_a_trusted_lookup_and_at_most_one_per_solve(monkeypatch):
+    from torchsde_amd import graph, trust
+    monkeypatch.setattr(trust, "rng_states", lambda device: (torch.get_rng_state(),))
+    true_state, walked = graph.python_state, []
+
+    def counting(*args, **kwargs):
+        walked.append(1)
+        return true_state(*args, **kwargs)
+    monkeypatch.setattr(graph, "python_state", counting)
+    sde = problems.make("gbm_ito", d=4)
+    solver = _LedgerSolver(sde)
+    ledger = trust.open_book(solver)
+    key = ledger.key(_Form(("form",)), torch.zeros(8, 4))
+    ledger.file(key, True)
+    ledger = trust.open_book(solver)
+    assert not ledger.refused() and ledger.verdict(key) == (True, False) and not walked
+    ledger.refuse("the drift is not a tracked function of the state")
+    assert len(walked) == 1
+    ledger = trust.open_book(solver)
+    assert ledger.refused() and len(walked) == 2
+    ledger.refuse("again")
+    assert len(walked) == 2
+    sde.scale = 2.0                                  # another Python-side state: not refused there
+    ledger = trust.open_book(solver)
+    assert not ledger.refused() and len(walked) == 3
+    snapshot = ledger.snapshot(None)                 # (the side-effect check: a fresh fingerprint, and one after the calls)
+    assert snapshot[0] == ledger.state() and len(walked) == 4
+    assert ledger.side_effect(snapshot, None) is None and len(walked) == 5
+
+
+def test_ledger_side_effect_check_sees_python_side_state_and_random_generators(monkeypatch):
+    from torchsde_amd import trust
+    monkeypatch.setattr(trust, "rng_states", lambda device: (torch.get_rng_state(),))
+    sde = problems.make("gbm_ito", d=4)
+    ledger = trust.open_book(_LedgerSolver(sde))
+    snapshot = ledger.snapshot(None)
+    assert snapshot[0] is not None and ledger.side_effect(snapshot, None) is None
+    torch.randn(1)
+    assert ledger.side_effect(snapshot, None) == "calling f and g advances a random number generator"
+    sde.calls = [1]
+    assert ledger.side_effect(snapshot, None) == "calling f and g changes the object's Python-side state"
+    assert ledger.side_effect((None,) + snapshot[1:], None) == "calling f and g changes the object's Python-side state"
+
+
+def test_ledger_opens_no_book_for_counters_it_cannot_keep_nor_for_what_cannot_be_interpreted():
+    from torchsde_amd import trust
+
+    class Counted(problems.GBMDiag):
+        def __init__(self):
+            super().__init__(4, "ito")
+            self._nfe = 0
+
+        def f(self, t, y):
+            self._nfe += 1
+            return super().f(t, y)
+    counted = Counted()
+    assert trust.open_book(_LedgerSolver(counted)) is None and not hasattr(counted, trust.ATTR)
+    assert trust.open_book(_LedgerSolver(counted), keep_counters=True).counters == {"_nfe": {"f": 1}}
+    assert trust.open_book(_LedgerSolver(counted, {"assume_pure": True})).counters == {}
+    assert trust.open_book(_LedgerSolver(type("OptimizedModule", (), {"sde_type": "ito"})())) is None
+    sde = problems.make("gbm_ito", d=4)
+    ledger = trust.open_book(_LedgerSolver(sde), create=False)
+    assert ledger.book is None and not ledger.refused() and ledger.recorded(("any",)) is None
+    assert not hasattr(sde, trust.ATTR)
+    trust.open_book(_LedgerSolver(sde))
+    assert ledger.book is getattr(sde, trust.ATTR)
+
+
+def test_describe_reads_the_book_key_layout():
+    """`recognise.describe` (README) prints one line per verdict and refusal; the lines below are those of a hand-filled book."""
+    from torchsde_amd import recognise, trust
+
+    class Wrapper:
+        def __init__(self, base):
+            self._base_sde = base
+    base = type("Base", (), {})()
+    assert recognise.describe is trust.describe
+    assert recognise.describe(base)[0].startswith("nothing recorded: no solve of this object has reached the recognised route")
+    setattr(base, trust.ATTR, {
+        "refused": {(("state", 1), (), "Euler"): "the drift is not a tracked function of the state",
+                    (("state", 2), (), "ReversibleHeun:kernels"): "calling f and g advances a random number generator"},
+        "trusted": {
+            ((("affine", 1), ("affine", 2)), (), "Euler", "ito", 4, torch.float32, 64): True,
+            ((("perceptron", 3), ("affine", 2)), (), "MilsteinIto", "ito", 8, torch.float32, 128):
+                "the trajectory kernel did not reproduce the stepwise solve",
+            ((("program", "diagonal"), ("program", "diagonal")), (), "SRK", "ito", 2, torch.float64, 16, "autograd"): True,
+            ((("affine", 1), ("const", 0), ("table", 3)), (), "Midpoint", "stratonovich", 4, torch.float32, 8): True,
+            ((("neural", 1), ("neural", 2)), (), "ReversibleHeun", "stratonovich", 4, torch.float32, 8, "kernels",
+             "autograd"): True,
+        },
+    })
+    assert recognise.describe(Wrapper(base)) == [
+        "[Euler, ito, batch = 64, d = 4, torch.float32] f: affine, g: affine: trajectory kernel",
+        "[MilsteinIto, ito, batch = 128, d = 8, torch.float32] perceptron drift: stays stepwise: the trajectory kernel did "
+        "not reproduce the stepwise solve",
+        "[SRK, ito, batch = 16, d = 2, torch.float64] expression program, diagonal noise: trajectory kernel (sensitivity "
+        "kernel: autograd)",
+        "[Midpoint, stratonovich, batch = 8, d = 4, torch.float32] f: affine, g: const: trajectory kernel with "
+        "per-stage-time coefficient rows",
+        "[ReversibleHeun, stratonovich, batch = 8, d = 4, torch.float32] f: neural, g: neural: trajectory kernel",
+        "[Euler] stays stepwise: the drift is not a tracked function of the state",
+        "[ReversibleHeun:kernels] stays stepwise: calling f and g advances a random number generator",
+    ]

@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from . import _native
+from . import timegrid
 from ._native import Noise, Seg
 
 
@@ -616,6 +617,106 @@ class TrajectorySchedule:
         n = k_hi - k_lo
         return TrajectorySchedule.cached(self.host_rows[k_lo:k_hi], self.host_cells[k_lo:k_hi], range(1, n + 1),
                                          [(0.0, 1.0)] * n, self.device, self.dtype)
+
+
+class SolveSteps:
+    """The steps of a fixed-step solve (a timegrid.TimeGrid) as cells of a BrownianInterval, one cell per step: their
+    `tsde_traj_t.step_rows`, and the output map. Built by `solve_steps`."""
+    __slots__ = ("grid", "cells", "h", "rows", "out_step", "out_w")
+
+    def __init__(self, grid, cells, h, rows, out_step, out_w):
+        self.grid, self.cells, self.h, self.rows, self.out_step, self.out_w = grid, cells, h, rows, out_step, out_w
+
+    @property
+    def on_boundaries(self):
+        """Every output on a step boundary (no interpolation)."""
+        return all(w0 == 0.0 and w1 == 1.0 for (w0, w1) in self.out_w)
+
+    def schedule(self, device, dtype, dt=None, every_step=False):
+        """The `TrajectorySchedule`. `dt`: step sizes other than the grid's (those of an adjoint's backward solve);
+        `every_step`: one output per step."""
+        rows = self.rows if dt is None else step_rows(self.grid, self.h, dt)
+        out_step, out_w = self.out_step, self.out_w
+        if every_step:
+            n = self.grid.n_steps
+            out_step, out_w = range(1, n + 1), [(0.0, 1.0)] * n
+        return TrajectorySchedule.cached(rows, self.cells, out_step, out_w, device, dtype)
+
+
+def step_rows(grid, h, dt=None):
+    """`tsde_traj_t.step_rows` (include/torchsde_amd.h) of the steps of `grid` on cells of widths `h`: dt, dt/2, 1/dt,
+    sqrt dt, sqrt h, sqrt(h/12), h, t_k. `dt`: other step sizes than the grid's."""
+    dt = grid.dt if dt is None else dt
+    np_dtype = grid.t.dtype.type
+    rows = np.zeros((grid.n_steps, 8), dtype=np.float64)
+    # each entry is rounded in ts.dtype like the stepwise path's scalars, then (TrajectorySchedule) cast to the state dtype
+    rows[:, 0] = dt
+    rows[:, 1] = np_dtype(0.5) * dt
+    rows[:, 2] = np_dtype(1) / dt
+    rows[:, 3] = np.sqrt(dt)
+    rows[:, 4] = np.sqrt(h)
+    rows[:, 5] = np.sqrt(h / 12.0)
+    rows[:, 6] = h
+    rows[:, 7] = grid.t[:-1]         # t_k, the time a step starts at (read by tsde_trajectory_mlp_general only)
+    return rows
+
+
+def solve_steps(grid, bm):
+    """The `SolveSteps` of `grid` on the BrownianInterval `bm` -- which adopts the grid as its cell structure if it has none
+    yet -- or None when the grid has no step or a step is not exactly one cell."""
+    if grid.n_steps == 0:
+        return None
+    t64 = grid.t_f64()
+    bm.adopt_grid(t64)
+    cells = bm.match_grid(t64)
+    if cells is None:
+        return None
+    cells = np.asarray(cells, dtype=np.int64)
+    h = bm._edges[cells + 1] - bm._edges[cells]
+    # (the step rows of a grid the process has just seen -- every iteration of a training loop: remembered on the
+    #  grid object, which timegrid.build hands back for equal (ts, dt); valid for these cell widths)
+    memo = getattr(grid, "_step_rows", None)
+    if memo is not None and memo[0].shape == h.shape and np.array_equal(memo[0], h):
+        rows, out_step, out_w = memo[1:]
+    else:
+        rows = step_rows(grid, h)
+        out_step = [kc for (_, kc, _, _) in grid.outputs]
+        out_w = [(w0, w1) for (_, _, w0, w1) in grid.outputs]
+        grid._step_rows = (h.copy(), rows, out_step, out_w)
+    return SolveSteps(grid, cells, h, rows, out_step, out_w)
+
+
+_BACKWARD_DT = {}
+
+
+def backward_step_sizes(bm, ts_host, dt, cells, out_steps):
+    """The step sizes (in forward order) of the backward solve of an adjoint if its steps are the forward `cells` walked
+    backwards, else None. The backward solver builds its own grid on every [-ts[i], -ts[i-1]] (adjoint.py:97-112).
+    Remembered by content: a training loop asks the same question every iteration, and an example with 64 output times
+    (examples/sde_gan.py) builds 63 grids to answer it."""
+    key = (ts_host.tobytes(), str(ts_host.dtype), float(dt), np.asarray(cells).tobytes(), tuple(out_steps),
+           bm._edges.tobytes())
+    if key not in _BACKWARD_DT:
+        if len(_BACKWARD_DT) >= 32:
+            _BACKWARD_DT.clear()
+        _BACKWARD_DT[key] = _backward_step_sizes(bm, ts_host, dt, cells, out_steps)
+    return _BACKWARD_DT[key]
+
+
+def _backward_step_sizes(bm, ts_host, dt, cells, out_steps):
+    backward_dt = np.empty(len(cells), dtype=ts_host.dtype)
+    boundaries = [0] + list(out_steps)
+    for i in range(len(ts_host) - 1, 0, -1):
+        back = timegrid.build(np.array([-ts_host[i], -ts_host[i - 1]], dtype=ts_host.dtype), dt)
+        k_lo, k_hi = boundaries[i - 1], boundaries[i]
+        if back.n_steps != k_hi - k_lo:
+            return None
+        walked = bm.match_grid(-back.t_f64()[::-1])
+        if walked is None or not np.array_equal(np.asarray(walked, dtype=np.int64), cells[k_lo:k_hi]):
+            return None
+        backward_dt[k_lo:k_hi] = back.dt[::-1]
+    backward_dt.setflags(write=False)
+    return backward_dt
 
 
 def _coefficient_tables(coefs, d, schedule, dtype, method):

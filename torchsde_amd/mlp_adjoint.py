@@ -194,47 +194,18 @@ def route(sde, y0, ts, bm, method, adjoint_method, dt, adaptive, adjoint_adaptiv
     grid = timegrid.build(ts_host, dt)
     if grid.n_steps == 0 or any(not (w0 == 0.0 and w1 == 1.0) for (_, _, w0, w1) in grid.outputs):
         return None
-    t64 = grid.t_f64()
-    bm.adopt_grid(t64)
-    cells = bm.match_grid(t64)
-    if cells is None:
+    steps = K.solve_steps(grid, bm)
+    if steps is None:
         return None
-    cells = np.asarray(cells, dtype=np.int64)
-    out_steps = [kc for (_, kc, _, _) in grid.outputs]
-    np_dtype = grid.t.dtype.type
-    h = bm._edges[cells + 1] - bm._edges[cells]
-
-    def rows_for(dts):
-        rows = np.zeros((grid.n_steps, 8), dtype=np.float64)
-        rows[:, 0] = dts
-        rows[:, 1] = np_dtype(0.5) * dts
-        rows[:, 2] = np_dtype(1) / dts
-        rows[:, 3] = np.sqrt(dts)
-        rows[:, 4] = np.sqrt(h)
-        rows[:, 5] = np.sqrt(h / 12.0)
-        rows[:, 6] = h
-        return rows
-
-    # the backward solver builds its own grid on every [-ts[i], -ts[i-1]] (adjoint.py:97-112): its steps must be the
-    # forward cells walked backwards, and it is ITS step sizes the backward kernel is given
-    backward_dt = np.array(grid.dt, dtype=grid.dt.dtype)
-    boundaries = [0] + out_steps
-    for i in range(len(ts_host) - 1, 0, -1):
-        back = timegrid.build(np.array([-ts_host[i], -ts_host[i - 1]], dtype=ts_host.dtype), dt)
-        k_lo, k_hi = boundaries[i - 1], boundaries[i]
-        if back.n_steps != k_hi - k_lo:
-            return None
-        walked = bm.match_grid(-back.t_f64()[::-1])
-        if walked is None or not np.array_equal(np.asarray(walked, dtype=np.int64), cells[k_lo:k_hi]):
-            return None
-        backward_dt[k_lo:k_hi] = back.dt[::-1]
-    schedule = K.TrajectorySchedule.cached(rows_for(grid.dt), cells, out_steps, [(0.0, 1.0)] * len(out_steps), y0.device,
-                                           y0.dtype)
-    backward_schedule = K.TrajectorySchedule.cached(rows_for(backward_dt), cells, out_steps,
-                                                    [(0.0, 1.0)] * len(out_steps), y0.device, y0.dtype)
+    # (it is the backward solver's step sizes the backward kernel is given)
+    backward_dt = K.backward_step_sizes(bm, ts_host, dt, steps.cells, steps.out_step)
+    if backward_dt is None:
+        return None
+    schedule = steps.schedule(y0.device, y0.dtype)
+    backward_schedule = steps.schedule(y0.device, y0.dtype, dt=backward_dt)
     ys = _MlpAdjointFn.apply(spec[-2], tuple(spec[-1]), code, sde.sde_type == SDE_TYPES.ito,
                              _BACKWARD_KINDS[adjoint_method], schedule, backward_schedule,
-                             tuple(int(k) for k in out_steps), bm, y0, *own)
+                             tuple(int(k) for k in steps.out_step), bm, y0, *own)
     if ys.grad_fn is not None:           # what a second-order backward pass needs (`ys.grad_fn` is the Function's ctx)
         ys.grad_fn.generic = (sde, ts_host, dt, own)
     return ys

@@ -43,6 +43,7 @@ import torch
 from torch.utils._python_dispatch import TorchDispatchMode
 
 from . import _native
+from .trust import describe  # noqa: F401  (documented as recognise.describe)
 
 # TSDE_RECOGNISE=0 switches the route off for the process (tests of the stepwise machinery also clear `ENABLED`)
 ENABLED = os.environ.get("TSDE_RECOGNISE", "1").strip().lower() not in ("0", "false", "off")
@@ -1590,30 +1591,3 @@ def recognise(sde, t, y0, differentiable=False, times=None, rows=None):
     found.users_tensors = interp.seen
     found._alive = interp.keep        # (the ids above stay meaningful for as long as this object lives)
     return found
-
-
-def describe(sde):
-    """What the recognised route has decided about `sde` so far, one line per form / refusal: the answer to "why is my
-    solve (not) one kernel launch?" (cf. `graph.describe_cache` for the stepwise route's launch graphs)."""
-    base = sde
-    while hasattr(base, "_base_sde"):
-        base = base._base_sde
-    book = getattr(base, "_tsde_recognised", None)
-    if not book:
-        return ["nothing recorded: no solve of this object has reached the recognised route (see the conditions in "
-                "solvers.BaseSDESolver._integrate_recognised: diagonal noise, fixed step, this package's BrownianInterval, "
-                "a CUDA state of at least 8 rows)"]
-    lines = []
-    for key, verdict in book["trusted"].items():
-        structure, _, solver, sde_type, d, dtype, batch = key[:7]
-        kind = ("perceptron drift" if structure[0][0] == "perceptron"
-                else f"expression program, {structure[0][1]} noise" if structure[0][0] == "program"
-                else f"f: {structure[0][0]}, g: {structure[1][0]}")
-        timed = any("table" in part for part in structure if isinstance(part, tuple))
-        route = ("trajectory kernel" + (" with per-stage-time coefficient rows" if timed else "")
-                 + (" (sensitivity kernel: autograd)" if key[7:] == ("autograd",) else ""))
-        lines.append(f"[{solver}, {sde_type}, batch = {batch}, d = {d}, {dtype}] {kind}: "
-                     + (route if verdict is True else f"stays stepwise: {verdict}"))
-    for (_, _, solver), reason in book["refused"].items():
-        lines.append(f"[{solver}] stays stepwise: {reason}")
-    return lines

@@ -22,6 +22,7 @@ from . import _native
 from . import closed_form
 from . import kernels as K
 from . import timegrid
+from . import trust
 from .brownian import BrownianInterval
 from .kernels import NoiseSpec
 from .settings import LEVY_AREA_APPROXIMATIONS, METHOD_OPTIONS, METHODS, NOISE_TYPES, SDE_TYPES
@@ -94,10 +95,6 @@ def _update_step_size(error_estimate, prev_step_size, prev_error_ratio, safety=0
         facmin = 1.0
     factor = min(facmax, max(facmin, factor))
     return prev_step_size * factor, prev_error_ratio
-
-
-class _Found(Exception):
-    """Control flow of `_integrate_recognised`: the additive route found its form, skip the other interpreters."""
 
 
 class BaseSDESolver:
@@ -218,17 +215,10 @@ class BaseSDESolver:
         coefficients = self._closed_form_coefficients(y0)
         if coefficients is not None:
             ys = self._integrate_trajectory(coefficients, y0, ts)
-            if ys is not None:
-                return ys, self._extra
         else:
-            self._counter_start = None
             ys = self._integrate_recognised(y0, ts)
-            if ys is not None:
-                return ys, self._extra
-            if self._counter_start is not None:       # (the probe calls of the interpretation are not steps of the solve)
-                owner, start = self._counter_start
-                for name, value in start.items():
-                    setattr(owner, name, value)
+        if ys is not None:
+            return ys, self._extra
         from . import graph
         mode = graph.mode_of(self.options)
         if mode is True:
@@ -425,8 +415,9 @@ class BaseSDESolver:
             return ("differentiable",) + tuple(own)
         return spec[1:]
 
-    # ---- unchanged user modules whose f and g are per-channel expressions (recognise.py) ----------------------
-    _RECOGNISED_ATTR = "_tsde_recognised"
+    # ---- unchanged user modules whose f and g are per-channel expressions (recognise.py; their trust ledger: trust.py) ---
+    _RECOGNISED_ATTR = trust.ATTR
+    _may_be_interpreted = staticmethod(trust.may_be_interpreted)
 
     def _integrate_recognised(self, y0, ts):
         """The solve as ONE trajectory-kernel launch when the user's own, unchanged drift and diffusion turn out to be
@@ -442,7 +433,7 @@ class BaseSDESolver:
         per step). That first solve returns the stepwise result. A refusal is remembered per Python-side state of the
         object, so code that does not fit costs one interpretation, not one per solve.
         `options={"trajectory_kernel": False}` opts out."""
-        from . import graph, recognise
+        from . import recognise
         from .sde import ForwardSDE
         sde = self.sde
         # diagonal noise: every scheme with an in-register form; drift AND diffusion networks (recognise.Recognised.neural:
@@ -464,6 +455,21 @@ class BaseSDESolver:
             return None
         if self._tracks_grad(y0):
             return self._integrate_recognised_with_grad(y0, ts) if (elementwise or programs) else None
+        bm = self._recognisable_bm(y0, ts)
+        if bm is None or (additive and (not hasattr(sde._base_sde, "f") or not hasattr(sde._base_sde, "g"))):
+            return None
+        ledger = trust.open_book(self, keep_counters=True)
+        if ledger is None:
+            return None
+        start = {name: getattr(ledger.base, name) for name in ledger.counters}
+        ys = self._solve_recognised(ledger, start, y0, ts, bm, (elementwise, networks, programs, additive), precision)
+        if ys is None:
+            for name, value in start.items():        # (the probe calls of the interpretation are not steps of the solve)
+                setattr(ledger.base, name, value)
+        return ys
+
+    def _recognisable_bm(self, y0, ts):
+        """This package's BrownianInterval of this solve if it and the state are what the recognised routes take, else None."""
         bm = self._native_bm()
         if (bm is None or y0.dim() != 2 or len(bm.shape) != 2 or bm.shape[0] != y0.shape[0] or not y0.is_cuda
                 or y0.shape[0] < 8
@@ -471,49 +477,98 @@ class BaseSDESolver:
                 or bm._rootW is not None or bm._rootH is not None or torch.cuda.is_current_stream_capturing()
                 or (self._program_code() == _native.TRAJ_SRK and not bm._have_H)):
             return None
-        if additive and (not hasattr(sde._base_sde, "f") or not hasattr(sde._base_sde, "g")):
+        if self.sde.noise_type == NOISE_TYPES.diagonal and tuple(bm.shape) != tuple(y0.shape):
             return None
-        if sde.noise_type == NOISE_TYPES.diagonal and tuple(bm.shape) != tuple(y0.shape):
+        if self.sde.noise_type == NOISE_TYPES.scalar and tuple(bm.shape) != (y0.shape[0], 1):
             return None
-        if sde.noise_type == NOISE_TYPES.scalar and tuple(bm.shape) != (y0.shape[0], 1):
-            return None
-        chain, base = graph._wrapper_chain(sde)
-        if not self._may_be_interpreted(base):
+        return bm
+
+    def _solve_recognised(self, ledger, start, y0, ts, bm, kinds, precision):
+        """`_integrate_recognised` past the gate: refused? -> interpret -> key -> verdict -> launch, or verify and file.
+        `start`: the call counters' values before the solve (this route keeps them at the stepwise loop's values)."""
+        from . import recognise
+        if ledger.refused():
             return None
         try:
-            book = base.__dict__.setdefault(self._RECOGNISED_ATTR, {"refused": {}, "trusted": {}})
-        except AttributeError:
+            found, spec, times = self._interpret(ledger, y0, ts, kinds, precision)
+        except recognise.NotElementwise as e:
+            return ledger.refuse(str(e))
+        if kinds[3] and tuple(bm.shape) != (y0.shape[0], found.m):
             return None
-        # Pure call counters (`self._nfe += 1` in the reference's Ex* test problems): not state of the dynamics (graph.
-        # call_counters decides that on the bytecode), so they neither refuse the form nor lose their meaning -- the verifying
-        # solve learns by how much the stepwise loop advances them per step, and a kernel solve leaves them at that value.
-        # `options={"assume_pure": True}` (or the attribute `tsde_assume_pure = True` on the SDE object): the USER vouches that
-        # whatever Python-side state their f and g touch (counters, logs, caches) does not reach the dynamics -- the documented
-        # switch for modules the checks below would keep stepwise. Nothing is fingerprinted then, counters run once per solve
-        # instead of once per step; the both-routes comparison of the first solve (and TSDE_VERIFY_EVERY) still applies.
-        assume_pure = self._assume_pure(base)
-        counters = {} if assume_pure else graph.call_counters(base)
-        ignore = frozenset(counters)
-        counter_start = {name: getattr(base, name) for name in counters}
-        self._counter_start = (base, counter_start) if counters else None
-
-        def state_of():
-            return ("assumed pure",) if assume_pure else graph.python_state(base, ignore=ignore)
-        state = None
-        if book["refused"]:
-            state = state_of()
-            if state is None or (state, chain, type(self).__name__) in book["refused"]:
+        if spec[0] in ("neural", "neural_rheun") and (tuple(bm.shape) != (y0.shape[0], spec[4]) or y0.numel() >= 2 ** 30):
+            return None
+        if spec[0] == "mlp_diagonal":
+            # perceptron drift: the sampling kernel's own limits (cf. `_closed_form_coefficients`)
+            code = self._trajectory_code()
+            if (code not in (_native.TRAJ_EULER, _native.TRAJ_MILSTEIN_ITO, _native.TRAJ_MILSTEIN_STRAT,
+                             _native.TRAJ_MIDPOINT, _native.TRAJ_SRK) or bm._elem0 % 4 != 0 or y0.numel() >= 2 ** 30):
                 return None
-
-        def refuse(reason):
-            key = (state if state is not None else state_of(), chain, type(self).__name__)
-            if key[0] is not None:
-                if len(book["refused"]) >= 16:
-                    book["refused"].clear()
-                book["refused"][key] = reason
+        key = ledger.key(found, y0, *(("bf16x3",) if spec[0] == "neural" and spec[2].precision != _native.PRECISION_F32
+                                      else ()))
+        verdict, reverify = ledger.verdict(key)
+        launch = spec[1:] if spec[0] == "affine_diagonal" else spec       # (what `_integrate_trajectory` takes)
+        counters, base = ledger.counters, ledger.base
+        if verdict is True:
+            rate = ledger.counter_rate(key) if counters else {}
+            if rate is None or set(rate) != set(counters):
+                return None
+            ys = self._integrate_trajectory(launch, y0, ts)
+            if ys is not None and counters:
+                n_steps = timegrid.build(timegrid.ts_to_host(ts), self.dt).n_steps
+                for name in counters:
+                    setattr(base, name, start[name] + rate[name] * n_steps)
+            return ys
+        if verdict is not None:
             return None
+        # first solve of this form: is the interpretation repeatable and free of side effects, and does the kernel
+        # reproduce the stepwise solve?
+        snapshot = ledger.snapshot(y0.device)
+        try:
+            again = self._interpret_again(spec, y0, ts, times)
+        except recognise.NotElementwise as e:
+            return ledger.refuse(str(e))
+        side_effect = ledger.side_effect(snapshot, y0.device)
+        if side_effect is not None:
+            return ledger.refuse(side_effect)
+        same = len(again) == len(spec) and all(
+            (torch.equal(a, b) if torch.is_tensor(a) else a == b) for a, b in zip(again, spec))
+        if not same:
+            ledger.file(key, "two interpretations of the same code (probes of 2 and 5 rows) gave different coefficients: "
+                        "they depend on the batch size or on how often the code has run", reverify)
+            return None
+        fast = self._integrate_trajectory(launch, y0, ts)
+        if fast is None:
+            return None                  # (grid and Brownian cells do not line up: nothing learnt about the form)
+        self._extra = ()
+        for name, value in start.items():       # (the interpretations' calls are not steps: count the real loop only)
+            setattr(base, name, value)
+        stepwise = self._run(self._plan(y0, ts), y0)
+        counter_rate = {}
+        if counters:
+            n_steps = timegrid.build(timegrid.ts_to_host(ts), self.dt).n_steps
+            advanced = {name: getattr(base, name) - start[name] for name in counters}
+            if any(v % n_steps for v in advanced.values()):
+                ledger.file(key, "a call counter does not advance by a fixed amount per step", reverify)
+                return stepwise
+            counter_rate = {name: v // n_steps for name, v in advanced.items()}
+        rtol, atol = (1e-4, 1e-5) if y0.dtype == torch.float32 else (1e-9, 1e-11)
+        if spec[0] in ("mlp_diagonal", "neural", "neural_additive", "neural_rheun"):      # the matrix cores sum the layers' products in another order than the library
+            rtol, atol = 1e-3, 1e-4
+        both_nan = fast.isnan() & stepwise.isnan()
+        close = ((fast - stepwise).abs() <= atol + rtol * stepwise.abs()) | both_nan | (fast == stepwise)
+        ledger.file(key, True if bool(close.all()) else "the trajectory kernel did not reproduce the stepwise solve",
+                    reverify, counter_rate)
+        return stepwise
 
-        times = None
+    def _interpret(self, ledger, y0, ts, kinds, precision):
+        """The interpreters of `_integrate_recognised` in turn, the first that holds the code wins: (found, spec, times) --
+        `times` the stage times the coefficient tables are taken at, or None -- or NotElementwise with every reason.
+        Additive noise: the drift a program, the diffusion tabulated at the scheme's stage times. Otherwise the single-function
+        forms, then per-stage-time coefficient tables (f, g use t), then expression programs, then row-coupled systems;
+        drift and diffusion networks: two-layer nets, then deep nets."""
+        from . import recognise
+        sde = self.sde
+        elementwise, networks, programs, additive = kinds
         milstein = self._program_code() in (_native.TRAJ_MILSTEIN_ITO, _native.TRAJ_MILSTEIN_STRAT)
 
         def as_program(first_reason):
@@ -536,190 +591,95 @@ class BaseSDESolver:
                     return found, found.spec()
                 except recognise.NotElementwise as e2:
                     raise recognise.NotElementwise(f"{reason}; as a row-coupled system: {e2}") from None
-            book["program"] = (chain, type(self).__name__)
+            ledger.remember("program")
             return found, spec
 
+        times = None
         try:
+            if additive:
+                times = self._stage_times(ts, y0.device, slots=self._ADDITIVE_SLOTS[self._additive_code()])
+                found = recognise.recognise_additive(sde, ts[0], y0, times)
+                return found, found.spec(), times
+            if ledger.remembers("program"):
+                raise recognise.NotElementwise("(remembered: an expression program)")
+            if ledger.remembers("uses_t"):
+                raise recognise.DependsOnTime("(remembered)")         # skip the pass that is known to end at t
+            found = recognise.recognise(sde, ts[0], y0)
+        except recognise.DependsOnTime:
+            ledger.remember("uses_t")
+            # f, g use t in their arithmetic: interpret once more with ALL the times at which this scheme evaluates them
+            # (its stage times of every step); the kernels then read one coefficient row per stage time
+            times = self._stage_times(ts, y0.device) if elementwise else None
             try:
-                if additive:
-                    times = self._stage_times(ts, y0.device, slots=self._ADDITIVE_SLOTS[self._additive_code()])
-                    found = recognise.recognise_additive(sde, ts[0], y0, times)
-                    spec = found.spec()
-                    if tuple(bm.shape) != (y0.shape[0], found.m):
-                        return None
-                    raise _Found()
-                if book.get("program") == (chain, type(self).__name__):
-                    raise recognise.NotElementwise("(remembered: an expression program)")
-                if book.get("uses_t") == (chain, type(self).__name__):
-                    raise recognise.DependsOnTime("(remembered)")         # skip the pass that is known to end at t
-                found = recognise.recognise(sde, ts[0], y0)
-            except recognise.DependsOnTime:
-                book["uses_t"] = (chain, type(self).__name__)
-                # f, g use t in their arithmetic: interpret once more with ALL the times at which this scheme evaluates them
-                # (its stage times of every step); the kernels then read one coefficient row per stage time
-                times = self._stage_times(ts, y0.device) if elementwise else None
-                try:
-                    if times is None:
-                        raise recognise.NotElementwise("no coefficient tables for this scheme")
-                    found = recognise.recognise(sde, ts[0], y0, times=times)
-                except recognise.NotElementwise as e:
-                    # ... or t takes part in arithmetic that is not affine in the state: t as an operand of a program
-                    times = None
-                    found, spec = as_program("drift or diffusion depends on t, and not only through arithmetic that "
-                                             f"broadcasts ({e})")
-            except _Found:
-                pass
+                if times is None:
+                    raise recognise.NotElementwise("no coefficient tables for this scheme")
+                found = recognise.recognise(sde, ts[0], y0, times=times)
             except recognise.NotElementwise as e:
-                if additive:
+                # ... or t takes part in arithmetic that is not affine in the state: t as an operand of a program
+                return as_program("drift or diffusion depends on t, and not only through arithmetic that broadcasts "
+                                  f"({e})") + (None,)
+        except recognise.NotElementwise as e:
+            if additive:
+                raise
+            return as_program(str(e)) + (times,)
+        if found.neural:
+            if not networks or times is not None:
+                raise recognise.NotElementwise("drift and diffusion networks, but no neural-SDE kernel for this scheme")
+            try:
+                if self._neural_code() is None:
+                    raise recognise.NotElementwise("no two-layer neural-SDE kernel for this scheme")
+                spec = found.neural_spec(sde.noise_type)
+            except recognise.NotElementwise as e:
+                # deeper nets, LipSwish, a closing tanh -- or a scheme only the deep kernel has (Heun, Euler-Heun)
+                if self._deep_code() is None or y0.dtype != torch.float32:
                     raise
-                found, spec = as_program(str(e))
-            if isinstance(found, (recognise.RecognisedProgram, recognise.RecognisedAdditive)) \
-                    or getattr(found, "statements", None) is not None:       # (programs, additive tables, row-coupled systems)
-                pass
-            elif found.neural:
-                if not networks or times is not None:
-                    raise recognise.NotElementwise("drift and diffusion networks, but no neural-SDE kernel for this scheme")
                 try:
-                    if self._neural_code() is None:
-                        raise recognise.NotElementwise("no two-layer neural-SDE kernel for this scheme")
-                    spec = found.neural_spec(sde.noise_type)
-                except recognise.NotElementwise as e:
-                    # deeper nets, LipSwish, a closing tanh -- or a scheme only the deep kernel has (Heun, Euler-Heun)
-                    if self._deep_code() is None or y0.dtype != torch.float32:
-                        raise
-                    try:
-                        spec = found.deep_spec(sde.noise_type)
-                    except recognise.NotElementwise as e2:
-                        raise recognise.NotElementwise(f"{e}; as deeper networks: {e2}") from None
-                if tuple(bm.shape) != (y0.shape[0], spec[4]) or y0.numel() >= 2 ** 30:
-                    return None
-                if precision == "bf16x3" and sde.noise_type == NOISE_TYPES.general and spec[0] == "neural":
-                    # opt-in: the diffusion net's second layer on split-bf16 products (csrc/mlp_general.hip SPLIT); NOT the
-                    # reference's arithmetic -- the default, and everything benchmarked as such, stays exact f32
-                    spec[2].precision = _native.PRECISION_BF16X3
-            elif not elementwise:
-                raise recognise.NotElementwise(f"{sde.noise_type} noise whose drift and diffusion are not both networks")
-            else:
-                try:
-                    spec = found.spec()
-                except recognise.NotElementwise as e:
-                    found, spec = as_program(str(e))
-        except recognise.NotElementwise as e:
-            return refuse(str(e))
-        if spec[0] == "mlp_diagonal":
-            # perceptron drift: the sampling kernel's own limits (cf. `_closed_form_coefficients`)
-            code = self._trajectory_code()
-            if (code not in (_native.TRAJ_EULER, _native.TRAJ_MILSTEIN_ITO, _native.TRAJ_MILSTEIN_STRAT,
-                             _native.TRAJ_MIDPOINT, _native.TRAJ_SRK) or bm._elem0 % 4 != 0 or y0.numel() >= 2 ** 30):
-                return None
-        key = self._recognised_key(found, chain, y0)
-        if spec[0] == "neural" and spec[2].precision != _native.PRECISION_F32:
-            key = key + ("bf16x3",)
-        verdict = book["trusted"].get(key)
-        launch = spec[1:] if spec[0] == "affine_diagonal" else spec       # (what `_integrate_trajectory` takes)
-        reverify = verdict is True and self._due_for_reverification(book, key)
-        if reverify:
-            verdict = None
-        if verdict is True:
-            rate = book.get("counter_rate", {}).get(key) if counters else {}
-            if rate is None or set(rate) != set(counters):
-                return None
-            ys = self._integrate_trajectory(launch, y0, ts)
-            if ys is not None and counters:
-                n_steps = timegrid.build(timegrid.ts_to_host(ts), self.dt).n_steps
-                for name in counters:
-                    setattr(base, name, counter_start[name] + rate[name] * n_steps)
-            return ys
-        if verdict is not None:
-            return None
-        # first solve of this form: is the interpretation repeatable and free of side effects, and does the kernel
-        # reproduce the stepwise solve?
-        # (the second interpretation runs on a probe of another height: a coefficient computed from the number of rows
-        #  -- `y / y.shape[0]` -- comes out different and the form is refused for what it is, not by a numeric accident)
-        before = state_of()
-        rng_before = self._rng_states(y0.device)
+                    spec = found.deep_spec(sde.noise_type)
+                except recognise.NotElementwise as e2:
+                    raise recognise.NotElementwise(f"{e}; as deeper networks: {e2}") from None
+            if precision == "bf16x3" and sde.noise_type == NOISE_TYPES.general and spec[0] == "neural":
+                # opt-in: the diffusion net's second layer on split-bf16 products (csrc/mlp_general.hip SPLIT); NOT the
+                # reference's arithmetic -- the default, and everything benchmarked as such, stays exact f32
+                spec[2].precision = _native.PRECISION_BF16X3
+            return found, spec, times
+        if not elementwise:
+            raise recognise.NotElementwise(f"{sde.noise_type} noise whose drift and diffusion are not both networks")
         try:
-            if spec[0] == "program_rows":
-                from . import recognise_rows
-                again = recognise_rows.recognise_rows(sde, ts[0], y0, rows=5).spec()
-            elif spec[0] == "program_diagonal":
-                again = recognise.recognise_program(sde, ts[0], y0, sde.noise_type, rows=5).spec(milstein)
-            elif spec[0] in ("program_additive", "neural_additive"):
-                again = recognise.recognise_additive(sde, ts[0], y0, times, rows=5, check_rows=True).spec()
-                # (a diffusion that is a network of t comes out of another matrix-product kernel on the taller probe: its
-                #  table is compared to rounding; everything else bit for bit, below)
-                tight = dict(rtol=1e-5, atol=1e-7) if y0.dtype == torch.float32 else dict(rtol=1e-12, atol=1e-14)
-                if again[3].shape == spec[3].shape and torch.allclose(again[3], spec[3], **tight):
-                    again = again[:3] + (spec[3],) + again[4:]
-            else:
-                again = recognise.recognise(sde, ts[0], y0, times=times, rows=5)
-                if spec[0] == "neural_rheun":
-                    again = again.deep_spec(sde.noise_type)
-                    same_nets = all(a.structure() == b.structure() and all(x is y for x, y in zip(a.parameters(), b.parameters()))
-                                    for a, b in zip(again[1:3], spec[1:3]))
-                    again = spec if (same_nets and again[3:] == spec[3:]) else again
-                else:
-                    again = again.neural_spec(sde.noise_type) if spec[0] == "neural" else again.spec()
-                if spec[0] == "neural":
-                    again[2].precision = spec[2].precision
+            return found, found.spec(), times
         except recognise.NotElementwise as e:
-            return refuse(str(e))
-        if before is None or state_of() != before:
-            return refuse("calling f and g changes the object's Python-side state")
-        if any(not torch.equal(a, b) for a, b in zip(rng_before, self._rng_states(y0.device))):
-            return refuse("calling f and g advances a random number generator")
-        same = len(again) == len(spec) and all(
-            (torch.equal(a, b) if torch.is_tensor(a) else a == b) for a, b in zip(again, spec))
-        if not same:
-            self._record_verdict(book, key, "two interpretations of the same code (probes of 2 and 5 rows) gave different "
-                                 "coefficients: they depend on the batch size or on how often the code has run", reverify)
-            return None
-        fast = self._integrate_trajectory(launch, y0, ts)
-        if fast is None:
-            return None                  # (grid and Brownian cells do not line up: nothing learnt about the form)
-        self._extra = ()
-        for name, value in counter_start.items():       # (the interpretations' calls are not steps: count the real loop only)
-            setattr(base, name, value)
-        stepwise = self._run(self._plan(y0, ts), y0)
-        if counters:
-            n_steps = timegrid.build(timegrid.ts_to_host(ts), self.dt).n_steps
-            advanced = {name: getattr(base, name) - counter_start[name] for name in counters}
-            if any(v % n_steps for v in advanced.values()):
-                self._record_verdict(book, key, "a call counter does not advance by a fixed amount per step", reverify)
-                return stepwise
-            counter_rate = {name: v // n_steps for name, v in advanced.items()}
-        rtol, atol = (1e-4, 1e-5) if y0.dtype == torch.float32 else (1e-9, 1e-11)
-        if spec[0] in ("mlp_diagonal", "neural", "neural_additive", "neural_rheun"):      # the matrix cores sum the layers' products in another order than the library
-            rtol, atol = 1e-3, 1e-4
-        both_nan = fast.isnan() & stepwise.isnan()
-        close = ((fast - stepwise).abs() <= atol + rtol * stepwise.abs()) | both_nan | (fast == stepwise)
-        self._record_verdict(book, key, True if bool(close.all()) else
-                             "the trajectory kernel did not reproduce the stepwise solve", reverify)
-        if counters:                        # (after the verdict: recording it prunes the book, rates included, when it is full)
-            book.setdefault("counter_rate", {})[key] = counter_rate
-        return stepwise
+            return as_program(str(e)) + (times,)
 
-    def _assume_pure(self, base):
-        return bool(self.options.get("assume_pure", False) or getattr(base, "tsde_assume_pure", False))
-
-    @staticmethod
-    def _rng_states(device):
-        """Host-side snapshots of the default CPU and device generators (seed + offset; no device synchronisation)."""
-        return torch.get_rng_state(), torch.cuda.get_rng_state(device)
-
-    @staticmethod
-    def _may_be_interpreted(base):
-        """The interpretation CALLS the user's f and g on a two-row probe. Modules for which one extra call is not
-        harmless are left alone: compiled modules (a dispatch mode under torch.compile recompiles or fails), and modules
-        with normalisation layers in training mode (a call would feed the probe into their running statistics)."""
-        if type(base).__name__ == "OptimizedModule":
-            return False
-        if isinstance(base, torch.nn.Module):
-            for m in base.modules():
-                if m.training and isinstance(m, torch.nn.modules.batchnorm._NormBase) \
-                        and getattr(m, "track_running_stats", False):
-                    return False
-        return True
+    def _interpret_again(self, spec, y0, ts, times):
+        """`spec` as a second interpretation on a probe of 5 rows finds it (NotElementwise if it finds nothing): a
+        coefficient computed from the number of rows -- `y / y.shape[0]` -- comes out different and the form is refused for
+        what it is, not by a numeric accident."""
+        from . import recognise
+        sde = self.sde
+        if spec[0] == "program_rows":
+            from . import recognise_rows
+            return recognise_rows.recognise_rows(sde, ts[0], y0, rows=5).spec()
+        if spec[0] == "program_diagonal":
+            milstein = self._program_code() in (_native.TRAJ_MILSTEIN_ITO, _native.TRAJ_MILSTEIN_STRAT)
+            return recognise.recognise_program(sde, ts[0], y0, sde.noise_type, rows=5).spec(milstein)
+        if spec[0] in ("program_additive", "neural_additive"):
+            again = recognise.recognise_additive(sde, ts[0], y0, times, rows=5, check_rows=True).spec()
+            # (a diffusion that is a network of t comes out of another matrix-product kernel on the taller probe: its
+            #  table is compared to rounding; everything else bit for bit, in `_solve_recognised`)
+            tight = dict(rtol=1e-5, atol=1e-7) if y0.dtype == torch.float32 else dict(rtol=1e-12, atol=1e-14)
+            if again[3].shape == spec[3].shape and torch.allclose(again[3], spec[3], **tight):
+                again = again[:3] + (spec[3],) + again[4:]
+            return again
+        again = recognise.recognise(sde, ts[0], y0, times=times, rows=5)
+        if spec[0] == "neural_rheun":
+            again = again.deep_spec(sde.noise_type)
+            same_nets = all(a.structure() == b.structure() and all(x is y for x, y in zip(a.parameters(), b.parameters()))
+                            for a, b in zip(again[1:3], spec[1:3]))
+            return spec if (same_nets and again[3:] == spec[3:]) else again
+        if spec[0] == "neural":
+            again = again.neural_spec(sde.noise_type)
+            again[2].precision = spec[2].precision
+            return again
+        return again.spec()
 
     def _integrate_recognised_with_grad(self, y0, ts):
         """Autograd is recording the solve (`sdeint` with trainable parameters or y0). A recognised module whose drift and
@@ -728,31 +688,17 @@ class BaseSDESolver:
         gradients land on those tensors -- through whatever graph the user's code built on the way to them. Trust as for
         the forward route; the verifying solve compares the kernel's VALUES with the stepwise solve, which is the one
         that is returned (with its graph). None: the stepwise path."""
-        from . import graph, recognise
-        sde, bm = self.sde, self._native_bm()
-        scalar = sde.noise_type == NOISE_TYPES.scalar
-        if (bm is None or y0.dim() != 2 or not y0.is_cuda or y0.shape[0] < 8
-                or tuple(bm.shape) != ((y0.shape[0], 1) if scalar else tuple(y0.shape))
-                or y0.dtype not in (torch.float32, torch.float64) or ts.dtype != y0.dtype or bm.dtype != y0.dtype
-                or bm._rootW is not None or bm._rootH is not None or torch.cuda.is_current_stream_capturing()
-                or (self._program_code() == _native.TRAJ_SRK and not bm._have_H)):
+        from . import recognise
+        if self._recognisable_bm(y0, ts) is None:
             return None
-        chain, base = graph._wrapper_chain(sde)
-        assume_pure = self._assume_pure(base)
-        if not self._may_be_interpreted(base) or (not assume_pure and graph.call_counters(base)):
-            # (call counters: only the forward route above keeps them at the stepwise loop's value; with autograd recording such
-            #  modules stay stepwise, where the counters are right by construction)
+        # (call counters: only the forward route above keeps them at the stepwise loop's value; with autograd recording such
+        #  modules stay stepwise, where the counters are right by construction)
+        ledger = trust.open_book(self)
+        if ledger is None or ledger.refused():
             return None
-        try:
-            book = base.__dict__.setdefault(self._RECOGNISED_ATTR, {"refused": {}, "trusted": {}})
-        except AttributeError:
-            return None
-        if book["refused"]:
-            state = ("assumed pure",) if assume_pure else graph.python_state(base)
-            if state is None or (state, chain, type(self).__name__) in book["refused"]:
-                return None
+        sde = self.sde
         leaves = None
-        if not scalar and self._trajectory_code() is not None:
+        if sde.noise_type != NOISE_TYPES.scalar and self._trajectory_code() is not None:
             try:
                 found = recognise.recognise(sde, ts[0], y0, differentiable=True)
                 leaves = found.affine_leaves()
@@ -760,13 +706,13 @@ class BaseSDESolver:
                 pass    # (the forward route records refusals; a training loop reaches it under no_grad or not at all)
         if leaves is None:
             # anything else that is elementwise: expression programs on dual numbers (tsde_trajectory_prog_diag_sens)
-            return self._integrate_program_with_grad(y0, ts, book, chain)
-        key = self._recognised_key(found, chain, y0) + ("autograd",)
-        verdict = book["trusted"].get(key)
-        reverify = verdict is True and self._due_for_reverification(book, key)
-        if verdict is True and not reverify:
-            return self._integrate_trajectory(("differentiable",) + tuple(leaves), y0, ts)
-        if verdict is not None and not reverify:
+            return self._integrate_program_with_grad(y0, ts, ledger)
+        key = ledger.key(found, y0, "autograd")
+        verdict, reverify = ledger.verdict(key)
+        launch = ("differentiable",) + tuple(leaves)
+        if verdict is True:
+            return self._integrate_trajectory(launch, y0, ts)
+        if verdict is not None:
             return None
         # (as in `_integrate_recognised`: a second interpretation on a probe of another height must give the same values)
         try:
@@ -774,19 +720,12 @@ class BaseSDESolver:
         except recognise.NotElementwise:
             return None
         if again is None or any(a.shape != b.shape or not torch.equal(a.detach(), b.detach()) for a, b in zip(again, leaves)):
-            self._record_verdict(book, key, "two interpretations of the same code (probes of 2 and 5 rows) gave different "
-                                 "coefficients", reverify)
+            ledger.file(key, "two interpretations of the same code (probes of 2 and 5 rows) gave different coefficients",
+                        reverify)
             return None
-        fast = self._integrate_trajectory(("differentiable",) + tuple(leaves), y0, ts)     # values AND a grad_fn
-        if fast is None:
-            return None
-        self._extra = ()
-        stepwise = self._run(self._plan(y0, ts), y0)           # recorded by autograd: this is the result
-        verdict = self._both_routes_agree(fast, stepwise, y0, "the sensitivity kernel")
-        self._record_verdict(book, key, verdict, reverify)
-        return stepwise
+        return self._verify_with_grad(ledger, key, reverify, launch, y0, ts, "the sensitivity kernel")
 
-    def _integrate_program_with_grad(self, y0, ts, book, chain):
+    def _integrate_program_with_grad(self, y0, ts, ledger):
         """`_integrate_recognised_with_grad` for code the affine form does not hold: drift and diffusion as expression
         programs, gradients to y0 and to up to four per-channel constants of the user's module (the tensors their code hands
         to its operators: parameters, or what autograd saw it derive from them) through the sensitivity kernel."""
@@ -820,13 +759,12 @@ class BaseSDESolver:
                 stack.extend(nxt for nxt, _ in fn.next_functions)
         if any(p.requires_grad and id(p) not in reached for p in self._params()):
             return None
-        key = self._recognised_key(found, chain, y0) + ("autograd",)
-        verdict = book["trusted"].get(key)
+        key = ledger.key(found, y0, "autograd")
+        verdict, reverify = ledger.verdict(key)
         launch = ("program_differentiable", spec[1], spec[2], spec[3], tuple(found.consts), tuple(rows), spec[5])
-        reverify = verdict is True and self._due_for_reverification(book, key)
-        if verdict is True and not reverify:
+        if verdict is True:
             return self._integrate_trajectory(launch, y0, ts)
-        if verdict is not None and not reverify:
+        if verdict is not None:
             return None
         try:
             again = recognise.recognise_program(sde, ts[0], y0, sde.noise_type, rows=5, differentiable=True)
@@ -835,16 +773,20 @@ class BaseSDESolver:
             return None
         if (again.structure() != found.structure()
                 or not torch.equal(again_spec[4], spec[4]) or again.trainable_rows(None) != rows):
-            self._record_verdict(book, key, "two interpretations of the same code (probes of 2 and 5 rows) gave different "
-                                 "programs", reverify)
+            ledger.file(key, "two interpretations of the same code (probes of 2 and 5 rows) gave different programs",
+                        reverify)
             return None
-        fast = self._integrate_trajectory(launch, y0, ts)       # values AND a grad_fn (the program sensitivity kernel)
+        return self._verify_with_grad(ledger, key, reverify, launch, y0, ts, "the program sensitivity kernel")
+
+    def _verify_with_grad(self, ledger, key, reverify, launch, y0, ts, what):
+        """The verifying solve of a sensitivity-kernel route: both routes, compared and filed; the stepwise result (recorded
+        by autograd) is returned. None when grid and Brownian cells do not line up."""
+        fast = self._integrate_trajectory(launch, y0, ts)       # values AND a grad_fn
         if fast is None:
             return None
         self._extra = ()
         stepwise = self._run(self._plan(y0, ts), y0)           # recorded by autograd: this is the result
-        verdict = self._both_routes_agree(fast, stepwise, y0, "the program sensitivity kernel")
-        self._record_verdict(book, key, verdict, reverify)
+        ledger.file(key, self._both_routes_agree(fast, stepwise, y0, what), reverify)
         return stepwise
 
 
@@ -890,30 +832,6 @@ class BaseSDESolver:
                         f"(max error {float((h - w).abs().max()):.3e} at scale {float(scale):.3e})")
         return True
 
-    @staticmethod
-    def _record_verdict(book, key, verdict, reverify=False):
-        if len(book["trusted"]) >= 32:
-            book["trusted"].clear()
-            book.get("counter_rate", {}).clear()
-            book.get("solves", {}).clear()
-        book["trusted"][key] = verdict
-        if reverify and verdict is not True:
-            # TSDE_VERIFY_EVERY: a form that had earned trust and no longer reproduces the stepwise solve is a loud failure
-            raise RuntimeError(f"torchsde_amd: periodic re-verification (TSDE_VERIFY_EVERY) of a trusted kernel route failed: "
-                               f"{verdict}. Results of earlier solves of this object on that route are suspect; "
-                               "options={'trajectory_kernel': False} keeps the stepwise path.")
-
-    @staticmethod
-    def _due_for_reverification(book, key):
-        """TSDE_VERIFY_EVERY=N (or `solvers.VERIFY_EVERY`): every N-th solve of a trusted form runs both routes again and
-        compares (values, and gradients where autograd records) -- a mis-recognition fails loudly in CI instead of quietly
-        in training. 0 (the default): only the first solve verifies."""
-        if VERIFY_EVERY <= 0:
-            return False
-        count = book.setdefault("solves", {})
-        count[key] = count.get(key, 0) + 1
-        return count[key] % VERIFY_EVERY == 0
-
     _STAGE_TIMES = {}
     # stage-time slots of the trajectory kernels (csrc/trajectory.hip stage_slots): offsets from t0 as multiples of dt
     _TIMED_SLOTS = {_native.TRAJ_EULER: (0,), _native.TRAJ_MILSTEIN_ITO: (0,), _native.TRAJ_MILSTEIN_STRAT: (0,),
@@ -943,31 +861,19 @@ class BaseSDESolver:
             self._STAGE_TIMES[key] = hit
         return hit
 
-    def _recognised_key(self, found, chain, y0):
-        # The batch size is part of the key: the interpretation runs on a probe of a few rows, so whatever the user's code
-        # derives from `y.shape[0]` (`-y if y.shape[0] > 1000 else -2 * y`) is evaluated for the probe; the both-routes
-        # comparison that earns the trust therefore has to be made at every batch size the form is solved at.
-        return (found.structure(), chain, type(self).__name__, self.sde.sde_type, y0.shape[1], y0.dtype, y0.shape[0])
-
     def recognised_perceptron(self, y0, ts):
         """For `sdeint_adjoint` (mlp_adjoint.route): the interpretation of an unchanged user module whose drift is a
         two-layer perceptron -- `recognise.Recognised` -- if this solver's forward solve of it through the sampling
         kernel is TRUSTED (verified against the stepwise solve; the check runs here, once, if it has not yet), else None."""
-        from . import graph, recognise
+        from . import recognise
         from .sde import ForwardSDE
         sde = self.sde
         if (not recognise.ENABLED or type(sde) is not ForwardSDE or sde.user_product
                 or sde.noise_type != NOISE_TYPES.diagonal or y0.dim() != 2 or not y0.is_cuda):
             return None
-        chain, base = graph._wrapper_chain(sde)
-        assume_pure = self._assume_pure(base)
-        if not self._may_be_interpreted(base) or (not assume_pure and graph.call_counters(base)):
+        ledger = trust.open_book(self, create=False)
+        if ledger is None or ledger.refused():
             return None
-        book = getattr(base, self._RECOGNISED_ATTR, None)
-        if book is not None and book["refused"]:
-            state = ("assumed pure",) if assume_pure else graph.python_state(base)
-            if state is None or (state, chain, type(self).__name__) in book["refused"]:
-                return None
         try:
             # (differentiable=True: the adjoint kernels differentiate the recognised network -- a stop-gradient in the user's
             #  code, which adjoint_sde.py:111-128 would honour, ends the interpretation: recognise.check_stop_gradient)
@@ -977,19 +883,18 @@ class BaseSDESolver:
             found.perceptron_spec()
         except recognise.NotElementwise:
             return None
-        key = self._recognised_key(found, chain, y0)
-        if book is None or key not in book["trusted"]:
+        key = ledger.key(found, y0)
+        if ledger.recorded(key) is None:
             with torch.no_grad():                                  # the verifying solve (both routes, compared)
                 self._integrate_recognised(y0.detach(), ts)
-            book = getattr(base, self._RECOGNISED_ATTR, None)
             # ... and the DERIVATIVES the adjoint kernels will stand for: vector-Jacobian products of the user's f and g
             # (what adjoint_sde.py:111-128, 218-230 asks autograd for at every backward step) against those of the recognised
             # network built from the same parameter tensors, on real rows of this solve
-            if book is not None and book["trusted"].get(key) is True:
+            if ledger.recorded(key) is True:
                 reason = self._perceptron_derivatives_agree(found, y0, ts)
                 if reason is not True:
-                    book["trusted"][key] = reason
-        return found if book is not None and book["trusted"].get(key) is True else None
+                    ledger.file(key, reason)
+        return found if ledger.recorded(key) is True else None
 
     def _perceptron_derivatives_agree(self, found, y0, ts):
         own = found.perceptron_parameters()
@@ -1022,72 +927,31 @@ class BaseSDESolver:
 
     def recognised_route(self):
         """{form key: True | reason} and {state: reason} of the SDE object this solver integrates (diagnostics)."""
-        from . import graph
-        _, base = graph._wrapper_chain(self.sde)
-        return getattr(base, self._RECOGNISED_ATTR, None)
+        return trust.book_of(self.sde)
 
     def _integrate_trajectory(self, coefficients, y0, ts):
         """All steps in one kernel launch; None if the Brownian motion's cells do not line up with the steps."""
         bm = self.bm
         grid = timegrid.build(timegrid.ts_to_host(ts), self.dt)
-        if grid.n_steps == 0:
+        steps = K.solve_steps(grid, bm)
+        if steps is None:
             return None
-        t64 = grid.t_f64()
-        bm.adopt_grid(t64)
-        cells = bm.match_grid(t64)
-        if cells is None:
-            return None
-        cells = np.asarray(cells, dtype=np.int64)
-        h = bm._edges[cells + 1] - bm._edges[cells]
-        # (the step rows of a grid the process has just seen -- every iteration of a training loop: remembered on the
-        #  grid object, which timegrid.build hands back for equal (ts, dt); valid for these cell widths)
-        memo = getattr(grid, "_step_rows", None)
-        if memo is not None and memo[0].shape == h.shape and np.array_equal(memo[0], h):
-            rows, out_step, out_w = memo[1:]
-        else:
-            np_dtype = grid.t.dtype.type
-            dt = grid.dt
-            rows = np.zeros((grid.n_steps, 8), dtype=np.float64)
-            # each entry is rounded in ts.dtype like the stepwise path's scalars, then (below) cast to the state dtype
-            rows[:, 0] = dt
-            rows[:, 1] = np_dtype(0.5) * dt
-            rows[:, 2] = np_dtype(1) / dt
-            rows[:, 3] = np.sqrt(dt)
-            rows[:, 4] = np.sqrt(h)
-            rows[:, 5] = np.sqrt(h / 12.0)
-            rows[:, 6] = h
-            rows[:, 7] = grid.t[:-1]         # t_k, the time a step starts at (read by tsde_trajectory_mlp_general only)
-            out_step = [kc for (_, kc, _, _) in grid.outputs]
-            out_w = [(w0, w1) for (_, _, w0, w1) in grid.outputs]
-            grid._step_rows = (h.copy(), rows, out_step, out_w)
-        if coefficients[0] == "mlp_differentiable":
-            if any(not (w0 == 0.0 and w1 == 1.0) for (w0, w1) in out_w):
+        kind = coefficients[0] if isinstance(coefficients[0], str) else "affine_diagonal"
+        if kind == "mlp_differentiable":
+            if not steps.on_boundaries:
                 return None
-            every_step = list(range(1, grid.n_steps + 1))
-            schedule_all = K.TrajectorySchedule.cached(rows, cells, every_step, [(0.0, 1.0)] * grid.n_steps, y0.device,
-                                                       y0.dtype)
+            schedule_all = steps.schedule(y0.device, y0.dtype, every_step=True)
             return K.trajectory_mlp_diag_differentiable(y0, coefficients[3:], coefficients[1], coefficients[2],
-                                                        self._trajectory_code(), schedule_all, out_step, bm)
-        schedule = K.TrajectorySchedule.cached(rows, cells, out_step, out_w, y0.device, y0.dtype)
-        if coefficients[0] == "program_differentiable":
+                                                        self._trajectory_code(), schedule_all, steps.out_step, bm)
+        schedule = steps.schedule(y0.device, y0.dtype)
+        if kind == "program_differentiable":
             _, f_code, g_code, dg_code, const_values, rows_with_grad, scalar_noise = coefficients
             return K.trajectory_prog_diag_differentiable(y0, (f_code, g_code, dg_code), const_values, rows_with_grad,
                                                          scalar_noise, self._program_code(), schedule, bm)
-        if coefficients[0] == "program_rows":
-            y0c = y0.detach() if y0.is_contiguous() else y0.detach().contiguous()
-            ys = torch.empty((len(grid.outputs) + 1,) + tuple(y0.shape), dtype=y0.dtype, device=y0.device)
-            ys[0].copy_(y0c)
-            done = K.trajectory_rows(ys[1:], y0c, coefficients[1], coefficients[2], self._program_code(), schedule, bm)
-            return None if done is None else ys          # (None: the generated unit is still compiling -- stepwise for now)
-        if coefficients[0] == "program_diagonal":
-            y0c = y0.detach() if y0.is_contiguous() else y0.detach().contiguous()
-            ys = torch.empty((len(grid.outputs) + 1,) + tuple(y0.shape), dtype=y0.dtype, device=y0.device)
-            ys[0].copy_(y0c)
-            K.trajectory_prog_diag(ys[1:], y0c, coefficients[1], coefficients[2], coefficients[3], coefficients[4],
-                                   coefficients[5], self._program_code(), schedule, bm)
-            return ys
-        if coefficients[0] in ("program_additive", "neural_additive"):
-            kind, f_code, const_table, table, m = coefficients
+        if kind == "differentiable":
+            return K.trajectory_affine_diag_differentiable(y0, coefficients[1:], self._trajectory_code(), schedule, bm)
+        if kind in ("program_additive", "neural_additive"):
+            _, f_code, const_table, table, m = coefficients
             code = self._additive_code()
             if table.dim() == 3:
                 slots = len(self._ADDITIVE_SLOTS[code])
@@ -1096,50 +960,39 @@ class BaseSDESolver:
                 table = table.view(grid.n_steps, slots, m, y0.shape[1])
             if kind == "neural_additive" and y0.numel() >= 2 ** 30:
                 return None
+        # the network kernels read y0 from a 16-byte boundary (`_aligned_start`); the others from any contiguous start
+        if kind in ("program_additive", "neural_additive", "neural_rheun", "neural", "mlp_diagonal"):
             y0c = self._aligned_start(y0)
-            ys = torch.empty((len(grid.outputs) + 1,) + tuple(y0.shape), dtype=y0.dtype, device=y0.device)
-            ys[0].copy_(y0c)
-            if kind == "neural_additive":
-                K.trajectory_mlp_additive(ys[1:], y0c, f_code, table, m, code, schedule, bm)       # (f_code: the drift net)
-            else:
-                K.trajectory_prog_additive(ys[1:], y0c, f_code, const_table, table, m, code, schedule, bm)
-            return ys
-        if coefficients[0] == "neural_rheun":
+        else:
+            y0c = y0.detach() if y0.is_contiguous() else y0.detach().contiguous()
+        ys = torch.empty((len(grid.outputs) + 1,) + tuple(y0.shape), dtype=y0.dtype, device=y0.device)
+        ys[0].copy_(y0c)
+        if kind == "program_rows":
+            done = K.trajectory_rows(ys[1:], y0c, coefficients[1], coefficients[2], self._program_code(), schedule, bm)
+            return None if done is None else ys          # (None: the generated unit is still compiling -- stepwise for now)
+        if kind == "program_diagonal":
+            K.trajectory_prog_diag(ys[1:], y0c, coefficients[1], coefficients[2], coefficients[3], coefficients[4],
+                                   coefficients[5], self._program_code(), schedule, bm)
+        elif kind == "neural_additive":
+            K.trajectory_mlp_additive(ys[1:], y0c, f_code, table, m, code, schedule, bm)       # (f_code: the drift net)
+        elif kind == "program_additive":
+            K.trajectory_prog_additive(ys[1:], y0c, f_code, const_table, table, m, code, schedule, bm)
+        elif kind == "neural_rheun":
             # (a stateless scheme on the deep-network kernel, csrc/tsde_neural_rheun.h)
             from . import neural_rheun
-            y0c = self._aligned_start(y0)
-            ys = torch.empty((len(grid.outputs) + 1,) + tuple(y0.shape), dtype=y0.dtype, device=y0.device)
-            ys[0].copy_(y0c)
             times = neural_rheun._device_times(np.ascontiguousarray(grid.t, dtype=np.float32), y0.device)
             neural_rheun.forward(ys[1:], torch.empty_like(y0c), y0c, coefficients[1], coefficients[2], coefficients[3],
                                  coefficients[4], schedule, times, bm, method=self._deep_code())
-            return ys
-        if coefficients[0] == "neural":
-            y0c = self._aligned_start(y0)
-            ys = torch.empty((len(grid.outputs) + 1,) + tuple(y0.shape), dtype=y0.dtype, device=y0.device)
-            ys[0].copy_(y0c)
+        elif kind == "neural":
             K.trajectory_mlp_general(ys[1:], y0c, coefficients[1], coefficients[2], coefficients[3], coefficients[4],
                                      self._neural_code(), schedule, bm)
-            return ys
-        if coefficients[0] == "mlp_diagonal":
-            y0c = self._aligned_start(y0)
-            ys = torch.empty((len(grid.outputs) + 1,) + tuple(y0.shape), dtype=y0.dtype, device=y0.device)
-            ys[0].copy_(y0c)
+        elif kind == "mlp_diagonal":
             K.trajectory_mlp_diag(ys[1:], y0c, *coefficients[1:], self._trajectory_code(), schedule, bm)
-            return ys
-        if coefficients[0] == "elementwise_diagonal":
-            y0c = y0.detach() if y0.is_contiguous() else y0.detach().contiguous()
-            ys = torch.empty((len(grid.outputs) + 1,) + tuple(y0.shape), dtype=y0.dtype, device=y0.device)
-            ys[0].copy_(y0c)
+        elif kind == "elementwise_diagonal":
             K.trajectory_expr_diag(ys[1:], y0c, coefficients[1], coefficients[2], coefficients[3:],
                                    self._trajectory_code(), schedule, bm)
-            return ys
-        if coefficients[0] == "differentiable":
-            return K.trajectory_affine_diag_differentiable(y0, coefficients[1:], self._trajectory_code(), schedule, bm)
-        y0c = y0.detach() if y0.is_contiguous() else y0.detach().contiguous()
-        ys = torch.empty((len(grid.outputs) + 1,) + tuple(y0.shape), dtype=y0.dtype, device=y0.device)
-        ys[0].copy_(y0c)
-        K.trajectory_affine_diag(ys[1:], y0c, *coefficients, self._trajectory_code(), schedule, bm)
+        else:
+            K.trajectory_affine_diag(ys[1:], y0c, *coefficients, self._trajectory_code(), schedule, bm)
         return ys
 
     @staticmethod

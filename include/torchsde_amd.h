@@ -363,7 +363,12 @@ int tsde_brownian_query_dev(void* W, void* U, void* H, int64_t n, uint64_t entro
  * generated cell (entropy, elem0 + i, cells[k]) of the counter RNG, and only the requested outputs
  * ys (n_out, rows, d) are written. `method` is one of TSDE_TRAJ_*. Results are bit-identical to driving
  * tsde_step_diag / tsde_milstein_diag / tsde_srk_diag_stage step by step with f, g evaluated as
- * (rate * y) + shift. */
+ * (rate * y) + shift.
+ * drift_shift == NULL && diff_shift == NULL means "both shifts are zero" and runs the LINEAR form of the kernel,
+ * f = rate * y, g = rate * y (no shift registers, no additions): bit-identical to the stepwise route with f, g
+ * evaluated as rate * y, and equal to passing explicit zero arrays except possibly for the sign of a zero. Exactly
+ * one of the two NULL is rejected with hipErrorInvalidValue like any other bad argument. (This entry only: the
+ * _timed and _sens entries below need all four arrays.) */
 int tsde_trajectory_affine_diag(void* ys, const void* y0, int64_t rows, int64_t d, const void* drift_rate,
                                 const void* drift_shift, const void* diff_rate, const void* diff_shift, int method,
                                 const tsde_traj_t* traj, uint64_t entropy, uint64_t elem0,

@@ -29,12 +29,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-HEADLINE_SYMBOL = "_ZN4tsde17trajectory_kernelIfLi0ELi4ELb0ELb0EEEvNS_8TrajArgsIT_EE"
+def affine_symbol(method, width=4, timed=False, linear=None):
+    """trajectory_kernel<float, METHOD, W, /*SENS=*/false, TIMED, LINEAR> (METHOD: include/torchsde_amd.h TSDE_TRAJ_*).
+    `linear`: the form without shifts, f = rate * y -- what geometric Brownian motion (bench.py's gbm_* workloads) runs and
+    therefore the default for constant coefficients; `linear=False` names the general form, f = rate * y + shift."""
+    linear = (not timed) if linear is None else bool(linear)
+    return f"_ZN4tsde17trajectory_kernelIfLi{method}ELi{width}ELb0ELb{int(timed)}ELb{int(linear)}EEEvNS_8TrajArgsIT_EE"
 
 
-def affine_symbol(method, width=4, timed=False):
-    """trajectory_kernel<float, METHOD, W, /*SENS=*/false, TIMED> (METHOD: include/torchsde_amd.h TSDE_TRAJ_*)."""
-    return f"_ZN4tsde17trajectory_kernelIfLi{method}ELi{width}ELb0ELb{int(timed)}EEEvNS_8TrajArgsIT_EE"
+HEADLINE_SYMBOL = affine_symbol(0)
 DEFAULT_CYCLES = 2.0        # guides/MI355X_MICROARCH.md: one plain wave64 VALU instruction issues over 2 cycles (SIMD-32)
 
 
@@ -169,14 +172,15 @@ def model(symbol=HEADLINE_SYMBOL, rates_path=None, source="trajectory.hip", elem
 
 
 def all_affine(rates_path=None):
-    """The models of the five constant-coefficient affine kernels (Euler, Milstein Ito / Stratonovich, midpoint, SRK; one
-    16-byte group per lane), from one compilation."""
+    """The models of the constant-coefficient affine kernels (Euler, Milstein Ito / Stratonovich, midpoint, SRK, Heun,
+    Euler-Heun; one 16-byte group per lane), linear and general form of each, from one compilation."""
     import bench
     asm = device_asm()
     kernels = {}
-    for method in range(7):        # TSDE_TRAJ_EULER .. TSDE_TRAJ_EULER_HEUN
-        symbol = affine_symbol(method)
-        kernels[symbol] = model(symbol, rates_path, asm=asm)
+    for linear in (True, False):
+        for method in range(7):        # TSDE_TRAJ_EULER .. TSDE_TRAJ_EULER_HEUN
+            symbol = affine_symbol(method, linear=linear)
+            kernels[symbol] = model(symbol, rates_path, asm=asm)
     return {"csrc_sha": bench.csrc_digest(), "kernels": kernels}
 
 

@@ -493,7 +493,11 @@ static int trajectory_affine_diag(const char* where, void* ys, void* sens, const
                                   const void* diff_shift, int64_t coef_step_stride, int method, const tsde_traj_t* traj,
                                   uint64_t entropy, uint64_t elem0, const uint64_t* entropy_dev, int dtype,
                                   void* stream) {
-  if (!ys || !y0 || !drift_rate || !drift_shift || !diff_rate || !diff_shift || !traj) return bad_arg(where, "null argument");
+  if (!ys || !y0 || !drift_rate || !diff_rate || !traj) return bad_arg(where, "null argument");
+  // both shifts null: the linear form, f = rate * y (the plain entry only); one of them null is a mistake
+  const bool linear = !drift_shift && !diff_shift;
+  if (!linear && (!drift_shift || !diff_shift)) return bad_arg(where, "one shift is null and the other is not");
+  if (linear && (sens || coef_step_stride != 0)) return bad_arg(where, "null argument");
   if (coef_step_stride != 0 && coef_step_stride < d) return bad_arg(where, "coef_step_stride must be 0 or >= d");
   if (coef_step_stride != 0 && sens) return bad_arg(where, "per-step coefficients: values only");
   if (rows < 0 || d <= 0) return bad_arg(where, "need rows >= 0 and d > 0");

@@ -189,7 +189,14 @@ TSDE_D S scheme_step(const S y, const M& m, const N w, const N u, const T dt, co
   }
 }
 
-// Affine drift and diffusion, f = a*x + b, g = c*x + e; the coefficient types A..E are T or Seed<T, 1..4>.
+// A shift that is zero by construction (the LINEAR form, f = a*x, g = c*x: geometric Brownian motion, any user module
+// recognised as `mu * y`, `sigma * y`): it occupies no register and `x + NoShift{}` is x, no instruction. The stepwise
+// route evaluates such a module with no addition at all; against `x + 0` the only difference is the sign of a zero.
+struct NoShift {};
+template <typename X>
+TSDE_D X operator+(const X& x, NoShift) { return x; }
+
+// Affine drift and diffusion, f = a*x + b, g = c*x + e; the coefficient types A..E are T or Seed<T, 1..4>, B and E also NoShift.
 template <typename T, typename S, typename A, typename B, typename C, typename E>
 struct AffineModel {
   A a;
@@ -308,6 +315,11 @@ TSDE_D int next_output_step(const int32_t* out_step, int j, int n_out) {
   return j < n_out ? __builtin_amdgcn_readfirstlane(out_step[j]) : -1;
 }
 
+// ... read through the constant address space (`uniform_load`): the affine kernel's
+TSDE_D int next_output_uniform(const int32_t* out_step, int j, int n_out) {
+  return j < n_out ? uniform_load(out_step, j) : -1;
+}
+
 template <typename T>
 TSDE_D T primal(const T& x) { return x; }
 template <typename T>
@@ -319,40 +331,49 @@ TSDE_D T primal(const Dual<T>& x) { return x.v; }
 // TIMED: the coefficients are functions of time, f(t, y) = a(t) * y + b(t), given as one row per STAGE TIME of every step
 //        (`stage_slots<METHOD>()` rows per step, in slot order): re-read, through the L2, at the top of every step. A
 //        separate instantiation, so the constant-coefficient kernels are untouched.
-template <typename T, int METHOD, int W, bool SENS, bool TIMED = false>
+// LINEAR: both shifts are zero (`p.b`, `p.e` are null and never read): f = a*y, g = c*y. Chosen by the host, values only,
+//        constant coefficients only -- the sensitivity kernels carry d/db and d/de, which are live at a zero shift too.
+template <typename T, int METHOD, int W, bool SENS, bool TIMED = false, bool LINEAR = false>
 __global__ void __launch_bounds__(kBlock) trajectory_kernel(const TrajArgs<T> p) {
+  static_assert(!LINEAR || (!SENS && !TIMED), "the linear form: values only, constant coefficients");
   constexpr bool kNeedU = METHOD == kSrk;
+  constexpr bool kInPlace = !SENS && !TIMED;
   using S = typename std::conditional<SENS, Dual<T>, T>::type;
   using A = typename std::conditional<SENS, Seed<T, 1>, T>::type;
-  using B = typename std::conditional<SENS, Seed<T, 2>, T>::type;
+  using B = typename std::conditional<LINEAR, NoShift, typename std::conditional<SENS, Seed<T, 2>, T>::type>::type;
   using C = typename std::conditional<SENS, Seed<T, 3>, T>::type;
-  using E = typename std::conditional<SENS, Seed<T, 4>, T>::type;
+  using E = typename std::conditional<LINEAR, NoShift, typename std::conditional<SENS, Seed<T, 4>, T>::type>::type;
   const int64_t lane = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   const int64_t i = lane * W;
   if (i >= p.n) return;
   const int64_t col = i % p.d;
-  const Pack<T, W> a = load<T, W>(p.a, col), b = load<T, W>(p.b, col), c = load<T, W>(p.c, col),
-                   e = load<T, W>(p.e, col);
+  const Pack<T, W> a = load<T, W>(p.a, col), c = load<T, W>(p.c, col);
+  Pack<T, W> b, e;
+  if constexpr (!LINEAR) {
+    b = load<T, W>(p.b, col);
+    e = load<T, W>(p.e, col);
+  }
   const Pack<T, W> y_init = load<T, W>(p.y0, i);
-  S y[W];
+  S y[W], y_prev[W];  // the state; and the state at the start of a step that meets an output time
 #pragma unroll
   for (int q = 0; q < W; ++q) {
-    y[q] = S(y_init.v[q]);
+    y[q] = y_prev[q] = S(y_init.v[q]);
     if constexpr (SENS) y[q].d[0] = (T)1;
   }
   NoiseKey key = p.key;
   if (p.key_dev != nullptr) {
-    const uint64_t ent = *p.key_dev;
+    const uint64_t ent = uniform_load(p.key_dev, 0);
     key.k0 = (uint32_t)ent;
     key.k1 = (uint32_t)(ent >> 32);
   }
   const uint64_t elem = key.elem0 + (uint64_t)i;
   int j = 0;
-  int next_out = next_output_step(p.out_step, 0, p.n_out);
+  int next_out = next_output_uniform(p.out_step, 0, p.n_out);
   for (int k = 0; k < p.n_steps; ++k) {
-    const T* row = p.rows + (int64_t)k * 8;   // wave-uniform
-    const T dt = row[0], half_dt = row[1], rdt = row[2], sqrt_dt = row[3], sw = row[4], sh = row[5], th = row[6];
-    const uint32_t cell = p.cells[k];
+    const T* row = p.rows + (int64_t)k * 8;   // wave-uniform: scalar loads
+    const T dt = uniform_load(row, 0), half_dt = uniform_load(row, 1), rdt = uniform_load(row, 2),
+            sqrt_dt = uniform_load(row, 3), sw = uniform_load(row, 4), sh = uniform_load(row, 5), th = uniform_load(row, 6);
+    const uint32_t cell = uniform_load(p.cells, k);
     constexpr int NS = stage_slots<METHOD>();
     Pack<T, W> ta[NS], tb[NS], tc[NS], te[NS];      // TIMED: the coefficient rows of this step's stage times
     if constexpr (TIMED) {
@@ -365,22 +386,37 @@ __global__ void __launch_bounds__(kBlock) trajectory_kernel(const TrajArgs<T> p)
         te[sl] = load<T, W>(p.e, at);
       }
     }
+    const StepNoise noise(key, cell);               // (the uniform head of this step's Philox calls: scalar unit)
     Pack<T, W> w, u;
     if constexpr (W == 4) {
       T z[4];
-      normal4<T>(key, elem >> 2, cell, 0, kStreamW, z);
+      noise.normal4(elem >> 2, kStreamW, z);
 #pragma unroll
       for (int q = 0; q < 4; ++q) w.v[q] = z[q] * sw;
       if constexpr (kNeedU) {
-        normal4<T>(key, elem >> 2, cell, 0, kStreamH, z);
+        noise.normal4(elem >> 2, kStreamH, z);
 #pragma unroll
         for (int q = 0; q < 4; ++q) u.v[q] = th * ((T)0.5 * w.v[q] + z[q] * sh);
       }
     } else {
-      w.v[0] = normal1<T>(key, elem, cell, 0, kStreamW) * sw;
-      if constexpr (kNeedU) u.v[0] = th * ((T)0.5 * w.v[0] + normal1<T>(key, elem, cell, 0, kStreamH) * sh);
+      w.v[0] = noise.template normal1<T>(elem, kStreamW) * sw;
+      if constexpr (kNeedU) u.v[0] = th * ((T)0.5 * w.v[0] + noise.template normal1<T>(elem, kStreamH) * sh);
     }
+    // Values-only kernels with constant coefficients advance the state IN PLACE: a step that ends at or after an output
+    // time -- all but a few do not -- first sets the state it starts from aside (the interpolation inside a step needs both
+    // ends) in a cold block, and the hot loop has no register copies at its latch. The others (dual numbers, coefficient
+    // rows: wide states, where the copy's registers cost occupancy) keep both states and copy at the latch.
+    const bool due = k + 1 == next_out;
     S y1[W];
+    if constexpr (kInPlace) {
+      if (__builtin_expect(due, 0)) {
+        asm volatile("" ::: "memory");    // (keeps this a branch: as selects it would cost W vector instructions per step)
+#pragma unroll
+        for (int q = 0; q < W; ++q) y_prev[q] = y[q];
+      }
+    }
+    S* const y_new = kInPlace ? y : y1;
+    const S* const y_old = kInPlace ? y_prev : y;
 #pragma unroll
     for (int q = 0; q < W; ++q) {
       if constexpr (TIMED) {
@@ -392,21 +428,27 @@ __global__ void __launch_bounds__(kBlock) trajectory_kernel(const TrajArgs<T> p)
           m.c[sl] = tc[sl].v[q];
           m.e[sl] = te[sl].v[q];
         }
-        y1[q] = scheme_step<T, METHOD, S>(y[q], m, w.v[q], kNeedU ? u.v[q] : (T)0, dt, half_dt, rdt, sqrt_dt);
+        y_new[q] = scheme_step<T, METHOD, S>(y[q], m, w.v[q], kNeedU ? u.v[q] : (T)0, dt, half_dt, rdt, sqrt_dt);
       } else {
-        y1[q] = affine_step<T, METHOD, S, A, B, C, E>(y[q], A{a.v[q]}, B{b.v[q]}, C{c.v[q]}, E{e.v[q]}, w.v[q],
-                                                       kNeedU ? u.v[q] : (T)0, dt, half_dt, rdt, sqrt_dt);
+        B bq;
+        E eq;
+        if constexpr (!LINEAR) {
+          bq = B{b.v[q]};
+          eq = E{e.v[q]};
+        }
+        y_new[q] = affine_step<T, METHOD, S, A, B, C, E>(y[q], A{a.v[q]}, bq, C{c.v[q]}, eq, w.v[q],
+                                                          kNeedU ? u.v[q] : (T)0, dt, half_dt, rdt, sqrt_dt);
       }
     }
     // (the step count of the next output lives in a scalar register: a step that is not an output time -- all but a few
     //  of them -- pays one scalar compare, and the output code is a cold block of its own)
-    if (__builtin_expect(k + 1 == next_out, 0)) {
-      while (j < p.n_out && p.out_step[j] == k + 1) {
-        const T w0 = p.out_w[2 * j], w1 = p.out_w[2 * j + 1];
+    if (__builtin_expect(due, 0)) {
+      while (j < p.n_out && uniform_load(p.out_step, j) == k + 1) {
+        const T w0 = uniform_load(p.out_w, 2 * j), w1 = uniform_load(p.out_w, 2 * j + 1);
         const bool exact = (w0 == (T)0 && w1 == (T)1);
         S o[W];
 #pragma unroll
-        for (int q = 0; q < W; ++q) o[q] = exact ? y1[q] : (w0 * y[q] + w1 * y1[q]);
+        for (int q = 0; q < W; ++q) o[q] = exact ? y_new[q] : (w0 * y_old[q] + w1 * y_new[q]);
         Pack<T, W> ov;
 #pragma unroll
         for (int q = 0; q < W; ++q) ov.v[q] = primal<T>(o[q]);
@@ -421,22 +463,24 @@ __global__ void __launch_bounds__(kBlock) trajectory_kernel(const TrajArgs<T> p)
         }
         ++j;
       }
-      next_out = next_output_step(p.out_step, j, p.n_out);
+      next_out = next_output_uniform(p.out_step, j, p.n_out);
     }
+    if constexpr (!kInPlace) {
 #pragma unroll
-    for (int q = 0; q < W; ++q) y[q] = y1[q];
+      for (int q = 0; q < W; ++q) y[q] = y1[q];
+    }
   }
 }
 
-template <typename T, int METHOD, bool SENS>
+template <typename T, int METHOD, bool SENS, bool LINEAR = false>
 static hipError_t launch_traj_ms(const TrajArgs<T>& p, bool vec, hipStream_t s) {
   if (vec) {
     const int64_t lanes = p.n >> 2;
-    hipLaunchKernelGGL((trajectory_kernel<T, METHOD, 4, SENS>), dim3((unsigned)((lanes + kBlock - 1) / kBlock)),
-                       dim3(kBlock), 0, s, p);
+    hipLaunchKernelGGL((trajectory_kernel<T, METHOD, 4, SENS, false, LINEAR>),
+                       dim3((unsigned)((lanes + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, p);
   } else {
-    hipLaunchKernelGGL((trajectory_kernel<T, METHOD, 1, SENS>), dim3((unsigned)((p.n + kBlock - 1) / kBlock)),
-                       dim3(kBlock), 0, s, p);
+    hipLaunchKernelGGL((trajectory_kernel<T, METHOD, 1, SENS, false, LINEAR>),
+                       dim3((unsigned)((p.n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, p);
   }
   return hipGetLastError();
 }
@@ -459,6 +503,10 @@ static hipError_t launch_traj_m(const TrajArgs<T>& p, bool vec, hipStream_t s) {
   if (p.cstride != 0) {            // coefficient tables (values only)
     if (p.sens) return hipErrorNotSupported;
     return launch_traj_timed<T, METHOD>(p, vec, s);
+  }
+  if (p.b == nullptr && p.e == nullptr) {   // both shifts zero: the linear form (values only)
+    if (p.sens) return hipErrorNotSupported;
+    return launch_traj_ms<T, METHOD, false, true>(p, vec, s);
   }
   return p.sens ? launch_traj_ms<T, METHOD, true>(p, vec, s) : launch_traj_ms<T, METHOD, false>(p, vec, s);
 }
@@ -490,6 +538,8 @@ hipError_t launch_trajectory_affine_diag(void* ys, void* sens, const void* y0, i
   p.n_out = tr->n_out;
   p.key = key;
   p.key_dev = key_dev;
+  if ((b == nullptr) != (e == nullptr)) return hipErrorInvalidValue;   // the linear form takes BOTH shifts as null
+  if (b == nullptr && (cstride != 0 || sens)) return hipErrorInvalidValue;
   if (p.n <= 0 || p.n_steps <= 0) return hipSuccess;
   const bool can_vec = (d % 4 == 0) && (key.elem0 % 4 == 0) && aligned16(ys) && aligned16(y0) && aligned16(a) &&
                        aligned16(b) && aligned16(c) && aligned16(e) && ((p.n * sizeof(T)) % 16 == 0) &&

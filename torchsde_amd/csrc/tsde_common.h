@@ -89,6 +89,16 @@ TSDE_D void store(T* __restrict__ p, int64_t i, const Pack<T, W>& r) {
   }
 }
 
+// Element i of a table that the HOST (or an earlier kernel on the stream) wrote before the launch and that no thread of
+// the running kernel writes: a solve's step rows, Brownian cells and output map (tsde_traj_t), the entropy word. That is
+// what makes it legal to read it through the constant address space -- where the compiler, which cannot prove that the
+// kernel's own stores to its outputs leave a plain global pointer alone, issues a scalar load for a wave-uniform index and
+// knows the value to be uniform, so everything computed from it stays on the scalar unit. Loads only.
+template <typename T>
+TSDE_D T uniform_load(const T* p, int64_t i) {
+  return *(const __attribute__((address_space(4))) T*)(p + i);
+}
+
 // A scalar coefficient of a step kernel: a launch-time constant, or a word in DEVICE memory that an earlier kernel on
 // the stream wrote (adaptive stepping without a host round trip per attempt: the step size, dt/2, sqrt(dt), 1/dt and
 // the interpolation weights of an attempt are produced by the controller kernel, csrc/adaptive.hip). On the C ABI such

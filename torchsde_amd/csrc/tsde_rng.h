@@ -49,6 +49,54 @@ TSDE_HD u32x4 philox4x32_10(u32x4 c, uint32_t k0, uint32_t k1) {
   return c;
 }
 
+// The same ten rounds with the two values of rounds 0 and 1 that depend on (c.y, c.z, k0) alone handed in. A solver's step
+// loop draws node 0 of one cell per step: c.y, c.z and the key are the same for every lane, so `philox_head` is work for
+// the scalar unit (plain ^ and *: TSDE_XOR3 is a vector-only instruction and would pull its operands into vector registers),
+// and only what depends on the lane's own counter words c.x, c.w is left to the vector unit. Same words as
+// philox4x32_10(c, k0, k1) for every input when `h` = philox_head(c.y, c.z, k0).
+struct PhiloxHead {
+  uint32_t x1;   // word x after round 0: hi(kM1 * c.z) ^ c.y ^ k0
+  uint64_t px;   // round 1's product kM0 * x1
+};
+
+TSDE_HD PhiloxHead philox_head(uint32_t cy, uint32_t cz, uint32_t k0) {
+  PhiloxHead h;
+  h.x1 = (uint32_t)(((uint64_t)0xCD9E8D57u * cz) >> 32) ^ cy ^ k0;
+  h.px = (uint64_t)0xD2511F53u * h.x1;
+  return h;
+}
+
+TSDE_HD u32x4 philox4x32_10_headed(u32x4 c, uint32_t k0, uint32_t k1, const PhiloxHead& h) {
+  constexpr uint32_t kM0 = 0xD2511F53u, kM1 = 0xCD9E8D57u;
+  constexpr uint32_t kW0 = 0x9E3779B9u, kW1 = 0xBB67AE85u;
+  {   // round 0: word x is h.x1
+    const uint64_t p0 = (uint64_t)kM0 * c.x;
+    const u32x4 n = {h.x1, kM1 * c.z, TSDE_XOR3((uint32_t)(p0 >> 32), c.w, k1), (uint32_t)p0};
+    c = n;
+    k0 += kW0;
+    k1 += kW1;
+  }
+  {   // round 1: the product of word x is h.px; its high half meets the key before it meets the lane's word
+    const uint64_t p1 = (uint64_t)kM1 * c.z;
+    const u32x4 n = {TSDE_XOR3((uint32_t)(p1 >> 32), c.y, k0), (uint32_t)p1, c.w ^ ((uint32_t)(h.px >> 32) ^ k1),
+                     (uint32_t)h.px};
+    c = n;
+    k0 += kW0;
+    k1 += kW1;
+  }
+#pragma unroll
+  for (int r = 2; r < 10; ++r) {
+    const uint64_t p0 = (uint64_t)kM0 * c.x;
+    const uint64_t p1 = (uint64_t)kM1 * c.z;
+    const u32x4 n = {TSDE_XOR3((uint32_t)(p1 >> 32), c.y, k0), (uint32_t)p1,
+                     TSDE_XOR3((uint32_t)(p0 >> 32), c.w, k1), (uint32_t)p0};
+    c = n;
+    k0 += kW0;
+    k1 += kW1;
+  }
+  return c;
+}
+
 // Noise streams of one tree node.
 enum : uint32_t { kStreamW = 0, kStreamH = 1, kStreamA = 2 };
 
@@ -129,6 +177,33 @@ TSDE_D T normal1(const NoiseKey& key, uint64_t elem, uint32_t cell, uint64_t nod
   box_muller(a, b, n0, n1);
   return (lane & 1u) ? n1 : n0;
 }
+// The draws of one solver step as the trajectory kernels' step loops make them: node 0 of `cell`, whose Philox head is
+// the same for every lane and every stream (scalar work, once per step). Same normals as normal4 / normal1 with node = 0.
+struct StepNoise {
+  NoiseKey key;
+  uint32_t cell;
+  PhiloxHead head;
+  TSDE_D StepNoise(const NoiseKey& k, uint32_t cell_) : key(k), cell(cell_), head(philox_head(cell_, 0u, k.k0)) {}
+  TSDE_D u32x4 bits(uint64_t quad, uint32_t stream) const {
+    return philox4x32_10_headed(noise_counter(quad, cell, 0, stream), key.k0, key.k1, head);
+  }
+  template <typename T>
+  TSDE_D void normal4(uint64_t quad, uint32_t stream, T (&n)[4]) const {
+    const u32x4 r = bits(quad, stream);
+    box_muller(r.x, r.y, n[0], n[1]);
+    box_muller(r.z, r.w, n[2], n[3]);
+  }
+  template <typename T>
+  TSDE_D T normal1(uint64_t elem, uint32_t stream) const {
+    const u32x4 r = bits(elem >> 2, stream);
+    const uint32_t lane = (uint32_t)elem & 3u;
+    const uint32_t a = (lane & 2u) ? r.z : r.x;
+    const uint32_t b = (lane & 2u) ? r.w : r.y;
+    T n0, n1;
+    box_muller(a, b, n0, n1);
+    return (lane & 1u) ? n1 : n0;
+  }
+};
 #endif  // __HIPCC__
 
 }  // namespace tsde

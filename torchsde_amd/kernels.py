@@ -734,25 +734,76 @@ def _coefficient_tables(coefs, d, schedule, dtype, method):
     raise ValueError(f"coefficients must all be (d,) tensors or all (n_steps * {slots}, d) tables, got {sorted(shapes)}")
 
 
-def trajectory_affine_diag(ys, y0, drift_rate, drift_shift, diff_rate, diff_shift, method, schedule, bm, sens=None):
+class AffineCoefficients(tuple):
+    """(drift rate, drift shift, diffusion rate, diffusion shift) of an affine launch plan, with the plan's answer to
+    "are both shifts all zero?" (`linear`): such a solve runs the kernel's linear form, f = rate * y."""
+    linear = False
+
+
+def _all_zero(tensor):
+    """The one device-to-host read of an affine launch plan (`affine_plan`)."""
+    return not bool(torch.count_nonzero(tensor))
+
+
+def affine_plan(coefs, shift_sources, memo):
+    """`coefs` as `AffineCoefficients`: decides ONCE per plan whether the solve takes the linear form of the trajectory
+    kernel (``tsde_trajectory_affine_diag`` with null shifts), never per solve and never under stream capture.
+
+    `shift_sources`: what the two shift vectors were made from -- None or a Python number (known without looking), or
+    the owner's own tensor (a parameter, a tensor the user's code handed to an operator). `memo`: a dict that lives as
+    long as the plan's owner (the SDE module, its trust book); it holds the answer under the sources' identities and
+    version counters, so an in-place update of a shift (an optimiser step) costs one more read and everything else none.
+    (As for autograd's saved tensors, an edit through `.data` is invisible to the version counter.) Coefficient tables
+    (functions of t) and sources that are neither -- values folded afresh at every solve -- keep the general form."""
+    plan = AffineCoefficients(coefs)
+    if any(c.dim() != 1 for c in plan):
+        return plan
+    key, tensors = [], []
+    for c in shift_sources:
+        if c is None or isinstance(c, (bool, int, float)):
+            if c is not None and float(c) != 0.0:
+                return plan
+            key.append(None)
+        elif torch.is_tensor(c):
+            key.append((id(c), c._version, c.data_ptr()))
+            tensors.append(c)
+        else:
+            return plan
+    if not tensors:
+        plan.linear = True
+        return plan
+    key = tuple(key)
+    hit = memo.get("linear_form")
+    if hit is None or hit[0] != key:
+        if tensors[0].is_cuda and torch.cuda.is_current_stream_capturing():     # (no read inside a captured graph)
+            return plan
+        hit = memo["linear_form"] = (key, all(_all_zero(c.detach()) for c in tensors), tensors)   # (`tensors`: ids stay taken)
+    plan.linear = hit[1]
+    return plan
+
+
+def trajectory_affine_diag(ys, y0, drift_rate, drift_shift, diff_rate, diff_shift, method, schedule, bm, sens=None,
+                           linear=False):
     """All steps of an affine diagonal SDE in one launch (``tsde_trajectory_affine_diag``); writes ys[j] for the
     schedule's outputs. `bm` is the native BrownianInterval whose generated cells drive the steps. With
     `sens` (n_out, 5, rows, d) the path-wise sensitivities d ys / d (y0, the four coefficients) are written too
-    (``tsde_trajectory_affine_diag_sens``)."""
+    (``tsde_trajectory_affine_diag_sens``). `linear`: the plan found both shifts all zero (`affine_plan`): the entry gets
+    null shift pointers and runs the linear form (values, constant coefficients)."""
     _native.require_device(ys, y0, drift_rate, drift_shift, diff_rate, diff_shift, sens)
     rows, d = y0.shape
     coefs = (drift_rate, drift_shift, diff_rate, diff_shift)
     timed = _coefficient_tables(coefs, d, schedule, y0.dtype, method)
     if timed and sens is not None:
         raise ValueError("per-step coefficient tables: values only")
+    linear = bool(linear) and not timed and sens is None
     if schedule.dtype != y0.dtype or ys.dtype != y0.dtype:
         raise ValueError("schedule / output dtype must equal the state dtype")
     if not (ys.is_contiguous() and y0.is_contiguous()) or ys.shape != (schedule.n_out, rows, d):
         raise ValueError("ys must be a contiguous (n_out, rows, d) tensor and y0 contiguous")
     lib, dt_code, stream = _launch_env(y0)
     entropy_dev = bm._entropy_dev
-    tail = (rows, d, drift_rate.data_ptr(), drift_shift.data_ptr(), diff_rate.data_ptr(), diff_shift.data_ptr(),
-            int(method), schedule.struct(), bm._key, bm._elem0, None if entropy_dev is None else entropy_dev.data_ptr(),
+    tail = (rows, d, drift_rate.data_ptr(), None if linear else drift_shift.data_ptr(), diff_rate.data_ptr(),
+            None if linear else diff_shift.data_ptr(), int(method), schedule.struct(), bm._key, bm._elem0, None if entropy_dev is None else entropy_dev.data_ptr(),
             dt_code, stream)
     if timed:
         code = lib.tsde_trajectory_affine_diag_timed(ys.data_ptr(), y0.data_ptr(), *tail[:6], d, *tail[6:])

@@ -413,7 +413,10 @@ class BaseSDESolver:
             if {id(p) for p in base.parameters()} != {id(p) for p in own}:
                 return None
             return ("differentiable",) + tuple(own)
-        return spec[1:]
+        # (zero shifts -- geometric Brownian motion -- take the kernel's linear form: decided once per state of the module's
+        #  shift parameters, kept on the module)
+        own = base.closed_form_parameters()
+        return K.affine_plan(spec[1:], (own[1], own[3]), base.__dict__.setdefault("_tsde_affine_plan", {}))
 
     # ---- unchanged user modules whose f and g are per-channel expressions (recognise.py; their trust ledger: trust.py) ---
     _RECOGNISED_ATTR = trust.ATTR
@@ -468,6 +471,19 @@ class BaseSDESolver:
                 setattr(ledger.base, name, value)
         return ys
 
+    @staticmethod
+    def _shift_sources(found):
+        """What the drift's and the diffusion's shift vectors of a recognised affine form were made from, as
+        `kernels.affine_plan` takes them: None / a number, the user's own tensor, or (anything the interpretation
+        assembled itself: a new tensor at every solve) a marker that keeps the general form."""
+        out = []
+        for form in (found.f, found.g):
+            c = form.shift
+            if form.constant() or (torch.is_tensor(c) and id(c) not in found.users_tensors):
+                c = NotImplemented
+            out.append(c)
+        return out
+
     def _recognisable_bm(self, y0, ts):
         """This package's BrownianInterval of this solve if it and the state are what the recognised routes take, else None."""
         bm = self._native_bm()
@@ -506,7 +522,11 @@ class BaseSDESolver:
         key = ledger.key(found, y0, *(("bf16x3",) if spec[0] == "neural" and spec[2].precision != _native.PRECISION_F32
                                       else ()))
         verdict, reverify = ledger.verdict(key)
-        launch = spec[1:] if spec[0] == "affine_diagonal" else spec       # (what `_integrate_trajectory` takes)
+        launch = spec                                                      # (what `_integrate_trajectory` takes)
+        if spec[0] == "affine_diagonal":
+            # `mu * y`, `sigma * y` (no shift in the code, or the user's own all-zero tensor): the linear form; the answer
+            # stays in the object's book
+            launch = K.affine_plan(spec[1:], self._shift_sources(found), ledger.book)
         counters, base = ledger.counters, ledger.base
         if verdict is True:
             rate = ledger.counter_rate(key) if counters else {}
@@ -992,7 +1012,8 @@ class BaseSDESolver:
             K.trajectory_expr_diag(ys[1:], y0c, coefficients[1], coefficients[2], coefficients[3:],
                                    self._trajectory_code(), schedule, bm)
         else:
-            K.trajectory_affine_diag(ys[1:], y0c, *coefficients, self._trajectory_code(), schedule, bm)
+            K.trajectory_affine_diag(ys[1:], y0c, *coefficients, self._trajectory_code(), schedule, bm,
+                                     linear=getattr(coefficients, "linear", False))
         return ys
 
     @staticmethod

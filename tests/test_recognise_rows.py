@@ -42,7 +42,8 @@ def test_the_reference_examples_lorenz_system_is_followed_column_by_column():
     f, g = _evaluate(found, y, torch.tensor(0.3))
     assert torch.equal(f, sde.f(None, y)) and torch.equal(g, sde.g(None, y))
     text = specialise.source_rows(found.structure(), 0, torch.float32, 0)
-    assert "trajectory_prog_kernel<T, METHOD, 3, RowModel<T>>" in text and "x.v[0] * x.v[2]" in text
+    # (csrc/trajectory.hip launch_prog_w<T, METHOD, W, M> launches trajectory_prog_kernel<T, METHOD, W, M>, one lane per W)
+    assert "launch_prog_w<T, METHOD, 3, RowModel<T>>" in text and "x.v[0] * x.v[2]" in text
 
 
 class _Indexed(nn.Module):
@@ -147,3 +148,42 @@ def test_compiled_programs_find_a_writable_directory(monkeypatch, tmp_path):
     specialise._compile("0" * 24, "// nothing", "gfx950")
     assert str(specialise._state["0" * 24]).startswith("failed: OSError")
     specialise._state.pop("0" * 24, None)
+
+
+def _exports(path):
+    import subprocess
+    listed = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
+    return sorted(line.split()[-1] for line in listed.splitlines() if "tsde_specialised" in line)
+
+
+@pytest.mark.skipif(specialise.compiler() is None, reason="no hipcc: generated units cannot be compiled here")
+def test_every_kind_of_generated_unit_compiles_and_exports_one_entry_point(tmp_path):
+    """One small program as a unit of every kind, and the Lorenz system as a rows unit: each compiles for gfx950 with the
+    flags `specialise._compile` uses (no GPU is needed for that) and exports exactly one entry point, the one `_ENTRY` names
+    for its family."""
+    import subprocess
+    ops = {name: number for number, name in specialise._OPS.items()}
+
+    def word(op, src=specialise._SRC_STACK, k=0):
+        return ops[op] | src << 8 | k << 16
+    state, const, time = specialise._SRC_STATE, specialise._SRC_CONST, specialise._SRC_TIME
+    # f = -(y * c0) + sin(t), g = tanh(y) * c1, and for the derivative schemes c1 - tanh(y)^2
+    f = (word("load", state), word("mul", const, 0), word("neg"), word("load", time), word("sin"), word("add"))
+    g = (word("load", state), word("tanh"), word("mul", const, 1))
+    h = (word("load", state), word("tanh"), word("square"), word("rsub", const, 1))
+    lorenz = recognise_rows.recognise_rows(ForwardSDE(_Lorenz()), torch.tensor(0.3), torch.randn(7, 3)).structure()
+    units = {
+        "values_f32": ("values", specialise.source(f, g, h, 2, torch.float32, 1)),
+        "values_f64": ("values", specialise.source(f, g, h, 2, torch.float64, 4)),
+        "sens": ("sens", specialise.source(f, g, h, 2, torch.float32, 1, kind="sens")),
+        "additive4": ("additive", specialise.source(f, (), (), 1, torch.float32, 0, kind="additive4")),
+        "additive8": ("additive", specialise.source(f, (), (), 1, torch.float32, 3, kind="additive8")),
+        "additive16": ("additive", specialise.source(f, (), (), 1, torch.float32, 4, kind="additive16")),
+        "rows": ("rows", specialise.source_rows(lorenz, 0, torch.float32, 0)),
+    }
+    for name, (family, text) in units.items():
+        src, out = tmp_path / f"{name}.hip", tmp_path / f"{name}.so"
+        src.write_text(text)
+        done = subprocess.run(specialise._compile_command("gfx950", str(out), str(src)), capture_output=True, text=True)
+        assert done.returncode == 0, (name, done.stderr[-2000:])
+        assert _exports(str(out)) == [specialise._ENTRY[family][0]], name

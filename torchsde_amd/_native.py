@@ -326,5 +326,13 @@ def ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
 
+def trajectory_tail(schedule, bm, *last):
+    """What the argument list of every trajectory launch ends with: the schedule (kernels.TrajectorySchedule), the noise key
+    of the BrownianInterval `bm` (entropy, first element, the entropy's device copy if it has one), then `last` (dtype code,
+    stream)."""
+    entropy_dev = bm._entropy_dev
+    return (schedule.struct(), bm._key, bm._elem0, None if entropy_dev is None else entropy_dev.data_ptr()) + last
+
+
 def contiguous(t):
     return t if t.is_contiguous() else t.contiguous()

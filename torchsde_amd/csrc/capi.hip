@@ -21,6 +21,14 @@ int bad_arg(const char* where, const char* what) {
   return (int)hipErrorInvalidValue;
 }
 
+// What is wrong with a step schedule (null: nothing); the entry points return it through `bad_arg`.
+const char* schedule_problem(const tsde_traj_t* traj) {
+  if (traj->n_steps < 0 || traj->n_out < 0) return "negative schedule length";
+  if (traj->n_steps > 0 && (!traj->step_rows || !traj->cells)) return "schedule without step rows";
+  if (traj->n_out > 0 && (!traj->out_step || !traj->out_w)) return "schedule without output map";
+  return nullptr;
+}
+
 tsde::NoiseKey make_key(uint64_t entropy, uint64_t elem0) {
   tsde::NoiseKey k;
   k.k0 = (uint32_t)entropy;
@@ -502,9 +510,7 @@ static int trajectory_affine_diag(const char* where, void* ys, void* sens, const
   if (coef_step_stride != 0 && sens) return bad_arg(where, "per-step coefficients: values only");
   if (rows < 0 || d <= 0) return bad_arg(where, "need rows >= 0 and d > 0");
   if (method < TSDE_TRAJ_EULER || method > TSDE_TRAJ_EULER_HEUN) return bad_arg(where, "unknown method");
-  if (traj->n_steps < 0 || traj->n_out < 0) return bad_arg(where, "negative schedule length");
-  if (traj->n_steps > 0 && (!traj->step_rows || !traj->cells)) return bad_arg(where, "schedule without step rows");
-  if (traj->n_out > 0 && (!traj->out_step || !traj->out_w)) return bad_arg(where, "schedule without output map");
+  if (const char* bad = schedule_problem(traj)) return bad_arg(where, bad);
   const hipStream_t s = (hipStream_t)stream;
   const tsde::NoiseKey key = make_key(entropy, elem0);
   ProfScope p(TSDE_KID_TRAJECTORY, s);
@@ -562,9 +568,7 @@ int tsde_trajectory_mlp_diag(void* ys, const void* y0, int64_t rows, int64_t d, 
       method != TSDE_TRAJ_MIDPOINT && method != TSDE_TRAJ_SRK)
     return bad_arg(where, "method must be Euler, Milstein, midpoint or SRK");
   if (elem0 % 4 != 0) return bad_arg(where, "elem0 must be a multiple of 4");
-  if (traj->n_steps < 0 || traj->n_out < 0) return bad_arg(where, "negative schedule length");
-  if (traj->n_steps > 0 && (!traj->step_rows || !traj->cells)) return bad_arg(where, "schedule without step rows");
-  if (traj->n_out > 0 && (!traj->out_step || !traj->out_w)) return bad_arg(where, "schedule without output map");
+  if (const char* bad = schedule_problem(traj)) return bad_arg(where, bad);
   const hipStream_t s = (hipStream_t)stream;
   ProfScope p(TSDE_KID_TRAJECTORY, s);
   return fail(tsde::launch_trajectory_mlp_diag(ys, y0, rows, d, hidden, w1, b1, w2, b2, diff_rate, diff_shift,
@@ -584,9 +588,7 @@ static int prog_diag(const char* where, void* ys, void* sens, const int8_t* para
   if (method < TSDE_TRAJ_EULER || method > TSDE_TRAJ_EULER_HEUN) return bad_arg(where, "unknown method");
   if ((method == TSDE_TRAJ_MILSTEIN_ITO || method == TSDE_TRAJ_MILSTEIN_STRAT) && dg_len < 1)
     return bad_arg(where, "Milstein needs the program of the diffusion's derivative");
-  if (traj->n_steps < 0 || traj->n_out < 0) return bad_arg(where, "negative schedule length");
-  if (traj->n_steps > 0 && (!traj->step_rows || !traj->cells)) return bad_arg(where, "schedule without step rows");
-  if (traj->n_out > 0 && (!traj->out_step || !traj->out_w)) return bad_arg(where, "schedule without output map");
+  if (const char* bad = schedule_problem(traj)) return bad_arg(where, bad);
   if (sens && param_slot)
     for (int k = 0; k < n_const; ++k)
       if (param_slot[k] == 0 || param_slot[k] >= TSDE_TRAJ_SENS || param_slot[k] < -1)
@@ -640,9 +642,7 @@ int tsde_trajectory_mlp_additive(void* ys, const void* y0, int64_t rows, int64_t
   if (rows * d >= (int64_t(1) << 30)) return bad_arg(where, "need rows * d < 2^30 (32-bit lane offsets)");
   if (method != TSDE_TRAJ_EULER && method != TSDE_TRAJ_MIDPOINT && method != TSDE_TRAJ_SRK)
     return bad_arg(where, "method must be Euler, midpoint or SRK (SRA1)");
-  if (traj->n_steps < 0 || traj->n_out < 0) return bad_arg(where, "negative schedule length");
-  if (traj->n_steps > 0 && (!traj->step_rows || !traj->cells)) return bad_arg(where, "schedule without step rows");
-  if (traj->n_out > 0 && (!traj->out_step || !traj->out_w)) return bad_arg(where, "schedule without output map");
+  if (const char* bad = schedule_problem(traj)) return bad_arg(where, bad);
   const hipStream_t s = (hipStream_t)stream;
   ProfScope p(TSDE_KID_TRAJECTORY, s);
   const hipError_t e = tsde::launch_trajectory_mlp_additive(ys, y0, rows, d, m, drift, g_table, g_time_dependent != 0, method,
@@ -663,9 +663,7 @@ int tsde_trajectory_prog_additive(void* ys, const void* y0, int64_t rows, int64_
   if (m < 1 || m > 16) return bad_arg(where, "need 1 <= m <= 16 Brownian channels");
   if (method != TSDE_TRAJ_EULER && method != TSDE_TRAJ_MIDPOINT && method != TSDE_TRAJ_SRK)
     return bad_arg(where, "method must be Euler, midpoint or SRK (SRA1)");
-  if (traj->n_steps < 0 || traj->n_out < 0) return bad_arg(where, "negative schedule length");
-  if (traj->n_steps > 0 && (!traj->step_rows || !traj->cells)) return bad_arg(where, "schedule without step rows");
-  if (traj->n_out > 0 && (!traj->out_step || !traj->out_w)) return bad_arg(where, "schedule without output map");
+  if (const char* bad = schedule_problem(traj)) return bad_arg(where, bad);
   const hipStream_t s = (hipStream_t)stream;
   const tsde::NoiseKey key = make_key(entropy, elem0);
   ProfScope p(TSDE_KID_TRAJECTORY, s);
@@ -722,9 +720,7 @@ int tsde_trajectory_mlp_general(void* ys, const void* y0, int64_t rows, int64_t 
     return bad_arg(where, "method must be Euler, midpoint or SRK");
   if (method == TSDE_TRAJ_SRK && noise == TSDE_NOISE_GENERAL)
     return bad_arg(where, "SRK (SRID2) takes diagonal or scalar noise, like the reference's (srk.py:34-35)");
-  if (traj->n_steps < 0 || traj->n_out < 0) return bad_arg(where, "negative schedule length");
-  if (traj->n_steps > 0 && (!traj->step_rows || !traj->cells)) return bad_arg(where, "schedule without step rows");
-  if (traj->n_out > 0 && (!traj->out_step || !traj->out_w)) return bad_arg(where, "schedule without output map");
+  if (const char* bad = schedule_problem(traj)) return bad_arg(where, bad);
   const hipStream_t s = (hipStream_t)stream;
   ProfScope p(TSDE_KID_TRAJECTORY, s);
   const hipError_t e = tsde::launch_trajectory_mlp_general(ys, y0, rows, d, m, noise, drift, diffusion, method, traj,
@@ -753,9 +749,7 @@ int tsde_trajectory_expr_diag_timed(void* ys, const void* y0, int64_t rows, int6
   if (method < TSDE_TRAJ_EULER || method > TSDE_TRAJ_EULER_HEUN) return bad_arg(where, "unknown method");
   if (f_kind < TSDE_FN_IDENTITY || f_kind > TSDE_FN_POLY3 || g_kind < TSDE_FN_IDENTITY || g_kind > TSDE_FN_POLY3)
     return bad_arg(where, "unknown function code");
-  if (traj->n_steps < 0 || traj->n_out < 0) return bad_arg(where, "negative schedule length");
-  if (traj->n_steps > 0 && (!traj->step_rows || !traj->cells)) return bad_arg(where, "schedule without step rows");
-  if (traj->n_out > 0 && (!traj->out_step || !traj->out_w)) return bad_arg(where, "schedule without output map");
+  if (const char* bad = schedule_problem(traj)) return bad_arg(where, bad);
   const hipStream_t s = (hipStream_t)stream;
   const tsde::NoiseKey key = make_key(entropy, elem0);
   ProfScope p(TSDE_KID_TRAJECTORY, s);
@@ -891,10 +885,7 @@ static const char* rheun_mlp_problem(int64_t rows, int64_t d, int64_t m, int noi
   if (tsde::rheun_footprint(d, m, drift->hidden, diffusion->hidden, diffusion->out, noise, drift->n_mid, diffusion->n_mid) == 0)
     return "no kernel for this shape";
   if (rows * d >= (int64_t(1) << 30)) return "need rows * d < 2^30 (32-bit lane offsets)";
-  if (traj->n_steps < 0 || traj->n_out < 0) return "negative schedule length";
-  if (traj->n_steps > 0 && (!traj->step_rows || !traj->cells)) return "schedule without step rows";
-  if (traj->n_out > 0 && (!traj->out_step || !traj->out_w)) return "schedule without output map";
-  return nullptr;
+  return schedule_problem(traj);
 }
 
 int tsde_rheun_mlp_forward(void* ys, void* z_out, const void* y0, int64_t rows, int64_t d, int64_t m, int noise,

@@ -1350,103 +1350,27 @@ __global__ void __launch_bounds__(kBlock) trajectory_prog_additive_kernel(const 
   }
 }
 
-template <typename T, int METHOD, int MP>
-static hipError_t launch_additive_mp(const ProgAdditiveArgs<T>& q, bool vec, hipStream_t s) {
-  const int64_t n = q.base.n;
-  if (vec) {
-    hipLaunchKernelGGL((trajectory_prog_additive_kernel<T, METHOD, 4, MP>), dim3((unsigned)(((n >> 2) + kBlock - 1) / kBlock)),
-                       dim3(kBlock), 0, s, q);
-  } else {
-    hipLaunchKernelGGL((trajectory_prog_additive_kernel<T, METHOD, 1, MP>), dim3((unsigned)((n + kBlock - 1) / kBlock)),
-                       dim3(kBlock), 0, s, q);
-  }
-  return hipGetLastError();
+// ---- launching a program kernel ---------------------------------------------------------------------------------------------
+// Written once, for the interpreter (`launch_trajectory_prog_diag`, `launch_trajectory_prog_additive` below) and for the units
+// torchsde_amd/specialise.py generates: such a unit is a model struct plus one call of these helpers with that model. They are
+// templates, so a unit instantiates the kernels of its own model and nothing else.
+inline NoiseKey noise_key(uint64_t entropy, uint64_t elem0) {
+  NoiseKey k;
+  k.k0 = (uint32_t)entropy;
+  k.k1 = (uint32_t)(entropy >> 32);
+  k.elem0 = elem0;
+  return k;
 }
 
-template <typename T, int METHOD>
-static hipError_t launch_additive_m(const ProgAdditiveArgs<T>& q, bool vec, hipStream_t s) {
-  if (q.m <= 4) return launch_additive_mp<T, METHOD, 4>(q, vec, s);
-  if (q.m <= 8) return launch_additive_mp<T, METHOD, 8>(q, vec, s);
-  if (q.m <= 16) return launch_additive_mp<T, METHOD, 16>(q, vec, s);
-  return hipErrorInvalidValue;
-}
-
+// `code`: the interpreter's words, the f, g and dg programs back to back (at most kProgWords: the caller checks); a generated
+// model has its programs in its code and passes none.
 template <typename T>
-hipError_t launch_trajectory_prog_additive(void* ys, const void* y0, int64_t rows, int64_t d, int64_t m, const uint32_t* code,
-                                           int f_len, const void* consts, int n_const, const void* gtab, int time_dependent,
-                                           int method, const tsde_traj_t* tr, NoiseKey key, const uint64_t* key_dev,
-                                           hipStream_t s) {
-  ProgAdditiveArgs<T> q;
-  ProgArgs<T>& p = q.base;
-  p.ys = (T*)ys;
-  p.y0 = (const T*)y0;
-  if (f_len > kProgWords) return hipErrorInvalidValue;
-  for (int w = 0; w < kProgWords; ++w) p.code[w] = w < f_len ? code[w] : 0u;
-  p.consts = (const T*)consts;
-  p.f_len = f_len;
-  p.g_len = 0;
-  p.dg_len = 0;
-  p.n_const = n_const;
-  p.scalar_noise = 0;
-  p.rows = (const T*)tr->step_rows;
-  p.cells = tr->cells;
-  p.out_step = tr->out_step;
-  p.out_w = (const T*)tr->out_w;
-  p.n = rows * d;
-  p.d = d;
-  p.n_steps = tr->n_steps;
-  p.n_out = tr->n_out;
-  p.key = key;
-  p.key_dev = key_dev;
-  if (p.n <= 0 || p.n_steps <= 0) return hipSuccess;
-  const int slots = method == kEuler ? 1 : 2;
-  q.gtab = (const T*)gtab;
-  q.slot_stride = time_dependent ? m * d : 0;
-  q.step_stride = time_dependent ? (int64_t)slots * m * d : 0;
-  q.m = (int32_t)m;
-  q.quads = (m % 4 == 0 && key.elem0 % 4 == 0) ? 1 : 0;
-  const bool can_vec = (d % 4 == 0) && aligned16(ys) && aligned16(y0) && aligned16(gtab) && ((p.n * sizeof(T)) % 16 == 0);
-  const bool vec = can_vec && (p.n >> 2) >= kTrajVecMinGroups;
-  switch (method) {
-    case kEuler: return launch_additive_m<T, kEuler>(q, vec, s);
-    case kMidpoint: return launch_additive_m<T, kMidpoint>(q, vec, s);
-    case kSrk: return launch_additive_m<T, kSrk>(q, vec, s);
-    default: return hipErrorInvalidValue;
-  }
-}
-
-#ifndef TSDE_SPECIALISE_TU
-template hipError_t launch_trajectory_prog_additive<float>(void*, const void*, int64_t, int64_t, int64_t, const uint32_t*, int,
-                                                           const void*, int, const void*, int, int, const tsde_traj_t*,
-                                                           NoiseKey, const uint64_t*, hipStream_t);
-template hipError_t launch_trajectory_prog_additive<double>(void*, const void*, int64_t, int64_t, int64_t, const uint32_t*, int,
-                                                            const void*, int, const void*, int, int, const tsde_traj_t*,
-                                                            NoiseKey, const uint64_t*, hipStream_t);
-#endif
-
-template <typename T, int METHOD>
-static hipError_t launch_prog_m(const ProgArgs<T>& p, bool vec, hipStream_t s) {
-  if (vec) {
-    const int64_t lanes = p.n >> 2;
-    hipLaunchKernelGGL((trajectory_prog_kernel<T, METHOD, 4>), dim3((unsigned)((lanes + kBlock - 1) / kBlock)), dim3(kBlock),
-                       0, s, p);
-  } else {
-    hipLaunchKernelGGL((trajectory_prog_kernel<T, METHOD, 1>), dim3((unsigned)((p.n + kBlock - 1) / kBlock)), dim3(kBlock),
-                       0, s, p);
-  }
-  return hipGetLastError();
-}
-
-template <typename T>
-hipError_t launch_trajectory_prog_diag(void* ys, void* sens, const int8_t* param_slot, const void* y0, int64_t rows, int64_t d,
-                                       const uint32_t* code, int f_len, int g_len, int dg_len, const void* consts, int n_const,
-                                       int scalar_noise, int method, const tsde_traj_t* tr, NoiseKey key,
-                                       const uint64_t* key_dev, hipStream_t s) {
+static ProgArgs<T> prog_args(void* ys, const void* y0, int64_t rows, int64_t d, const void* consts, int n_const,
+                             int scalar_noise, const tsde_traj_t* tr, NoiseKey key, const uint64_t* key_dev,
+                             const uint32_t* code = nullptr, int f_len = 0, int g_len = 0, int dg_len = 0) {
   ProgArgs<T> p;
   p.ys = (T*)ys;
   p.y0 = (const T*)y0;
-  if (f_len + g_len + dg_len > kProgWords) return hipErrorInvalidValue;
-  for (int w = 0; w < kProgWords; ++w) p.code[w] = w < f_len + g_len + dg_len ? code[w] : 0u;
   p.consts = (const T*)consts;
   p.f_len = f_len;
   p.g_len = g_len;
@@ -1463,37 +1387,141 @@ hipError_t launch_trajectory_prog_diag(void* ys, void* sens, const int8_t* param
   p.n_out = tr->n_out;
   p.key = key;
   p.key_dev = key_dev;
+  for (int w = 0; w < kProgWords; ++w) p.code[w] = (code && w < f_len + g_len + dg_len) ? code[w] : 0u;
+  return p;
+}
+
+template <typename T>
+static ProgSensArgs<T> prog_sens_args(const ProgArgs<T>& base, void* sens, const int8_t* param_slot) {
+  ProgSensArgs<T> q;
+  q.base = base;
+  q.sens = (T*)sens;
+  for (int k = 0; k < kProgParamRows; ++k) q.param_slot[k] = (param_slot && k < base.n_const) ? param_slot[k] : (int8_t)-1;
+  return q;
+}
+
+// `base`: g_len = dg_len = 0 and no scalar noise; `gtab`: (m, d), or one such matrix per stage time of every step
+template <typename T>
+static ProgAdditiveArgs<T> prog_additive_args(const ProgArgs<T>& base, int64_t m, const void* gtab, int time_dependent,
+                                              int method) {
+  const int slots = method == kEuler ? 1 : 2;
+  ProgAdditiveArgs<T> q;
+  q.base = base;
+  q.gtab = (const T*)gtab;
+  q.slot_stride = time_dependent ? m * base.d : 0;
+  q.step_stride = time_dependent ? (int64_t)slots * m * base.d : 0;
+  q.m = (int32_t)m;
+  q.quads = (m % 4 == 0 && base.key.elem0 % 4 == 0) ? 1 : 0;
+  return q;
+}
+
+// May a lane own 4 consecutive elements? (Scalar noise addresses the field by row: no alignment condition on elem0.)
+template <typename T>
+static bool prog_may_vec(const ProgArgs<T>& p) {
+  return (p.d % 4 == 0) && (p.scalar_noise || p.key.elem0 % 4 == 0) && aligned16(p.ys) && aligned16(p.y0) &&
+         ((p.n * sizeof(T)) % 16 == 0) && (p.n >> 2) >= kTrajVecMinGroups;
+}
+
+template <typename T>
+static bool prog_additive_may_vec(const ProgAdditiveArgs<T>& q) {
+  const ProgArgs<T>& p = q.base;
+  return (p.d % 4 == 0) && aligned16(p.ys) && aligned16(p.y0) && aligned16(q.gtab) && ((p.n * sizeof(T)) % 16 == 0) &&
+         (p.n >> 2) >= kTrajVecMinGroups;
+}
+
+// One lane per W elements (W = d: per row, the row-coupled systems of specialise.source_rows). An empty problem launches nothing.
+template <typename T, int METHOD, int W, typename M = ProgModel<T, W>>
+static hipError_t launch_prog_w(const ProgArgs<T>& p, hipStream_t s) {
   if (p.n <= 0 || p.n_steps <= 0) return hipSuccess;
-  if (sens != nullptr) {
-    ProgSensArgs<T> q;
-    q.base = p;
-    q.sens = (T*)sens;
-    for (int k = 0; k < kProgParamRows; ++k) q.param_slot[k] = (param_slot && k < n_const) ? param_slot[k] : (int8_t)-1;
-    const dim3 grid((unsigned)((p.n + kBlock - 1) / kBlock));
-    switch (method) {
-      case kEuler: hipLaunchKernelGGL((trajectory_prog_sens_kernel<T, kEuler>), grid, dim3(kBlock), 0, s, q); break;
-      case kMilIto: hipLaunchKernelGGL((trajectory_prog_sens_kernel<T, kMilIto>), grid, dim3(kBlock), 0, s, q); break;
-      case kMilStrat: hipLaunchKernelGGL((trajectory_prog_sens_kernel<T, kMilStrat>), grid, dim3(kBlock), 0, s, q); break;
-      case kMidpoint: hipLaunchKernelGGL((trajectory_prog_sens_kernel<T, kMidpoint>), grid, dim3(kBlock), 0, s, q); break;
-      case kSrk: hipLaunchKernelGGL((trajectory_prog_sens_kernel<T, kSrk>), grid, dim3(kBlock), 0, s, q); break;
-      case kHeun: hipLaunchKernelGGL((trajectory_prog_sens_kernel<T, kHeun>), grid, dim3(kBlock), 0, s, q); break;
-      case kEulerHeun: hipLaunchKernelGGL((trajectory_prog_sens_kernel<T, kEulerHeun>), grid, dim3(kBlock), 0, s, q); break;
-      default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+  hipLaunchKernelGGL((trajectory_prog_kernel<T, METHOD, W, M>), dim3((unsigned)((p.n / W + kBlock - 1) / kBlock)), dim3(kBlock),
+                     0, s, p);
+  return hipGetLastError();
+}
+
+template <typename T, int METHOD, template <typename, int> class M = ProgModel>
+static hipError_t launch_prog_m(const ProgArgs<T>& p, hipStream_t s) {
+  return prog_may_vec(p) ? launch_prog_w<T, METHOD, 4, M<T, 4>>(p, s) : launch_prog_w<T, METHOD, 1, M<T, 1>>(p, s);
+}
+
+template <typename T, int METHOD, typename M = ProgSensModel<T>>
+static hipError_t launch_prog_sens_m(const ProgSensArgs<T>& q, hipStream_t s) {
+  const int64_t n = q.base.n;
+  if (n <= 0 || q.base.n_steps <= 0) return hipSuccess;
+  hipLaunchKernelGGL((trajectory_prog_sens_kernel<T, METHOD, M>), dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0,
+                     s, q);
+  return hipGetLastError();
+}
+
+// `MP`: the channel-count class (4, 8, 16), q.m <= MP
+template <typename T, int METHOD, int MP, template <typename, int> class M = ProgModel>
+static hipError_t launch_additive_mp(const ProgAdditiveArgs<T>& q, hipStream_t s) {
+  const int64_t n = q.base.n;
+  if (n <= 0 || q.base.n_steps <= 0) return hipSuccess;
+  if (prog_additive_may_vec(q)) {
+    hipLaunchKernelGGL((trajectory_prog_additive_kernel<T, METHOD, 4, MP, M<T, 4>>),
+                       dim3((unsigned)(((n >> 2) + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, q);
+  } else {
+    hipLaunchKernelGGL((trajectory_prog_additive_kernel<T, METHOD, 1, MP, M<T, 1>>), dim3((unsigned)((n + kBlock - 1) / kBlock)),
+                       dim3(kBlock), 0, s, q);
   }
-  // (scalar noise addresses the field by row: no alignment condition on elem0)
-  const bool can_vec = (d % 4 == 0) && (scalar_noise || key.elem0 % 4 == 0) && aligned16(ys) && aligned16(y0) &&
-                       ((p.n * sizeof(T)) % 16 == 0);
-  const bool vec = can_vec && (p.n >> 2) >= kTrajVecMinGroups;
+  return hipGetLastError();
+}
+
+template <typename T, int METHOD>
+static hipError_t launch_additive_m(const ProgAdditiveArgs<T>& q, hipStream_t s) {
+  if (q.m <= 4) return launch_additive_mp<T, METHOD, 4>(q, s);
+  if (q.m <= 8) return launch_additive_mp<T, METHOD, 8>(q, s);
+  if (q.m <= 16) return launch_additive_mp<T, METHOD, 16>(q, s);
+  return hipErrorInvalidValue;
+}
+
+template <typename T>
+hipError_t launch_trajectory_prog_additive(void* ys, const void* y0, int64_t rows, int64_t d, int64_t m, const uint32_t* code,
+                                           int f_len, const void* consts, int n_const, const void* gtab, int time_dependent,
+                                           int method, const tsde_traj_t* tr, NoiseKey key, const uint64_t* key_dev,
+                                           hipStream_t s) {
+  if (f_len > kProgWords) return hipErrorInvalidValue;
+  const ProgAdditiveArgs<T> q = prog_additive_args(
+      prog_args<T>(ys, y0, rows, d, consts, n_const, 0, tr, key, key_dev, code, f_len), m, gtab, time_dependent, method);
   switch (method) {
-    case kEuler: return launch_prog_m<T, kEuler>(p, vec, s);
-    case kMilIto: return launch_prog_m<T, kMilIto>(p, vec, s);
-    case kMilStrat: return launch_prog_m<T, kMilStrat>(p, vec, s);
-    case kMidpoint: return launch_prog_m<T, kMidpoint>(p, vec, s);
-    case kSrk: return launch_prog_m<T, kSrk>(p, vec, s);
-    case kHeun: return launch_prog_m<T, kHeun>(p, vec, s);
-    case kEulerHeun: return launch_prog_m<T, kEulerHeun>(p, vec, s);
+    case kEuler: return launch_additive_m<T, kEuler>(q, s);
+    case kMidpoint: return launch_additive_m<T, kMidpoint>(q, s);
+    case kSrk: return launch_additive_m<T, kSrk>(q, s);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+#ifndef TSDE_SPECIALISE_TU
+template hipError_t launch_trajectory_prog_additive<float>(void*, const void*, int64_t, int64_t, int64_t, const uint32_t*, int,
+                                                           const void*, int, const void*, int, int, const tsde_traj_t*,
+                                                           NoiseKey, const uint64_t*, hipStream_t);
+template hipError_t launch_trajectory_prog_additive<double>(void*, const void*, int64_t, int64_t, int64_t, const uint32_t*, int,
+                                                            const void*, int, const void*, int, int, const tsde_traj_t*,
+                                                            NoiseKey, const uint64_t*, hipStream_t);
+#endif
+
+// values, or (with `sens`) values and path-wise sensitivities
+template <typename T, int METHOD>
+static hipError_t launch_prog_diag_m(const ProgArgs<T>& p, void* sens, const int8_t* param_slot, hipStream_t s) {
+  if (sens != nullptr) return launch_prog_sens_m<T, METHOD>(prog_sens_args(p, sens, param_slot), s);
+  return launch_prog_m<T, METHOD>(p, s);
+}
+
+template <typename T>
+hipError_t launch_trajectory_prog_diag(void* ys, void* sens, const int8_t* param_slot, const void* y0, int64_t rows, int64_t d,
+                                       const uint32_t* code, int f_len, int g_len, int dg_len, const void* consts, int n_const,
+                                       int scalar_noise, int method, const tsde_traj_t* tr, NoiseKey key,
+                                       const uint64_t* key_dev, hipStream_t s) {
+  if (f_len + g_len + dg_len > kProgWords) return hipErrorInvalidValue;
+  const ProgArgs<T> p = prog_args<T>(ys, y0, rows, d, consts, n_const, scalar_noise, tr, key, key_dev, code, f_len, g_len, dg_len);
+  switch (method) {
+    case kEuler: return launch_prog_diag_m<T, kEuler>(p, sens, param_slot, s);
+    case kMilIto: return launch_prog_diag_m<T, kMilIto>(p, sens, param_slot, s);
+    case kMilStrat: return launch_prog_diag_m<T, kMilStrat>(p, sens, param_slot, s);
+    case kMidpoint: return launch_prog_diag_m<T, kMidpoint>(p, sens, param_slot, s);
+    case kSrk: return launch_prog_diag_m<T, kSrk>(p, sens, param_slot, s);
+    case kHeun: return launch_prog_diag_m<T, kHeun>(p, sens, param_slot, s);
+    case kEulerHeun: return launch_prog_diag_m<T, kEulerHeun>(p, sens, param_slot, s);
     default: return hipErrorInvalidValue;
   }
 }

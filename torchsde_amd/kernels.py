@@ -801,10 +801,8 @@ def trajectory_affine_diag(ys, y0, drift_rate, drift_shift, diff_rate, diff_shif
     if not (ys.is_contiguous() and y0.is_contiguous()) or ys.shape != (schedule.n_out, rows, d):
         raise ValueError("ys must be a contiguous (n_out, rows, d) tensor and y0 contiguous")
     lib, dt_code, stream = _launch_env(y0)
-    entropy_dev = bm._entropy_dev
     tail = (rows, d, drift_rate.data_ptr(), None if linear else drift_shift.data_ptr(), diff_rate.data_ptr(),
-            None if linear else diff_shift.data_ptr(), int(method), schedule.struct(), bm._key, bm._elem0, None if entropy_dev is None else entropy_dev.data_ptr(),
-            dt_code, stream)
+            None if linear else diff_shift.data_ptr(), int(method), *_native.trajectory_tail(schedule, bm, dt_code, stream))
     if timed:
         code = lib.tsde_trajectory_affine_diag_timed(ys.data_ptr(), y0.data_ptr(), *tail[:6], d, *tail[6:])
     elif sens is None:
@@ -831,46 +829,75 @@ def trajectory_expr_diag(ys, y0, f_kind, g_kind, coefs, method, schedule, bm):
     if not (ys.is_contiguous() and y0.is_contiguous()) or ys.shape != (schedule.n_out, rows, d):
         raise ValueError("ys must be a contiguous (n_out, rows, d) tensor and y0 contiguous")
     lib, dt_code, stream = _launch_env(y0)
-    entropy_dev = bm._entropy_dev
     arr = (ctypes.c_void_p * 8)(*[c.data_ptr() for c in coefs])
     code = lib.tsde_trajectory_expr_diag_timed(ys.data_ptr(), y0.data_ptr(), rows, d, arr, d if timed else 0, int(f_kind),
-                                               int(g_kind), int(method), schedule.struct(), bm._key, bm._elem0,
-                                               None if entropy_dev is None else entropy_dev.data_ptr(), dt_code, stream)
+                                               int(g_kind), int(method), *_native.trajectory_tail(schedule, bm, dt_code, stream))
     _native.check(code, "tsde_trajectory_expr_diag")
     return ys
 
 
+def _check_program_args(ys, y0, schedule, consts, g_table=None, per_channel=True):
+    """The argument checks of the program-kernel launches; returns (rows, d). `per_channel`: the constants are a
+    (n_const, d) table (a row-coupled system has one scalar per constant)."""
+    rows, d = y0.shape
+    tensors = [t for t in (ys, y0, consts, g_table) if t is not None]
+    if schedule.dtype != y0.dtype or any(t.dtype != y0.dtype for t in tensors):
+        raise ValueError("the schedule, ys, consts and g_table must have the state dtype")
+    if not all(t.is_contiguous() for t in tensors):
+        raise ValueError("ys, y0, consts and g_table must be contiguous")
+    if ys.shape != (schedule.n_out, rows, d):
+        raise ValueError(f"ys must be (n_out, rows, d) = {(schedule.n_out, rows, d)}, got {tuple(ys.shape)}")
+    if per_channel and (consts.dim() != 2 or consts.shape[1] != d):
+        raise ValueError(f"consts must be (n_const, {d}), got {tuple(consts.shape)}")
+    return rows, d
+
+
+def _same_bits(a, b):
+    """Equal element by element, NaN == NaN (a 0-d device tensor: reading it synchronises)."""
+    return ((a == b) | (a.isnan() & b.isnan())).all()
+
+
+def _compiled_or_interpreted(key, compiled, interpret, run_compiled, outputs):
+    """Fill `outputs` with the compiled unit of a program (`key`, `compiled`: specialise.lookup) once it is verified; otherwise
+    with the interpreter -- and the first time the unit is there, run it once beside the interpreter, compare bits and record
+    the verdict (one synchronisation per program, ever; never inside a stream capture, where the verdict stays open).
+    `interpret()` writes into `outputs`, `run_compiled(*tensors)` into tensors shaped like them."""
+    from . import specialise
+    if compiled is not None and specialise.verified(key):
+        run_compiled(*outputs)
+        return
+    interpret()
+    if compiled is not None and specialise.verified(key) is None and not torch.cuda.is_current_stream_capturing():
+        others = [torch.empty_like(t) for t in outputs]
+        run_compiled(*others)
+        same = _same_bits(others[0], outputs[0])
+        for other, out in zip(others[1:], outputs[1:]):
+            same = same & _same_bits(other, out)
+        specialise.set_verified(key, bool(same))
+
+
 def trajectory_prog_diag(ys, y0, f_code, g_code, dg_code, consts, scalar_noise, method, schedule, bm):
     """All steps of a diagonal- or scalar-noise SDE whose drift and diffusion are expression programs (tuples of
-    instruction words, recognise.RecognisedProgram) in one launch (``tsde_trajectory_prog_diag``)."""
+    instruction words, recognise.RecognisedProgram) in one launch (``tsde_trajectory_prog_diag``) -- or the same programs as
+    straight-line code, compiled at run time (specialise.py, `_compiled_or_interpreted`)."""
+    from . import specialise
     _native.require_device(ys, y0, consts)
-    rows, d = y0.shape
-    if schedule.dtype != y0.dtype or ys.dtype != y0.dtype or consts.dtype != y0.dtype:
-        raise ValueError("schedule / output / constant dtype must equal the state dtype")
-    if not (ys.is_contiguous() and y0.is_contiguous() and consts.is_contiguous()) or ys.shape != (schedule.n_out, rows, d) \
-            or consts.dim() != 2 or consts.shape[1] != d:
-        raise ValueError("ys must be a contiguous (n_out, rows, d) tensor, y0 contiguous, consts (n_const, d)")
+    rows, d = _check_program_args(ys, y0, schedule, consts)
     words = tuple(f_code) + tuple(g_code) + tuple(dg_code)
     lib, dt_code, stream = _launch_env(y0)
-    # the same programs as straight-line code, compiled at run time (specialise.py): used once the library is there AND its
-    # first launch has reproduced the interpreter's result bit for bit
-    from . import specialise
-    key, compiled = specialise.lookup(f_code, g_code, dg_code, consts.shape[0], y0.dtype, method, y0.device)
-    if compiled is not None and specialise.verified(key):
-        specialise.launch(compiled, ys, y0, consts, scalar_noise, schedule, bm, stream)
-        return ys
-    code = (ctypes.c_uint32 * len(words))(*words)            # a host array: the words travel in the kernel arguments
-    entropy_dev = bm._entropy_dev
-    rc = lib.tsde_trajectory_prog_diag(ys.data_ptr(), y0.data_ptr(), rows, d, code, len(f_code), len(g_code),
-                                       len(dg_code), consts.data_ptr(), consts.shape[0], int(bool(scalar_noise)), int(method),
-                                       schedule.struct(), bm._key, bm._elem0,
-                                       None if entropy_dev is None else entropy_dev.data_ptr(), dt_code, stream)
-    _native.check(rc, "tsde_trajectory_prog_diag")
-    if compiled is not None and specialise.verified(key) is None and not torch.cuda.is_current_stream_capturing():
-        other = torch.empty_like(ys)
-        specialise.launch(compiled, other, y0, consts, scalar_noise, schedule, bm, stream)
-        same = ((other == ys) | (other.isnan() & ys.isnan())).all()
-        specialise.set_verified(key, bool(same))             # (one synchronisation per program, ever)
+    n_const, scalar = consts.shape[0], int(bool(scalar_noise))
+
+    def interpret():
+        code = (ctypes.c_uint32 * len(words))(*words)            # a host array: the words travel in the kernel arguments
+        rc = lib.tsde_trajectory_prog_diag(ys.data_ptr(), y0.data_ptr(), rows, d, code, len(f_code), len(g_code), len(dg_code),
+                                           consts.data_ptr(), n_const, scalar, int(method),
+                                           *_native.trajectory_tail(schedule, bm, dt_code, stream))
+        _native.check(rc, "tsde_trajectory_prog_diag")
+
+    def run_compiled(out):
+        specialise.launch(compiled, schedule, bm, stream, out.data_ptr(), y0.data_ptr(), rows, d, consts.data_ptr(), n_const, scalar)
+    key, compiled = specialise.lookup(f_code, g_code, dg_code, n_const, y0.dtype, method, y0.device)
+    _compiled_or_interpreted(key, compiled, interpret, run_compiled, [ys])
     return ys
 
 
@@ -880,53 +907,43 @@ def trajectory_rows(ys, y0, structure, consts, method, schedule, bm):
     generated unit is not compiled yet (there is no interpreter for such systems: the caller stays stepwise)."""
     from . import specialise
     _native.require_device(ys, y0, consts)
-    rows, d = y0.shape
-    if ys.dtype != y0.dtype or consts.dtype != y0.dtype or schedule.dtype != y0.dtype:
-        raise ValueError("schedule / output / constant dtype must equal the state dtype")
-    if not (ys.is_contiguous() and y0.is_contiguous() and consts.is_contiguous()) or ys.shape != (schedule.n_out, rows, d):
-        raise ValueError("ys must be a contiguous (n_out, rows, d) tensor, y0 and consts contiguous")
+    rows, d = _check_program_args(ys, y0, schedule, consts, per_channel=False)
     key, compiled = specialise.lookup_rows(structure, structure[1][1], y0.dtype, method, y0.device)
     if compiled is None:
         return None
     _, _, stream = _launch_env(y0)
-    specialise.launch_rows(compiled, ys, y0, consts, schedule, bm, stream)
+    specialise.launch(compiled, schedule, bm, stream, ys.data_ptr(), y0.data_ptr(), rows, d, consts.data_ptr(), consts.numel())
     return ys
 
 
 def trajectory_prog_additive(ys, y0, f_code, consts, g_table, m, method, schedule, bm):
-    """All steps of an additive-noise SDE in one launch (``tsde_trajectory_prog_additive``): the drift an expression program,
-    the diffusion the table `g_table` -- (m, d), the transpose of the one matrix g, or (n_steps, slots, m, d) with the matrices
-    at the scheme's stage times (recognise.RecognisedAdditive)."""
+    """All steps of an additive-noise SDE in one launch (``tsde_trajectory_prog_additive``): the drift an expression program
+    (interpreted, or compiled at run time: `_compiled_or_interpreted`), the diffusion the table `g_table` -- (m, d), the
+    transpose of the one matrix g, or (n_steps, slots, m, d) with the matrices at the scheme's stage times
+    (recognise.RecognisedAdditive)."""
+    from . import specialise
     _native.require_device(ys, y0, consts, g_table)
-    rows, d = y0.shape
-    if any(t.dtype != y0.dtype for t in (ys, consts, g_table)) or schedule.dtype != y0.dtype:
-        raise ValueError("schedule / output / constant / table dtype must equal the state dtype")
-    if not (ys.is_contiguous() and y0.is_contiguous() and consts.is_contiguous() and g_table.is_contiguous()) \
-            or ys.shape != (schedule.n_out, rows, d) or consts.dim() != 2 or consts.shape[1] != d:
-        raise ValueError("ys must be a contiguous (n_out, rows, d) tensor, y0 contiguous, consts (n_const, d)")
+    rows, d = _check_program_args(ys, y0, schedule, consts, g_table)
     slots = 1 if int(method) == _native.TRAJ_EULER else 2
     timed = g_table.dim() == 4
     if tuple(g_table.shape) != ((schedule.n_steps, slots, m, d) if timed else (m, d)):
         raise ValueError(f"g_table must be (m, d) or (n_steps, {slots}, m, d), got {tuple(g_table.shape)}")
     lib, dt_code, stream = _launch_env(y0)
-    # the drift program as straight-line code, compiled at run time and verified bit for bit on first use (specialise.py)
-    from . import specialise
+    n_const = consts.shape[0]
+
+    def interpret():
+        code = (ctypes.c_uint32 * len(f_code))(*f_code)
+        rc = lib.tsde_trajectory_prog_additive(ys.data_ptr(), y0.data_ptr(), rows, d, int(m), code, len(f_code), consts.data_ptr(),
+                                               n_const, g_table.data_ptr(), int(timed), int(method),
+                                               *_native.trajectory_tail(schedule, bm, dt_code, stream))
+        _native.check(rc, "tsde_trajectory_prog_additive")
+
+    def run_compiled(out):
+        specialise.launch(compiled, schedule, bm, stream, out.data_ptr(), y0.data_ptr(), rows, d, int(m), consts.data_ptr(),
+                          n_const, g_table.data_ptr(), int(timed))
     kind = "additive4" if m <= 4 else "additive8" if m <= 8 else "additive16"
-    key, compiled = specialise.lookup(f_code, (), (), consts.shape[0], y0.dtype, method, y0.device, kind=kind)
-    if compiled is not None and specialise.verified(key):
-        specialise.launch_additive(compiled, ys, y0, consts, g_table, m, timed, schedule, bm, stream)
-        return ys
-    code = (ctypes.c_uint32 * len(f_code))(*f_code)
-    entropy_dev = bm._entropy_dev
-    rc = lib.tsde_trajectory_prog_additive(ys.data_ptr(), y0.data_ptr(), rows, d, int(m), code, len(f_code), consts.data_ptr(),
-                                           consts.shape[0], g_table.data_ptr(), int(timed), int(method), schedule.struct(),
-                                           bm._key, bm._elem0, None if entropy_dev is None else entropy_dev.data_ptr(),
-                                           dt_code, stream)
-    _native.check(rc, "tsde_trajectory_prog_additive")
-    if compiled is not None and specialise.verified(key) is None and not torch.cuda.is_current_stream_capturing():
-        other = torch.empty_like(ys)
-        specialise.launch_additive(compiled, other, y0, consts, g_table, m, timed, schedule, bm, stream)
-        specialise.set_verified(key, bool(((other == ys) | (other.isnan() & ys.isnan())).all()))
+    key, compiled = specialise.lookup(f_code, (), (), n_const, y0.dtype, method, y0.device, kind=kind)
+    _compiled_or_interpreted(key, compiled, interpret, run_compiled, [ys])
     return ys
 
 
@@ -938,6 +955,7 @@ class _ProgTrajectoryFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, programs, scalar_noise, method, schedule, bm, const_values, param_rows, y0, *params):
+        from . import specialise
         rows, d = y0.shape
         f_code, g_code, dg_code = programs
         y0c = _native.contiguous(y0.detach())
@@ -949,33 +967,27 @@ class _ProgTrajectoryFn(torch.autograd.Function):
             else:
                 table.append(torch.full((d,), float(c), dtype=y0.dtype, device=y0.device))
         consts = torch.stack(table).contiguous() if table else torch.zeros(1, d, dtype=y0.dtype, device=y0.device)
-        slots = (ctypes.c_int8 * max(len(const_values), 1))(*[(param_rows.index(k) + 1 if k in param_rows else -1)
-                                                              for k in range(len(const_values))])
+        n_const, scalar = len(const_values), int(bool(scalar_noise))
+        slots = (ctypes.c_int8 * max(n_const, 1))(*[(param_rows.index(k) + 1 if k in param_rows else -1) for k in range(n_const)])
         ys = torch.empty((schedule.n_out + 1, rows, d), dtype=y0.dtype, device=y0.device)
         sens = torch.empty((schedule.n_out, _native.TRAJ_SENS, rows, d), dtype=y0.dtype, device=y0.device)
         ys[0].copy_(y0c)
         words = tuple(f_code) + tuple(g_code) + tuple(dg_code)
         lib, dt_code, stream = _launch_env(y0c)
-        entropy_dev = bm._entropy_dev
-        # the same programs on dual numbers as straight-line code, compiled at run time and verified bit for bit on first use
-        from . import specialise
-        key, compiled = specialise.lookup(f_code, g_code, dg_code, len(const_values), y0.dtype, method, y0.device, kind="sens")
-        if compiled is not None and specialise.verified(key):
-            specialise.launch_sens(compiled, ys[1:], sens, slots, y0c, consts, len(const_values), scalar_noise, schedule, bm, stream)
-        else:
+
+        def interpret():
             code = (ctypes.c_uint32 * len(words))(*words)
             rc = lib.tsde_trajectory_prog_diag_sens(
                 ys[1:].data_ptr(), sens.data_ptr(), y0c.data_ptr(), rows, d, code, len(f_code), len(g_code), len(dg_code),
-                consts.data_ptr(), len(const_values), slots, int(bool(scalar_noise)), int(method), schedule.struct(), bm._key,
-                bm._elem0, None if entropy_dev is None else entropy_dev.data_ptr(), dt_code, stream)
+                consts.data_ptr(), n_const, slots, scalar, int(method), *_native.trajectory_tail(schedule, bm, dt_code, stream))
             _native.check(rc, "tsde_trajectory_prog_diag_sens")
-            if compiled is not None and specialise.verified(key) is None:
-                ys2, sens2 = torch.empty_like(ys[1:]), torch.empty_like(sens)
-                specialise.launch_sens(compiled, ys2, sens2, slots, y0c, consts, len(const_values), scalar_noise, schedule, bm,
-                                       stream)
-                same = (((ys2 == ys[1:]) | (ys2.isnan() & ys[1:].isnan())).all()
-                        & ((sens2 == sens) | (sens2.isnan() & sens.isnan())).all())
-                specialise.set_verified(key, bool(same))
+
+        def run_compiled(values, tangents):
+            specialise.launch(compiled, schedule, bm, stream, values.data_ptr(), tangents.data_ptr(),
+                              ctypes.cast(slots, ctypes.c_void_p), y0c.data_ptr(), rows, d, consts.data_ptr(), n_const, scalar)
+        # the same programs on dual numbers, interpreted or compiled at run time
+        key, compiled = specialise.lookup(f_code, g_code, dg_code, n_const, y0.dtype, method, y0.device, kind="sens")
+        _compiled_or_interpreted(key, compiled, interpret, run_compiled, [ys[1:], sens])
         ctx.save_for_backward(sens)
         ctx.param_shapes = [tuple(p.shape) for p in params]
         return ys
@@ -1020,12 +1032,10 @@ def trajectory_mlp_diag(ys, y0, w1, b1, w2, b2, diff_rate, diff_shift, activatio
     if w1.shape != (d, hidden) or w2.shape != (hidden, d) or b2.numel() != d or ys.shape != (schedule.n_out, rows, d):
         raise ValueError("shape mismatch: w1 (d, hidden), w2 (hidden, d), ys (n_out, rows, d)")
     lib, dt_code, stream = _launch_env(y0)
-    entropy_dev = bm._entropy_dev
     code = lib.tsde_trajectory_mlp_diag(
         ys.data_ptr(), y0.data_ptr(), rows, d, hidden, w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(),
         diff_rate.data_ptr(), diff_shift.data_ptr(), int(diffusion[0]), float(diffusion[1]), int(activation),
-        int(method), schedule.struct(), bm._key,
-        bm._elem0, None if entropy_dev is None else entropy_dev.data_ptr(), dt_code, stream)
+        int(method), *_native.trajectory_tail(schedule, bm, dt_code, stream))
     _native.check(code, "tsde_trajectory_mlp_diag")
     return ys
 
@@ -1075,11 +1085,9 @@ def trajectory_mlp_general(ys, y0, drift, diffusion, noise, m, method, schedule,
         if w1.shape != (d, net.hidden) or w2.shape != (net.hidden, net.out) or (w1t is not None and w1t.numel() != net.hidden):
             raise ValueError("shape mismatch: w1 (d, hidden), w1t (hidden), w2 (hidden, out)")
     lib, dt_code, stream = _launch_env(y0)
-    entropy_dev = bm._entropy_dev
     code = lib.tsde_trajectory_mlp_general(
         ys.data_ptr(), y0.data_ptr(), rows, d, int(m), int(noise), ctypes.byref(drift.struct()),
-        ctypes.byref(diffusion.struct()), int(method), schedule.struct(), bm._key, bm._elem0,
-        None if entropy_dev is None else entropy_dev.data_ptr(), dt_code, stream)
+        ctypes.byref(diffusion.struct()), int(method), *_native.trajectory_tail(schedule, bm, dt_code, stream))
     _native.check(code, "tsde_trajectory_mlp_general")
     return ys
 
@@ -1099,11 +1107,9 @@ def trajectory_mlp_additive(ys, y0, drift, g_table, m, method, schedule, bm):
     if tuple(g_table.shape) != ((schedule.n_steps, slots, m, d) if timed else (m, d)):
         raise ValueError(f"g_table must be (m, d) or (n_steps, {slots}, m, d), got {tuple(g_table.shape)}")
     lib, dt_code, stream = _launch_env(y0)
-    entropy_dev = bm._entropy_dev
     code = lib.tsde_trajectory_mlp_additive(
         ys.data_ptr(), y0.data_ptr(), rows, d, int(m), ctypes.byref(drift.struct()), g_table.data_ptr(), int(timed),
-        int(method), schedule.struct(), bm._key, bm._elem0, None if entropy_dev is None else entropy_dev.data_ptr(),
-        dt_code, stream)
+        int(method), *_native.trajectory_tail(schedule, bm, dt_code, stream))
     _native.check(code, "tsde_trajectory_mlp_additive")
     return ys
 
@@ -1295,8 +1301,7 @@ class _MlpTrajectoryFn(torch.autograd.Function):
                 row_shift.data_ptr(), ys.data_ptr(), ys_first, gys.data_ptr(), ctx.grad_step.data_ptr(), grad_last,
                 rows, d, hidden, w1_in.data_ptr(), b1c.data_ptr(), w2_in.data_ptr(), rate.data_ptr(), shift.data_ptr(),
                 ctx.diffusion[0], ctx.diffusion[1], ctx.activation, ctx.method, schedule.struct(), k_lo, k_hi, bm._key,
-                bm._elem0,
-                None if entropy_dev is None else entropy_dev.data_ptr(), dt_code, stream)
+                bm._elem0, None if entropy_dev is None else entropy_dev.data_ptr(), dt_code, stream)
             _native.check(code, "tsde_trajectory_mlp_diag_backward")
             flat_lam = stash_lam[:n].reshape(n * rows, d)
             flat_hid = stash_hid[:n].reshape(n * rows, hidden)

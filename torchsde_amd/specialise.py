@@ -4,7 +4,9 @@
 the kernel (csrc/trajectory.hip, `ProgModel`): a compare tree and register shuffles per instruction, ~3 000 cycles per
 wave-step where the hand-written affine kernel needs ~400. This module turns the SAME instruction words into straight-line HIP
 code -- a struct with the interpreter's interface, `f<SLOT>(x)`, `g<SLOT>(x)`, `gdg<SLOT>(x, g, v)` -- and instantiates the
-interpreter's own kernel (`trajectory_prog_kernel<T, METHOD, W, Model>`: same loop, same schemes, same generator) with it:
+interpreter's own kernel (`trajectory_prog_kernel<T, METHOD, W, Model>`: same loop, same schemes, same generator) with it,
+through the interpreter's own launch helpers (csrc/trajectory.hip `prog_args`, `launch_prog_m` ...: a unit is a model, `_model`,
+plus one entry point of a few lines, `_unit`):
 one operation of the user's code = one statement, in the order the interpreter would execute it, with the same functions and
 `-ffp-contract=off`, hence THE SAME BITS (checked on first use: the specialised launch must equal the interpreter's with
 `torch.equal`, or it is never used).
@@ -124,239 +126,101 @@ def _body(words, name, dual=False):
     return lines, stack[-1], used
 
 
+_P, _I64, _INT = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
+# family of a unit -> its one exported entry point: symbol, C parameters, their ctypes; every entry ends with _TAIL
+_TAIL = ("const tsde_traj_t* tr, uint64_t entropy, uint64_t elem0, const uint64_t* entropy_dev, void* stream",
+         [ctypes.POINTER(_native.Traj), ctypes.c_uint64, ctypes.c_uint64, _P, _P])
+_ENTRY = {
+    "values": ("tsde_specialised_launch",
+               "void* ys, const void* y0, int64_t rows, int64_t d, const void* consts, int n_const, int scalar_noise",
+               [_P, _P, _I64, _I64, _P, _INT, _INT]),
+    "sens": ("tsde_specialised_sens_launch",
+             "void* ys, void* sens, const int8_t* param_slot, const void* y0, int64_t rows, int64_t d, const void* consts, "
+             "int n_const, int scalar_noise", [_P, _P, _P, _P, _I64, _I64, _P, _INT, _INT]),
+    "additive": ("tsde_specialised_additive_launch",
+                 "void* ys, const void* y0, int64_t rows, int64_t d, int64_t m, const void* consts, int n_const, "
+                 "const void* gtab, int time_dependent", [_P, _P, _I64, _I64, _I64, _P, _INT, _P, _INT]),
+    "rows": ("tsde_specialised_rows_launch", "void* ys, const void* y0, int64_t rows, int64_t d, const void* consts, int n_const",
+             [_P, _P, _I64, _I64, _P, _INT]),
+}
+
+
+def _family(kind):
+    return kind.rstrip("0123456789")          # ("additive8": the additive family, channel-count class 8)
+
+
+def _unit(note, model, kind, dtype, method, refuse, scalar_noise, call):
+    """A translation unit: the kernels' source, the generated model, and the entry point of `kind` -- which refuses arguments
+    the model was not generated for (`refuse`) and hands everything else to the launch helpers of csrc/trajectory.hip."""
+    symbol, params, _ = _ENTRY[_family(kind)]
+    return f'''// generated by torchsde_amd/specialise.py{note} -- do not edit
+#define TSDE_SPECIALISE_TU 1
+#include "{os.path.join(_CSRC, "trajectory.hip")}"
+namespace tsde {{
+{model}}}  // namespace tsde
+
+extern "C" int {symbol}({params}, {_TAIL[0]}) {{
+  using namespace tsde;
+  using T = {"float" if dtype == torch.float32 else "double"};
+  constexpr int METHOD = {int(method)};
+  if ({refuse}) return (int)hipErrorInvalidValue;
+  const hipStream_t s = (hipStream_t)stream;
+  const ProgArgs<T> p = prog_args<T>(ys, y0, rows, d, consts, n_const, {scalar_noise}, tr, noise_key(entropy, elem0), entropy_dev);
+  return (int){call};
+}}
+'''
+
+
+def _model(struct, value, members, setup, bodies, v2):
+    """A generated model, with the interface of the interpreter's (csrc/trajectory.hip ProgModel, ProgSensModel). `struct`: its
+    template head and name; `value`: the alias of its value type (V, or S on dual numbers); `members`, `setup`: its constants
+    and how a lane loads them; `bodies`: of eval_f, eval_g and, where the derivative schemes run, eval_h; `v2`: the type of gdg's
+    last argument."""
+    V = value.split()[0]
+    evals = "".join(f"  TSDE_D {V} eval_{name}(const {V}& x, const T time) const {{\n{body}\n  }}\n" for name, body in bodies.items())
+    gdg = "(gv * v2) * eval_h(x, tslot[SLOT])" if "h" in bodies else f"{V}((T)0)"
+    return f'''{struct} {{
+  using {value};
+{members}  T tslot[4];
+{setup}{evals}  template <int SLOT>
+  TSDE_D {V} f(const {V}& x) const {{ return eval_f(x, tslot[SLOT]); }}
+  template <int SLOT>
+  TSDE_D {V} g(const {V}& x) const {{ return eval_g(x, tslot[SLOT]); }}
+  template <int SLOT>
+  TSDE_D {V} gdg(const {V}& x, const {V}& gv, {v2} v2) const {{ return {gdg}; }}
+}};
+'''
+
+
 def source(f_code, g_code, dg_code, n_const, dtype, method, kind="values"):
     """The translation unit for these programs, this state dtype and this scheme. `kind`: "values"
-    (`trajectory_prog_kernel`), or "sens" (`trajectory_prog_sens_kernel`: the programs on dual numbers)."""
-    if kind == "sens":
-        return _source_sens(f_code, g_code, dg_code, n_const, dtype, method)
-    additive = kind.startswith("additive")
-    ctype = "float" if dtype == torch.float32 else "double"
-    parts, used = {}, set()
+    (`trajectory_prog_kernel`), "sens" (`trajectory_prog_sens_kernel`: the programs on dual numbers), or "additive<MP>"
+    (`trajectory_prog_additive_kernel` for ONE channel-count class, the drift program alone)."""
+    dual = kind == "sens"
+    bodies, used = {}, set()
     for name, words in (("f", f_code), ("g", g_code), ("h", dg_code)):
-        lines, result, consts = _body(tuple(words), name)
-        parts[name] = (lines, result)
+        lines, result, consts = _body(tuple(words), name, dual)
+        bodies[name] = "\n".join(lines + [f"    return {result};"])
         used |= consts
     used = sorted(used)
-    members = "".join(f"  V c{k};\n" for k in used)
-    setup = "".join(
-        f"    {{ const Pack<T, W> pk = load<T, W>(p.consts, (int64_t){k} * p.d + column);\n"
-        f"      _Pragma(\"unroll\") for (int q = 0; q < W; ++q) c{k}.v[q] = pk.v[q]; }}\n" for k in used)
-
-    def fn(name):
-        lines, result = parts[name]
-        return "\n".join(lines) + ("\n" if lines else "") + f"    return {result};"
-    return f'''// generated by torchsde_amd/specialise.py -- do not edit
-#define TSDE_SPECIALISE_TU 1
-#include "{os.path.join(_CSRC, "trajectory.hip")}"
-namespace tsde {{
-template <typename T, int W>
-struct SpecModel {{
-  using V = Vec<T, W>;
-{members}  T tslot[4];
-  TSDE_D void setup(const ProgArgs<T>& p, int64_t column) {{
-{setup}  }}
-  TSDE_D V eval_f(const V& x, const T time) const {{
-{fn("f")}
-  }}
-  TSDE_D V eval_g(const V& x, const T time) const {{
-{fn("g")}
-  }}
-  TSDE_D V eval_h(const V& x, const T time) const {{
-{fn("h")}
-  }}
-  template <int SLOT>
-  TSDE_D V f(const V& x) const {{ return eval_f(x, tslot[SLOT]); }}
-  template <int SLOT>
-  TSDE_D V g(const V& x) const {{ return eval_g(x, tslot[SLOT]); }}
-  template <int SLOT>
-  TSDE_D V gdg(const V& x, const V& gv, const V& v2) const {{ return (gv * v2) * eval_h(x, tslot[SLOT]); }}
-}};
-}}  // namespace tsde
-
-{_additive_launcher(ctype, method, kind, used) if additive else ""}
-extern "C" int tsde_specialised_launch(void* ys, const void* y0, int64_t rows, int64_t d, const void* consts, int n_const,
-                                       int scalar_noise, const tsde_traj_t* tr, uint64_t entropy, uint64_t elem0,
-                                       const uint64_t* entropy_dev, void* stream) {{
-  using namespace tsde;
-  if ({1 if additive else 0}) return (int)hipErrorInvalidValue;        // (an additive-noise unit: tsde_specialised_additive_launch)
-  using T = {ctype};
-  constexpr int METHOD = {int(method)};
-  if (n_const < {(used[-1] + 1) if used else 0}) return (int)hipErrorInvalidValue;
-  ProgArgs<T> p;
-  p.ys = (T*)ys;
-  p.y0 = (const T*)y0;
-  p.consts = (const T*)consts;
-  p.f_len = p.g_len = p.dg_len = 0;
-  p.n_const = n_const;
-  p.scalar_noise = scalar_noise;
-  p.rows = (const T*)tr->step_rows;
-  p.cells = tr->cells;
-  p.out_step = tr->out_step;
-  p.out_w = (const T*)tr->out_w;
-  p.n = rows * d;
-  p.d = d;
-  p.n_steps = tr->n_steps;
-  p.n_out = tr->n_out;
-  p.key.k0 = (uint32_t)entropy;
-  p.key.k1 = (uint32_t)(entropy >> 32);
-  p.key.elem0 = elem0;
-  p.key_dev = entropy_dev;
-  for (int w = 0; w < kProgWords; ++w) p.code[w] = 0u;
-  if (p.n <= 0 || p.n_steps <= 0) return 0;
-  const hipStream_t s = (hipStream_t)stream;
-  const bool can_vec = (d % 4 == 0) && (scalar_noise || elem0 % 4 == 0) && aligned16(ys) && aligned16(y0) &&
-                       ((p.n * sizeof(T)) % 16 == 0);
-  const bool vec = can_vec && (p.n >> 2) >= kTrajVecMinGroups;
-  if (vec) {{
-    const int64_t lanes = p.n >> 2;
-    hipLaunchKernelGGL((trajectory_prog_kernel<T, METHOD, 4, SpecModel<T, 4>>), dim3((unsigned)((lanes + kBlock - 1) / kBlock)),
-                       dim3(kBlock), 0, s, p);
-  }} else {{
-    hipLaunchKernelGGL((trajectory_prog_kernel<T, METHOD, 1, SpecModel<T, 1>>), dim3((unsigned)((p.n + kBlock - 1) / kBlock)),
-                       dim3(kBlock), 0, s, p);
-  }}
-  return (int)hipGetLastError();
-}}
-'''
-
-
-def _additive_launcher(ctype, method, kind, used):
-    """The launcher of an additive-noise unit (kind "additive<MP>"): csrc/trajectory.hip launch_trajectory_prog_additive for ONE
-    scheme and ONE channel-count class, with the generated drift model."""
+    short = f"n_const < {(used[-1] + 1) if used else 0}"
+    if dual:
+        setup = "".join(f"    c{k} = S(q.base.consts[(int64_t){k} * q.base.d + column]);\n"
+                        f"    if (q.param_slot[{k}] > 0) c{k}.d[q.param_slot[{k}]] = (T)1;\n" for k in used)
+        model = _DUAL_HELPERS + _model("template <typename T>\nstruct SpecSensModel", "S = Dual<T>",
+                                       "".join(f"  S c{k};\n" for k in used),
+                                       f"  TSDE_D void setup(const ProgSensArgs<T>& q, int64_t column) {{\n{setup}  }}\n", bodies, "T")
+        return _unit("", model, kind, dtype, method, f"{short} || n_const > kProgParamRows", "scalar_noise",
+                     "launch_prog_sens_m<T, METHOD, SpecSensModel<T>>(prog_sens_args(p, sens, param_slot), s)")
+    setup = "".join(f"    {{ const Pack<T, W> pk = load<T, W>(p.consts, (int64_t){k} * p.d + column);\n"
+                    f"      _Pragma(\"unroll\") for (int q = 0; q < W; ++q) c{k}.v[q] = pk.v[q]; }}\n" for k in used)
+    model = _model("template <typename T, int W>\nstruct SpecModel", "V = Vec<T, W>", "".join(f"  V c{k};\n" for k in used),
+                   f"  TSDE_D void setup(const ProgArgs<T>& p, int64_t column) {{\n{setup}  }}\n", bodies, "const V&")
+    if kind == "values":
+        return _unit("", model, kind, dtype, method, short, "scalar_noise", "launch_prog_m<T, METHOD, SpecModel>(p, s)")
     mp = int(kind[len("additive"):])
-    return f'''
-extern "C" int tsde_specialised_additive_launch(void* ys, const void* y0, int64_t rows, int64_t d, int64_t m, const void* consts,
-                                                int n_const, const void* gtab, int time_dependent, const tsde_traj_t* tr,
-                                                uint64_t entropy, uint64_t elem0, const uint64_t* entropy_dev, void* stream) {{
-  using namespace tsde;
-  using T = {ctype};
-  constexpr int METHOD = {int(method)};
-  constexpr int MP = {mp};
-  if (n_const < {(used[-1] + 1) if used else 0} || m < 1 || m > MP) return (int)hipErrorInvalidValue;
-  ProgAdditiveArgs<T> q;
-  ProgArgs<T>& p = q.base;
-  p.ys = (T*)ys;
-  p.y0 = (const T*)y0;
-  for (int w = 0; w < kProgWords; ++w) p.code[w] = 0u;
-  p.consts = (const T*)consts;
-  p.f_len = p.g_len = p.dg_len = 0;
-  p.n_const = n_const;
-  p.scalar_noise = 0;
-  p.rows = (const T*)tr->step_rows;
-  p.cells = tr->cells;
-  p.out_step = tr->out_step;
-  p.out_w = (const T*)tr->out_w;
-  p.n = rows * d;
-  p.d = d;
-  p.n_steps = tr->n_steps;
-  p.n_out = tr->n_out;
-  p.key.k0 = (uint32_t)entropy;
-  p.key.k1 = (uint32_t)(entropy >> 32);
-  p.key.elem0 = elem0;
-  p.key_dev = entropy_dev;
-  if (p.n <= 0 || p.n_steps <= 0) return 0;
-  const int slots = METHOD == kEuler ? 1 : 2;
-  q.gtab = (const T*)gtab;
-  q.slot_stride = time_dependent ? m * d : 0;
-  q.step_stride = time_dependent ? (int64_t)slots * m * d : 0;
-  q.m = (int32_t)m;
-  q.quads = (m % 4 == 0 && elem0 % 4 == 0) ? 1 : 0;
-  const bool can_vec = (d % 4 == 0) && aligned16(ys) && aligned16(y0) && aligned16(gtab) && ((p.n * sizeof(T)) % 16 == 0);
-  const bool vec = can_vec && (p.n >> 2) >= kTrajVecMinGroups;
-  const hipStream_t s = (hipStream_t)stream;
-  if (vec) {{
-    hipLaunchKernelGGL((trajectory_prog_additive_kernel<T, METHOD, 4, MP, SpecModel<T, 4>>),
-                       dim3((unsigned)(((p.n >> 2) + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, q);
-  }} else {{
-    hipLaunchKernelGGL((trajectory_prog_additive_kernel<T, METHOD, 1, MP, SpecModel<T, 1>>),
-                       dim3((unsigned)((p.n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, q);
-  }}
-  return (int)hipGetLastError();
-}}
-'''
-
-
-def _source_sens(f_code, g_code, dg_code, n_const, dtype, method):
-    ctype = "float" if dtype == torch.float32 else "double"
-    parts, used = {}, set()
-    for name, words in (("f", f_code), ("g", g_code), ("h", dg_code)):
-        lines, result, consts = _body(tuple(words), name, dual=True)
-        parts[name] = (lines, result)
-        used |= consts
-    used = sorted(used)
-    members = "".join(f"  S c{k};\n" for k in used)
-    setup = "".join(
-        f"    c{k} = S(q.base.consts[(int64_t){k} * q.base.d + column]);\n"
-        f"    if (q.param_slot[{k}] > 0) c{k}.d[q.param_slot[{k}]] = (T)1;\n" for k in used)
-
-    def fn(name):
-        lines, result = parts[name]
-        return "\n".join(lines) + ("\n" if lines else "") + f"    return {result};"
-    return f'''// generated by torchsde_amd/specialise.py -- do not edit
-#define TSDE_SPECIALISE_TU 1
-#include "{os.path.join(_CSRC, "trajectory.hip")}"
-namespace tsde {{
-{_DUAL_HELPERS}
-template <typename T>
-struct SpecSensModel {{
-  using S = Dual<T>;
-{members}  T tslot[4];
-  TSDE_D void setup(const ProgSensArgs<T>& q, int64_t column) {{
-{setup}  }}
-  TSDE_D S eval_f(const S& x, const T time) const {{
-{fn("f")}
-  }}
-  TSDE_D S eval_g(const S& x, const T time) const {{
-{fn("g")}
-  }}
-  TSDE_D S eval_h(const S& x, const T time) const {{
-{fn("h")}
-  }}
-  template <int SLOT>
-  TSDE_D S f(const S& x) const {{ return eval_f(x, tslot[SLOT]); }}
-  template <int SLOT>
-  TSDE_D S g(const S& x) const {{ return eval_g(x, tslot[SLOT]); }}
-  template <int SLOT>
-  TSDE_D S gdg(const S& x, const S& gv, T v2) const {{ return (gv * v2) * eval_h(x, tslot[SLOT]); }}
-}};
-}}  // namespace tsde
-
-extern "C" int tsde_specialised_sens_launch(void* ys, void* sens, const int8_t* param_slot, const void* y0, int64_t rows,
-                                            int64_t d, const void* consts, int n_const, int scalar_noise, const tsde_traj_t* tr,
-                                            uint64_t entropy, uint64_t elem0, const uint64_t* entropy_dev, void* stream) {{
-  using namespace tsde;
-  using T = {ctype};
-  constexpr int METHOD = {int(method)};
-  if (n_const < {(used[-1] + 1) if used else 0} || n_const > kProgParamRows) return (int)hipErrorInvalidValue;
-  ProgSensArgs<T> q;
-  ProgArgs<T>& p = q.base;
-  p.ys = (T*)ys;
-  p.y0 = (const T*)y0;
-  p.consts = (const T*)consts;
-  p.f_len = p.g_len = p.dg_len = 0;
-  p.n_const = n_const;
-  p.scalar_noise = scalar_noise;
-  p.rows = (const T*)tr->step_rows;
-  p.cells = tr->cells;
-  p.out_step = tr->out_step;
-  p.out_w = (const T*)tr->out_w;
-  p.n = rows * d;
-  p.d = d;
-  p.n_steps = tr->n_steps;
-  p.n_out = tr->n_out;
-  p.key.k0 = (uint32_t)entropy;
-  p.key.k1 = (uint32_t)(entropy >> 32);
-  p.key.elem0 = elem0;
-  p.key_dev = entropy_dev;
-  for (int w = 0; w < kProgWords; ++w) p.code[w] = 0u;
-  q.sens = (T*)sens;
-  for (int k = 0; k < kProgParamRows; ++k) q.param_slot[k] = (param_slot && k < n_const) ? param_slot[k] : (int8_t)-1;
-  if (p.n <= 0 || p.n_steps <= 0) return 0;
-  hipLaunchKernelGGL((trajectory_prog_sens_kernel<T, METHOD, SpecSensModel<T>>), dim3((unsigned)((p.n + kBlock - 1) / kBlock)),
-                     dim3(kBlock), 0, (hipStream_t)stream, q);
-  return (int)hipGetLastError();
-}}
-'''
+    return _unit("", model, kind, dtype, method, f"{short} || m < 1 || m > {mp}", "0",
+                 f"launch_additive_mp<T, METHOD, {mp}, SpecModel>(prog_additive_args(p, m, gtab, time_dependent, METHOD), s)")
 
 
 # ---- compiling, caching, loading -------------------------------------------------------------------------------------------
@@ -366,28 +230,13 @@ _verified = {}         # key -> True | False (the specialised launch reproduced 
 
 
 class _Library:
-    def __init__(self, path):
+    def __init__(self, path, kind):
         self.path = path
         self.lib = ctypes.CDLL(path)
-        tail = [ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_native.Traj),
-                ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
-        if hasattr(self.lib, "tsde_specialised_rows_launch"):
-            fn = self.lib.tsde_specialised_rows_launch
-            fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int,
-                           ctypes.POINTER(_native.Traj), ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
-        elif hasattr(self.lib, "tsde_specialised_additive_launch"):
-            fn = self.lib.tsde_specialised_additive_launch
-            fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
-                           ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(_native.Traj), ctypes.c_uint64,
-                           ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
-        elif hasattr(self.lib, "tsde_specialised_sens_launch"):
-            fn = self.lib.tsde_specialised_sens_launch
-            fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p] + tail
-        else:
-            fn = self.lib.tsde_specialised_launch
-            fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p] + tail
-        fn.restype = ctypes.c_int
-        self.launch = fn
+        symbol, _, argtypes = _ENTRY[_family(kind)]
+        self.launch = getattr(self.lib, symbol)
+        self.launch.argtypes = argtypes + _TAIL[1]
+        self.launch.restype = ctypes.c_int
 
 
 def cache_dir():
@@ -417,7 +266,11 @@ def _arch(device):
         return "gfx950"
 
 
-def _compile(key, text, arch):
+def _compile_command(arch, out, src):
+    return [compiler(), "-O3", "-std=c++17", "-fPIC", f"--offload-arch={arch}", "-ffp-contract=off", "-shared", "-o", out, src]
+
+
+def _compile(key, text, arch, kind="values"):
     try:
         path = os.path.join(cache_dir(), f"{key}.so")
         if not os.path.exists(path):
@@ -425,25 +278,24 @@ def _compile(key, text, arch):
             with open(src, "w") as fh:
                 fh.write(text)
             tmp = f"{path}.{os.getpid()}.{threading.get_ident()}.tmp"
-            cmd = [compiler(), "-O3", "-std=c++17", "-fPIC", f"--offload-arch={arch}", "-ffp-contract=off", "-shared", "-o", tmp, src]
-            done = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+            done = subprocess.run(_compile_command(arch, tmp, src), capture_output=True, text=True, timeout=600)
             if done.returncode != 0:
                 raise RuntimeError(done.stderr[-2000:])
             os.replace(tmp, path)                 # (atomic: another process may be compiling the same key)
-        result = _Library(path)
+        result = _Library(path, kind)
     except Exception as e:       # no compiler, a compile error, a load error: the interpreter stays
         result = f"failed: {type(e).__name__}: {e}"
     with _lock:
         _state[key] = result
 
 
-def lookup(f_code, g_code, dg_code, n_const, dtype, method, device, wait=None, kind="values"):
-    """(key, the loaded library of these programs or None). The first call starts the compilation (in the background unless
-    TSDE_SPECIALISE=sync or `wait`)."""
+def _find(make_text, kind, device, wait):
+    """(key, the loaded library of the unit `make_text()` or None). The first call starts the compilation (in the background
+    unless TSDE_SPECIALISE=sync or `wait`)."""
     if MODE in ("0", "false", "off") or compiler() is None:
         return None, None
     arch = _arch(device)
-    text = source(f_code, g_code, dg_code, n_const, dtype, method, kind)
+    text = make_text()
     key = hashlib.sha256((text + arch + _sources_digest()).encode()).hexdigest()[:24]
     with _lock:
         have = _state.get(key)
@@ -451,8 +303,8 @@ def lookup(f_code, g_code, dg_code, n_const, dtype, method, device, wait=None, k
             _state[key] = "pending"
     if have is None:
         if MODE == "sync" or wait:
-            _compile(key, text, arch)
-        elif not _enqueue(key, text, arch):
+            _compile(key, text, arch, kind)
+        elif not _enqueue(key, text, arch, kind):
             with _lock:
                 _state.pop(key, None)            # (the queue is full: ask again at a later solve)
         with _lock:
@@ -460,11 +312,16 @@ def lookup(f_code, g_code, dg_code, n_const, dtype, method, device, wait=None, k
     return key, (have if isinstance(have, _Library) else None)
 
 
+def lookup(f_code, g_code, dg_code, n_const, dtype, method, device, wait=None, kind="values"):
+    """(key, library or None) of these programs (`_find`)."""
+    return _find(lambda: source(f_code, g_code, dg_code, n_const, dtype, method, kind), kind, device, wait)
+
+
 # one worker, a short queue: a process that meets hundreds of different programs (a test-suite) compiles a few at a time
 _queue = None
 
 
-def _enqueue(key, text, arch):
+def _enqueue(*job):
     global _queue
     import queue
     with _lock:
@@ -473,11 +330,10 @@ def _enqueue(key, text, arch):
 
             def work():
                 while True:
-                    job = _queue.get()
-                    _compile(*job)
+                    _compile(*_queue.get())
             threading.Thread(target=work, daemon=True, name="torchsde_amd-specialise").start()
     try:
-        _queue.put_nowait((key, text, arch))
+        _queue.put_nowait(job)
         return True
     except queue.Full:
         return False
@@ -507,19 +363,6 @@ def status():
         return {k: (v.path if isinstance(v, _Library) else v) for k, v in _state.items()}
 
 
-def launch(library, ys, y0, consts, scalar_noise, schedule, bm, stream):
-    rows, d = y0.shape
-    entropy_dev = bm._entropy_dev
-    lib = _native.load()
-    slot = lib.tsde_prof_bracket_open(_native.KID_TRAJECTORY, stream)       # (bench.py's per-launch timing of this kernel family)
-    rc = library.launch(ys.data_ptr(), y0.data_ptr(), rows, d, consts.data_ptr(), consts.shape[0], int(bool(scalar_noise)),
-                        schedule.struct(), bm._key, bm._elem0, None if entropy_dev is None else entropy_dev.data_ptr(), stream)
-    if slot >= 0:
-        lib.tsde_prof_bracket_close(slot, stream)
-    if rc != 0:
-        raise _native.NativeLibraryError(f"torchsde_amd: a specialised program kernel failed with hipError {rc}")
-
-
 def verified(key):
     return _verified.get(key)
 
@@ -528,28 +371,12 @@ def set_verified(key, ok):
     _verified[key] = bool(ok)
 
 
-def launch_sens(library, ys, sens, slots, y0, consts, n_const, scalar_noise, schedule, bm, stream):
-    rows, d = y0.shape
-    entropy_dev = bm._entropy_dev
+def launch(library, schedule, bm, stream, *args):
+    """One launch of a compiled unit: `args` are its entry point's own arguments (`_ENTRY`), the schedule, the noise key and the
+    stream follow."""
     lib = _native.load()
-    slot = lib.tsde_prof_bracket_open(_native.KID_TRAJECTORY, stream)
-    rc = library.launch(ys.data_ptr(), sens.data_ptr(), ctypes.cast(slots, ctypes.c_void_p), y0.data_ptr(), rows, d,
-                        consts.data_ptr(), int(n_const), int(bool(scalar_noise)), schedule.struct(), bm._key, bm._elem0,
-                        None if entropy_dev is None else entropy_dev.data_ptr(), stream)
-    if slot >= 0:
-        lib.tsde_prof_bracket_close(slot, stream)
-    if rc != 0:
-        raise _native.NativeLibraryError(f"torchsde_amd: a specialised program kernel failed with hipError {rc}")
-
-
-def launch_additive(library, ys, y0, consts, g_table, m, timed, schedule, bm, stream):
-    rows, d = y0.shape
-    entropy_dev = bm._entropy_dev
-    lib = _native.load()
-    slot = lib.tsde_prof_bracket_open(_native.KID_TRAJECTORY, stream)
-    rc = library.launch(ys.data_ptr(), y0.data_ptr(), rows, d, int(m), consts.data_ptr(), consts.shape[0], g_table.data_ptr(),
-                        int(bool(timed)), schedule.struct(), bm._key, bm._elem0,
-                        None if entropy_dev is None else entropy_dev.data_ptr(), stream)
+    slot = lib.tsde_prof_bracket_open(_native.KID_TRAJECTORY, stream)       # (bench.py's per-launch timing of this kernel family)
+    rc = library.launch(*args, *_native.trajectory_tail(schedule, bm, stream))
     if slot >= 0:
         lib.tsde_prof_bracket_close(slot, stream)
     if rc != 0:
@@ -567,9 +394,9 @@ _ROW_OPS = {
 
 
 def source_rows(structure, n_const, dtype, method):
-    """The translation unit of a row-coupled system: `structure` = RecognisedRows.structure()."""
+    """The translation unit of a row-coupled system: `structure` = RecognisedRows.structure(). (No derivative schemes on this
+    route: the model has no eval_h.)"""
     (_, d, statements, outputs), _ = structure
-    ctype = "float" if dtype == torch.float32 else "double"
     names = [f"n{k}" for k in range(len(statements))]
     needs = {}
     for name, (op, operands) in zip(names, statements):
@@ -590,98 +417,16 @@ def source_rows(structure, n_const, dtype, method):
         lines.append("    return r;")
         return "\n".join(lines)
     nc = max(1, n_const)
-    return f'''// generated by torchsde_amd/specialise.py (a row-coupled system) -- do not edit
-#define TSDE_SPECIALISE_TU 1
-#include "{os.path.join(_CSRC, "trajectory.hip")}"
-namespace tsde {{
-template <typename T>
-struct RowModel {{
-  using V = Vec<T, {d}>;
-  T c[{nc}];
-  T tslot[4];
-  TSDE_D void setup(const ProgArgs<T>& p, int64_t) {{
+    setup = f"""  TSDE_D void setup(const ProgArgs<T>& p, int64_t) {{
     _Pragma("unroll") for (int k = 0; k < {nc}; ++k) c[k] = k < p.n_const ? p.consts[k] : (T)0;
   }}
-  TSDE_D V eval_f(const V& x, const T time) const {{
-{body(list(outputs[:d]))}
-  }}
-  TSDE_D V eval_g(const V& x, const T time) const {{
-{body(list(outputs[d:]))}
-  }}
-  template <int SLOT>
-  TSDE_D V f(const V& x) const {{ return eval_f(x, tslot[SLOT]); }}
-  template <int SLOT>
-  TSDE_D V g(const V& x) const {{ return eval_g(x, tslot[SLOT]); }}
-  template <int SLOT>
-  TSDE_D V gdg(const V& x, const V& gv, const V& v2) const {{ return V((T)0); }}        // (no derivative schemes on this route)
-}};
-}}  // namespace tsde
-
-extern "C" int tsde_specialised_rows_launch(void* ys, const void* y0, int64_t rows, int64_t d, const void* consts, int n_const,
-                                            const tsde_traj_t* tr, uint64_t entropy, uint64_t elem0,
-                                            const uint64_t* entropy_dev, void* stream) {{
-  using namespace tsde;
-  using T = {ctype};
-  constexpr int METHOD = {int(method)};
-  if (d != {d} || n_const > {nc}) return (int)hipErrorInvalidValue;
-  ProgArgs<T> p;
-  p.ys = (T*)ys;
-  p.y0 = (const T*)y0;
-  p.consts = (const T*)consts;
-  p.f_len = p.g_len = p.dg_len = 0;
-  p.n_const = n_const;
-  p.scalar_noise = 0;
-  p.rows = (const T*)tr->step_rows;
-  p.cells = tr->cells;
-  p.out_step = tr->out_step;
-  p.out_w = (const T*)tr->out_w;
-  p.n = rows * d;
-  p.d = d;
-  p.n_steps = tr->n_steps;
-  p.n_out = tr->n_out;
-  p.key.k0 = (uint32_t)entropy;
-  p.key.k1 = (uint32_t)(entropy >> 32);
-  p.key.elem0 = elem0;
-  p.key_dev = entropy_dev;
-  for (int w = 0; w < kProgWords; ++w) p.code[w] = 0u;
-  if (p.n <= 0 || p.n_steps <= 0) return 0;
-  hipLaunchKernelGGL((trajectory_prog_kernel<T, METHOD, {d}, RowModel<T>>), dim3((unsigned)((rows + kBlock - 1) / kBlock)),
-                     dim3(kBlock), 0, (hipStream_t)stream, p);
-  return (int)hipGetLastError();
-}}
-'''
+"""
+    model = _model("template <typename T>\nstruct RowModel", f"V = Vec<T, {d}>", f"  T c[{nc}];\n", setup,
+                   {"f": body(list(outputs[:d])), "g": body(list(outputs[d:]))}, "const V&")
+    return _unit(" (a row-coupled system)", model, "rows", dtype, method, f"d != {d} || n_const > {nc}", "0",
+                 f"launch_prog_w<T, METHOD, {d}, RowModel<T>>(p, s)")
 
 
 def lookup_rows(structure, n_const, dtype, method, device, wait=None):
-    """(key, library or None) of a row-coupled system; starts the compilation on first sight (cf. `lookup`)."""
-    if MODE in ("0", "false", "off") or compiler() is None:
-        return None, None
-    arch = _arch(device)
-    text = source_rows(structure, n_const, dtype, method)
-    key = hashlib.sha256((text + arch + _sources_digest()).encode()).hexdigest()[:24]
-    with _lock:
-        have = _state.get(key)
-        if have is None:
-            _state[key] = "pending"
-    if have is None:
-        if MODE == "sync" or wait:
-            _compile(key, text, arch)
-        elif not _enqueue(key, text, arch):
-            with _lock:
-                _state.pop(key, None)
-        with _lock:
-            have = _state.get(key)
-    return key, (have if isinstance(have, _Library) else None)
-
-
-def launch_rows(library, ys, y0, consts, schedule, bm, stream):
-    rows, d = y0.shape
-    entropy_dev = bm._entropy_dev
-    lib = _native.load()
-    slot = lib.tsde_prof_bracket_open(_native.KID_TRAJECTORY, stream)
-    rc = library.launch(ys.data_ptr(), y0.data_ptr(), rows, d, consts.data_ptr(), consts.numel(), schedule.struct(), bm._key,
-                        bm._elem0, None if entropy_dev is None else entropy_dev.data_ptr(), stream)
-    if slot >= 0:
-        lib.tsde_prof_bracket_close(slot, stream)
-    if rc != 0:
-        raise _native.NativeLibraryError(f"torchsde_amd: a specialised row kernel failed with hipError {rc}")
+    """(key, library or None) of a row-coupled system (`_find`)."""
+    return _find(lambda: source_rows(structure, n_const, dtype, method), "rows", device, wait)

@@ -356,6 +356,8 @@ int tsde_brownian_query_dev(void* W, void* U, void* H, int64_t n, uint64_t entro
 #define TSDE_TRAJ_HEUN 5       /* heun.py:35-48; the affine / expression / program kernels (values and sensitivities) */
 #define TSDE_TRAJ_EULER_HEUN 6 /* euler_heun.py:29-42; the same kernels */
 #define TSDE_TRAJ_REVERSIBLE_HEUN 7 /* reversible_heun.py:48-73; tsde_rheun_mlp_forward only */
+#define TSDE_TRAJ_MILSTEIN_ITO_GF 8   /* derivative-free Milstein, milstein.py:58-67; tsde_trajectory_mlp_general only */
+#define TSDE_TRAJ_MILSTEIN_STRAT_GF 9 /* the same for Stratonovich SDEs; tsde_trajectory_mlp_general only */
 
 /* All `traj->n_steps` fixed steps of a diagonal-noise SDE with per-channel affine drift and diffusion
  *   f(t, y) = drift_rate * y + drift_shift,   g(t, y) = diff_rate * y + diff_shift      (each of length d)
@@ -527,7 +529,19 @@ typedef struct tsde_mlp {
  * method: TSDE_TRAJ_EULER (Ito), TSDE_TRAJ_MIDPOINT (Stratonovich; stage times t_k and t_k + dt/2), or -- diagonal and scalar
  * noise only, like the reference's (srk.py:34-35) -- TSDE_TRAJ_SRK (SRID2, srk.py:57-88: three drift and four diffusion
  * evaluations per step, every one a pass of its net; needs the increments' second stream, i.e. a Brownian motion with a
- * space-time Levy area).
+ * space-time Levy area), or -- diagonal and scalar noise only, like the reference's (milstein.py:25) -- Milstein
+ * (milstein.py:52-74), one stage time t_k like Euler, six layer passes per step against Euler's four:
+ *   TSDE_TRAJ_MILSTEIN_ITO / _STRAT        the derivative form: y1 = ((y + f dt) + g W) + gdg with v = W^2 - dt (Ito) or W^2
+ *                                          (milstein.py:54-57) and gdg = (dg/dy)^T (g v/2), the vector-Jacobian product of
+ *                                          base_sde.py:127-155 -- here the diffusion net walked backwards: two transposed
+ *                                          products from the same LDS copy of its weights, no autograd;
+ *   TSDE_TRAJ_MILSTEIN_ITO_GF / _STRAT_GF  the derivative-free form (milstein.py:58-67, `options={"grad_free": True}`):
+ *                                          gdg = (g(t, y') - g(t, y)) v / (2 sqrt(dt)) at y' = y + (f dt if Ito) + g sqrt(dt),
+ *                                          a second pass of the diffusion net.
+ * General noise with any Milstein code is refused (the reference has no such scheme; the opt-in general-noise Milstein of
+ * csrc/milstein_general.hip stays a stepwise route). step_rows[k][3] must hold sqrt(dt) for the derivative-free form.
+ * The Milstein codes have not been timed on an MI355X yet (the estimate of 1.5x the Euler kernel's time is unmeasured):
+ * `sdeint` sends a solve here under Milstein only with options={"neural_milstein_kernel": True}, off by default.
  * A wave keeps 16 rows in registers for the whole solve; every weight lives in LDS; all four layers run on
  * v_mfma_f32_16x16x4_f32 (exact f32), the contraction with the increments included (csrc/mlp_general.hip).
  * traj->step_rows[k][7] must hold t_k, the time at which step k starts (the other trajectory kernels ignore that slot).

@@ -716,10 +716,14 @@ int tsde_trajectory_mlp_general(void* ys, const void* y0, int64_t rows, int64_t 
   if (((reinterpret_cast<uintptr_t>(y0) | reinterpret_cast<uintptr_t>(ys)) & (d % 4 == 0 ? 15u : 3u)) != 0)
     return bad_arg(where, "ys and y0 must be 16-byte aligned (4-byte when d is not a multiple of 4)");
   if (rows * d >= (int64_t(1) << 30)) return bad_arg(where, "need rows * d < 2^30 (32-bit lane offsets)");
-  if (method != TSDE_TRAJ_EULER && method != TSDE_TRAJ_MIDPOINT && method != TSDE_TRAJ_SRK)
-    return bad_arg(where, "method must be Euler, midpoint or SRK");
+  const bool milstein = method == TSDE_TRAJ_MILSTEIN_ITO || method == TSDE_TRAJ_MILSTEIN_STRAT ||
+                        method == TSDE_TRAJ_MILSTEIN_ITO_GF || method == TSDE_TRAJ_MILSTEIN_STRAT_GF;
+  if (method != TSDE_TRAJ_EULER && method != TSDE_TRAJ_MIDPOINT && method != TSDE_TRAJ_SRK && !milstein)
+    return bad_arg(where, "method must be Euler, midpoint, SRK or Milstein (derivative or derivative-free form)");
   if (method == TSDE_TRAJ_SRK && noise == TSDE_NOISE_GENERAL)
     return bad_arg(where, "SRK (SRID2) takes diagonal or scalar noise, like the reference's (srk.py:34-35)");
+  if (milstein && noise == TSDE_NOISE_GENERAL)
+    return bad_arg(where, "Milstein takes diagonal or scalar noise, like the reference's (milstein.py:25)");
   if (const char* bad = schedule_problem(traj)) return bad_arg(where, bad);
   const hipStream_t s = (hipStream_t)stream;
   ProfScope p(TSDE_KID_TRAJECTORY, s);

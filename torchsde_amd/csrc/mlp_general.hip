@@ -17,6 +17,9 @@
 //   methods/euler.py:29-37 (f_and_g_prod -> misc.batch_mvp, _core/misc.py:62-63: bmm(g, dW))     TSDE_TRAJ_EULER
 //   methods/midpoint.py:29-45 (two evaluations, the second at t + dt/2 and the predicted state)   TSDE_TRAJ_MIDPOINT
 //   methods/srk.py:57-88 (SRID2, diagonal / scalar noise: 3 drift + 4 diffusion evaluations)       TSDE_TRAJ_SRK
+//   methods/milstein.py:52-74 (diagonal / scalar noise: the derivative form, whose vector-Jacobian
+//     product base_sde.py:127-155 is the diffusion net walked backwards, and the derivative-free
+//     form, a second pass of the net at y + f dt + g sqrt(dt))                                    TSDE_TRAJ_MILSTEIN_*[_GF]
 // in ONE launch. Stepwise, this SDE costs a (rows, d, m) diffusion tensor through HBM and four library GEMMs per step
 // (the user's two nets are 93 % of the solve at the configs[2] shape); here nothing but y0 and the outputs touches HBM.
 //
@@ -62,7 +65,8 @@ struct NeuralArgs {
   int64_t B;
   int32_t d, m;
   int32_t n_steps, n_out;
-  int32_t method;           // TSDE_TRAJ_EULER | TSDE_TRAJ_MIDPOINT | TSDE_TRAJ_SRK (diagonal / scalar noise)
+  int32_t method;           // TSDE_TRAJ_EULER | TSDE_TRAJ_MIDPOINT | TSDE_TRAJ_SRK | TSDE_TRAJ_MILSTEIN_* (the last two: diagonal /
+                            // scalar noise)
   NoiseKey key;
   const uint64_t* key_dev;
   const float* gtab;        // additive noise: (m, d) or (n_steps, slots, m, d), the diffusion matrix transposed
@@ -142,7 +146,9 @@ struct PairLayout {
 // GENERIC (diagonal noise only): the state width is not a multiple of 4 or the field is unaligned, so the increments are
 // drawn element by element; a separate instantiation, so that the common one carries no call and no second path (the SRK
 // body keeps ~300 registers live across the draws).
-template <int D, int H, int MODE, bool SPLIT = false, bool GENERIC = false>
+// MILSTEIN (diagonal and scalar noise): the four Milstein codes, an instantiation of their own -- the step body of every other
+// scheme is compiled without them and is the code it was before they existed.
+template <int D, int H, int MODE, bool SPLIT = false, bool GENERIC = false, bool MILSTEIN = false>
 __global__ void __launch_bounds__(256, (MODE >= 4 || (H <= 64 && !GENERIC)) ? 2 : 1) neural_trajectory_kernel(const NeuralArgs p, const int outp) {
   // (up to 64 hidden units the compiler is asked for at most 256 registers: it then keeps the accumulators in ordinary
   //  registers -- with the 512 of one wave per SIMD it parks them in the accumulation file and every tile pays eight copies
@@ -151,6 +157,7 @@ __global__ void __launch_bounds__(256, (MODE >= 4 || (H <= 64 && !GENERIC)) ? 2 
   //  instantiation, which would spill ~100 registers.)
   using NS = NoiseShape<MODE>;
   static_assert(!SPLIT || (NS::kGeneral && H == 64), "split mode: general noise, 64 hidden units");
+  static_assert(!MILSTEIN || MODE <= 1, "Milstein: diagonal or scalar noise");
   using L = NeuralLds<D, H>;
   using PL = PairLayout<D, MODE, SPLIT>;
   static_assert(!PL::kOn || NS::G == 2, "pairs of tiles");
@@ -237,6 +244,8 @@ __global__ void __launch_bounds__(256, (MODE >= 4 || (H <= 64 && !GENERIC)) ? 2 
     key.k1 = (uint32_t)(ent >> 32);
   }
   const bool midpoint = p.method == TSDE_TRAJ_MIDPOINT;
+  const bool milstein_ito = p.method == TSDE_TRAJ_MILSTEIN_ITO || p.method == TSDE_TRAJ_MILSTEIN_ITO_GF;
+  const bool grad_free = p.method == TSDE_TRAJ_MILSTEIN_ITO_GF || p.method == TSDE_TRAJ_MILSTEIN_STRAT_GF;
   const float g_scale = p.g.scale;
   const bool sigmoid_out = p.g.final == TSDE_FINAL_SIGMOID;
   const int64_t n_groups = (p.B + 15) / 16;
@@ -640,6 +649,132 @@ __global__ void __launch_bounds__(256, (MODE >= 4 || (H <= 64 && !GENERIC)) ? 2 
       }
     };
 
+    // ---- Milstein, diagonal / scalar noise (the MILSTEIN instantiations; milstein.py:52-74) --------------------------------
+    // the step's increments W alone, in the state's layout (`increments` without the second stream)
+    auto increments_w = [&](uint32_t cell, float sw, f32x4* w) {
+      if constexpr (MODE == 1) {
+        const float wr = normal1<float>(key, key.elem0 + (uint64_t)row, cell, 0, kStreamW) * sw;
+#pragma unroll
+        for (int t = 0; t < TD; ++t) w[t] = f32x4{wr, wr, wr, wr};
+      } else {
+#pragma unroll
+        for (int t = 0; t < TD; ++t) {
+          const int ch = 16 * t + 4 * part;
+          uint64_t quad = (key.elem0 + (uint64_t)off_d + (uint64_t)ch) >> 2;
+          asm volatile("" : "+v"(quad));
+          float zw[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+          if constexpr (noise_quads) {
+            if (real(ch)) normal4<float>(key, quad, cell, 0, kStreamW, zw);
+          } else {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              if (ch + r < dT) zw[r] = draw_one(key, key.elem0 + (uint64_t)off_d + (uint64_t)(ch + r), cell, kStreamW);
+            }
+          }
+#pragma unroll
+          for (int r = 0; r < 4; ++r) w[t][r] = zw[r] * sw;
+        }
+      }
+    };
+    // `hidden_layer` of the diffusion net that also keeps act'(pre-activation) for the way back: 1 - tanh^2, or for softplus
+    // the sigmoid of the pre-activation from the activation's own exponential, e^x / (1 + e^x) (exact where e^x is small;
+    // torch's backward returns 1 past the threshold)
+    auto diffusion_hidden_with_slope = [&](float time, const f32x4* x, f32x4* hid, f32x4* slope) {
+#pragma unroll
+      for (int th = 0; th < TH; ++th) hid[th] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int t = 0; t < TD; ++t) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+#pragma unroll
+          for (int th = 0; th < TH; ++th) {
+            const float a = W1g[(16 * t + 4 * part + r) * S1 + 16 * th + n];
+            hid[th] = Tile<16>::mfma(a, x[t][r], hid[th]);
+          }
+        }
+      }
+      reads_ahead<TD * 4 * TH / 2, 2>();
+      auto finish = [&](auto kind) {
+        constexpr int ACT = decltype(kind)::value;
+#pragma unroll
+        for (int th = 0; th < TH; ++th) {
+          const f32x4 bias = lds_quad(b1g, 16 * th + 4 * part), wt = lds_quad(wtg, 16 * th + 4 * part);
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float pre = hid[th][r] + (bias[r] + wt[r] * time);
+            const float v = activate<ACT>(pre);
+            hid[th][r] = v;
+            if constexpr (ACT == TSDE_ACT_TANH) {
+              slope[th][r] = 1.0f - v * v;
+            } else {
+              const float ex = __builtin_amdgcn_exp2f(pre * 1.4426950408889634f);
+              slope[th][r] = pre > 20.0f ? 1.0f : ex * __builtin_amdgcn_rcpf(1.0f + ex);
+            }
+          }
+        }
+      };
+      if (p.g.act == TSDE_ACT_TANH) finish(std::integral_constant<int, TSDE_ACT_TANH>{});
+      else finish(std::integral_constant<int, TSDE_ACT_SOFTPLUS>{});
+    };
+    // `diffusion_values` that also returns dg/dz2, the derivative of a value by the net's own output: scale * s (1 - s) with a
+    // closing sigmoid s, scale without
+    auto diffusion_values_with_slope = [&](const f32x4* hid, f32x4* g, f32x4* dg) {
+#pragma unroll
+      for (int t = 0; t < TD; ++t) g[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int th = 0; th < TH; ++th) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+#pragma unroll
+          for (int t = 0; t < TD; ++t) {
+            const float a = W2g[(16 * th + 4 * part + r) * S2G + 16 * t + n];
+            g[t] = Tile<16>::mfma(a, hid[th][r], g[t]);
+          }
+        }
+      }
+      if constexpr (TD == 1) reads_ahead<TH * 4, 1>();
+      else reads_ahead<TH * 4 * TD / 2, 2>();
+#pragma unroll
+      for (int t = 0; t < TD; ++t) {
+        const f32x4 bias = lds_quad(b2g, 16 * t + 4 * part);
+        if (sigmoid_out) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float s = finalise<true>(g[t][r] + bias[r]);
+            g[t][r] = g_scale * s;
+            dg[t][r] = (g_scale * s) * (1.0f - s);
+          }
+        } else {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            g[t][r] = g_scale * (g[t][r] + bias[r]);
+            dg[t][r] = g_scale;
+          }
+        }
+      }
+    };
+    // cin^T (tin tiles) = W cout^T for W [in][out] with row stride `stride`: the TRANSPOSED product from the forward copy of the
+    // weights. Lane (part, n) supplies A[n][part] = W[16 ti + n][16 to + 4 part + r], r = 0..3: four consecutive floats, one
+    // 16-byte read per four matrix instructions (csrc/tsde_neural_rheun.h product_t). Output tiles at or past `out_staged`
+    // columns are skipped: nothing is staged there (for 33 <= d <= 48 the state has four tiles and W2g three), and the
+    // cotangents of such channels are zero by construction.
+    auto product_t = [&](const float* W, int stride, const f32x4* cout, int tout, int out_staged, f32x4* cin, int tin) {
+#pragma unroll
+      for (int ti = 0; ti < tin; ++ti) cin[ti] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+      for (int to = 0; to < tout; ++to) {
+        if (16 * to >= out_staged) continue;
+#pragma unroll
+        for (int ti = 0; ti < tin; ++ti) {
+          const f32x4 a = *reinterpret_cast<const f32x4*>(W + (16 * ti + n) * stride + 16 * to + 4 * part);
+#pragma unroll
+          for (int r = 0; r < 4; ++r) cin[ti] = Tile<16>::mfma(a[r], cout[to][r], cin[ti]);
+        }
+      }
+    };
+
     // additive noise: (G w)^T in the state's layout, D[i][n] = sum_j G[i][j] w[n][j] on the matrix cores -- lane (part, n)
     // supplies A[i = n][k = part] = G[16 t + n][4 kk + part] (read from the table: a few KB, cache-resident) and
     // B[k = part][n] = the weight of ITS batch row for Brownian channel j = 4 kk + part, drawn by the lane itself
@@ -739,7 +874,77 @@ __global__ void __launch_bounds__(256, (MODE >= 4 || (H <= 64 && !GENERIC)) ? 2 
         }
         stepped = true;
       }
-      if constexpr (MODE <= 1) {
+      if constexpr (MILSTEIN) {
+        // Milstein for diagonal / scalar noise with BOTH functions networks (milstein.py:52-74), in the stepwise route's
+        // operation order (tsde_schemes.h; csrc/steps.hip MilsteinGfPrimeOp / MilsteinGfDiagOp for the derivative-free form):
+        // six layer passes per step against Euler's four, on the same LDS copy of the weights
+        // (channels the state does not have stay exactly zero through the step: their diffusion values come from reads past the
+        //  staged rows of W2g / b2g and must reach neither the supporting state y' nor the next step's products)
+        const float sqrt_dt = srow[3];
+        f32x4 w[TD], g0[TD], corr[TD];
+        auto has = [&](int t, int r) { return 16 * t + 4 * part + r < dT; };
+        increments_w(cell, sw, w);
+        hidden_layer(W1f, b1f, wtf, p.f.act, t0, y, hid);
+        drift(hid, f);
+        if (grad_free) {
+          // g' = g(t, y') at y' = y + (dt f if Ito) + g sqrt(dt); gdg = (g' - g) v / (2 sqrt(dt))         (milstein.py:58-67)
+          f32x4 yp[TD];
+          hidden_layer(W1g, b1g, wtg, p.g.act, t0, y, hid);
+          diffusion_values(hid, g0);
+#pragma unroll
+          for (int t = 0; t < TD; ++t) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              g0[t][r] = has(t, r) ? g0[t][r] : 0.0f;
+              yp[t][r] = (y[t][r] + (milstein_ito ? dt * f[t][r] : 0.0f)) + g0[t][r] * sqrt_dt;
+            }
+          }
+          hidden_layer(W1g, b1g, wtg, p.g.act, t0, yp, hid);
+          diffusion_values(hid, corr);
+          const float two_sqrt_dt = 2.0f * sqrt_dt;
+#pragma unroll
+          for (int t = 0; t < TD; ++t) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const float sq = w[t][r] * w[t][r];
+              const float v = milstein_ito ? sq - dt : sq;
+              corr[t][r] = ((corr[t][r] - g0[t][r]) * v) / two_sqrt_dt;
+            }
+          }
+        } else {
+          // gdg = (dg/dy)^T (g v/2) (base_sde.py:127-155), the diffusion net walked backwards: c2 = (g v/2) dg/dz2 at its
+          // output, c1 = act'(.) W2g c2 at the hidden layer, gdg = W1g c1 (state rows only: t is no input of the product).
+          // c2 is exactly zero for channels the state does not have (they are contraction indices here), and so is c1 for
+          // hidden units the net does not have (their rows of W2g are staged as zeros).
+          f32x4 slope[TH], c1[TH], c2[TD];
+          diffusion_hidden_with_slope(t0, y, hid, slope);
+          diffusion_values_with_slope(hid, g0, c2);
+#pragma unroll
+          for (int t = 0; t < TD; ++t) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const float v2 = milstein_v<float>(w[t][r], dt, 0.5f, milstein_ito ? 1 : 0);
+              c2[t][r] = has(t, r) ? (g0[t][r] * v2) * c2[t][r] : 0.0f;
+            }
+          }
+          product_t(W2g, S2G, c2, TD, outp, c1, TH);
+#pragma unroll
+          for (int th = 0; th < TH; ++th) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) c1[th][r] *= slope[th][r];
+          }
+          product_t(W1g, S1, c1, TH, H, corr, TD);
+        }
+#pragma unroll
+        for (int t = 0; t < TD; ++t) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            yn[t][r] = has(t, r) ? milstein_update<float>(y[t][r], f[t][r], g0[t][r], corr[t][r], w[t][r], dt) : 0.0f;
+          }
+        }
+        stepped = true;
+      }
+      if constexpr (MODE <= 1 && !MILSTEIN) {
         if (p.method == TSDE_TRAJ_SRK) {
           // SRID2 (srk.py:57-88, tableaus/srid2.py) for diagonal / scalar noise with BOTH functions networks: three drift
           // evaluations f(t, y), f(t + dt, H0_1), f(t + dt/2, H0_2) (the tableau's alpha_3 = 0) and four diffusion
@@ -820,7 +1025,7 @@ __global__ void __launch_bounds__(256, (MODE >= 4 || (H <= 64 && !GENERIC)) ? 2 
           stepped = true;
         }
       }
-      if constexpr (!NS::kTable) {
+      if constexpr (!NS::kTable && !MILSTEIN) {
       if (!stepped) {
       hidden_layer(W1f, b1f, wtf, p.f.act, t0, y, hid);
       drift(hid, f);
@@ -891,7 +1096,7 @@ static size_t neural_lds_limit() {
   return limit;
 }
 
-template <int D, int H, int MODE, bool SPLIT = false, bool GENERIC = false>
+template <int D, int H, int MODE, bool SPLIT = false, bool GENERIC = false, bool MILSTEIN = false>
 static hipError_t launch_neural_mode(const NeuralArgs& p, hipStream_t s) {
   if constexpr (!SPLIT && NoiseShape<MODE>::kGeneral && H == 64) {
     if (p.split) return launch_neural_mode<D, H, MODE, true>(p, s);
@@ -904,7 +1109,7 @@ static hipError_t launch_neural_mode(const NeuralArgs& p, hipStream_t s) {
   if (lds_bytes > neural_lds_limit()) return hipErrorInvalidValue;
   static bool configured = false;   // per instantiation
   if (!configured) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&neural_trajectory_kernel<D, H, MODE, SPLIT, GENERIC>),
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&neural_trajectory_kernel<D, H, MODE, SPLIT, GENERIC, MILSTEIN>),
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
     if (e != hipSuccess) return e;
     configured = true;
@@ -915,18 +1120,26 @@ static hipError_t launch_neural_mode(const NeuralArgs& p, hipStream_t s) {
   const int64_t per_cu = (int64_t)((160 * 1024) / lds_bytes) < 1 ? 1 : (int64_t)((160 * 1024) / lds_bytes);
   const int64_t resident = 256 * (per_cu > 8 ? 8 : per_cu);
   if (blocks > resident) blocks = resident;
-  hipLaunchKernelGGL((neural_trajectory_kernel<D, H, MODE, SPLIT, GENERIC>), dim3((unsigned)blocks), dim3(256), lds_bytes, s, p,
+  hipLaunchKernelGGL((neural_trajectory_kernel<D, H, MODE, SPLIT, GENERIC, MILSTEIN>), dim3((unsigned)blocks), dim3(256), lds_bytes, s, p,
                      outp);
   return hipGetLastError();
 }
 
 template <int D, int H>
 static hipError_t launch_neural_dh(const NeuralArgs& p, int noise, hipStream_t s) {
+  const bool milstein = p.method == TSDE_TRAJ_MILSTEIN_ITO || p.method == TSDE_TRAJ_MILSTEIN_STRAT ||
+                        p.method == TSDE_TRAJ_MILSTEIN_ITO_GF || p.method == TSDE_TRAJ_MILSTEIN_STRAT_GF;
   if (noise == TSDE_NOISE_DIAGONAL) {
     const bool quads = (p.d % 4 == 0) && (p.key.elem0 % 4 == 0);
+    if (milstein) {
+      return quads ? launch_neural_mode<D, H, 0, false, false, true>(p, s) : launch_neural_mode<D, H, 0, false, true, true>(p, s);
+    }
     return quads ? launch_neural_mode<D, H, 0, false, false>(p, s) : launch_neural_mode<D, H, 0, false, true>(p, s);
   }
-  if (noise == TSDE_NOISE_SCALAR) return launch_neural_mode<D, H, 1>(p, s);
+  if (noise == TSDE_NOISE_SCALAR) {
+    return milstein ? launch_neural_mode<D, H, 1, false, false, true>(p, s) : launch_neural_mode<D, H, 1>(p, s);
+  }
+  if (milstein) return hipErrorInvalidValue;      // (general and additive noise: no Milstein in this kernel)
   if (noise == TSDE_NOISE_ADDITIVE) return launch_neural_mode<D, H, 2>(p, s);
   if constexpr (H <= 64) {      // (general noise: H x d*m weights of the diffusion's second layer; 128 units do not fit the LDS)
     // (m real Brownian channels run in the next tile width up; the padding is zero weights and zero increments)

@@ -519,8 +519,10 @@ class BaseSDESolver:
             if (code not in (_native.TRAJ_EULER, _native.TRAJ_MILSTEIN_ITO, _native.TRAJ_MILSTEIN_STRAT,
                              _native.TRAJ_MIDPOINT, _native.TRAJ_SRK) or bm._elem0 % 4 != 0 or y0.numel() >= 2 ** 30):
                 return None
-        key = ledger.key(found, y0, *(("bf16x3",) if spec[0] == "neural" and spec[2].precision != _native.PRECISION_F32
-                                      else ()))
+        tags = ("bf16x3",) if spec[0] == "neural" and spec[2].precision != _native.PRECISION_F32 else ()
+        if spec[0] == "neural" and self._neural_code() in (_native.TRAJ_MILSTEIN_ITO_GF, _native.TRAJ_MILSTEIN_STRAT_GF):
+            tags += ("grad_free",)       # (the derivative-free form is another kernel path: it earns its own trust)
+        key = ledger.key(found, y0, *tags)
         verdict, reverify = ledger.verdict(key)
         launch = spec                                                      # (what `_integrate_trajectory` takes)
         if spec[0] == "affine_diagonal":
@@ -578,6 +580,8 @@ class BaseSDESolver:
         close = ((fast - stepwise).abs() <= atol + rtol * stepwise.abs()) | both_nan | (fast == stepwise)
         ledger.file(key, True if bool(close.all()) else "the trajectory kernel did not reproduce the stepwise solve",
                     reverify, counter_rate)
+        if spec[0] == "neural":
+            ledger.name_kernel(key, "tsde_trajectory_mlp_general")
         return stepwise
 
     def _interpret(self, ledger, y0, ts, kinds, precision):
@@ -1299,6 +1303,21 @@ class _Milstein(BaseSDESolver):
     def _program_code(self):
         if self.options[METHOD_OPTIONS.grad_free]:
             return None
+        return _native.TRAJ_MILSTEIN_ITO if self.ito else _native.TRAJ_MILSTEIN_STRAT
+
+    def _neural_code(self):
+        # drift and diffusion two-layer networks, diagonal or scalar noise: both forms in the neural-SDE kernel (the
+        # derivative form walks the diffusion net backwards, the derivative-free one evaluates it a second time). General
+        # noise (the opt-in extension of `_advance_general`) stays stepwise.
+        if self.sde.noise_type not in (NOISE_TYPES.diagonal, NOISE_TYPES.scalar):
+            return None
+        # OPT-IN (`options={"neural_milstein_kernel": True}`), off by default: the condition for routing these solves to the kernel
+        # is a measured gain over the stepwise solve on an MI355X, and no such timing has been taken yet (DESIGN.md section 4,
+        # "Milstein on the neural-SDE kernel"). Without the option such solves stay stepwise.
+        if not self.options.get("neural_milstein_kernel", False):
+            return None
+        if self.options[METHOD_OPTIONS.grad_free]:
+            return _native.TRAJ_MILSTEIN_ITO_GF if self.ito else _native.TRAJ_MILSTEIN_STRAT_GF
         return _native.TRAJ_MILSTEIN_ITO if self.ito else _native.TRAJ_MILSTEIN_STRAT
 
     def _additive_code(self):

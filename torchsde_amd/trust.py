@@ -160,6 +160,7 @@ class Ledger:
             trusted.clear()
             self.book.get("counter_rate", {}).clear()
             self.book.get("solves", {}).clear()
+            self.book.get("kernel", {}).clear()
         trusted[key] = verdict
         if reverify and verdict is not True:
             # TSDE_VERIFY_EVERY: a form that had earned trust and no longer reproduces the stepwise solve is a loud failure
@@ -168,6 +169,10 @@ class Ledger:
                                "options={'trajectory_kernel': False} keeps the stepwise path.")
         if counter_rate:
             self.book.setdefault("counter_rate", {})[key] = counter_rate
+
+    def name_kernel(self, key, name):
+        """The C entry point a form's solves launch, for `describe`."""
+        self.book.setdefault("kernel", {})[key] = name
 
     def counter_rate(self, key):
         """{call counter: advance per step} learnt by the verifying solve of `key`, or None."""
@@ -204,7 +209,9 @@ def describe(sde):
                 else f"f: {structure[0][0]}, g: {structure[1][0]}")
         timed = any("table" in part for part in structure if isinstance(part, tuple))
         route = ("trajectory kernel" + (" with per-stage-time coefficient rows" if timed else "")
-                 + (" (sensitivity kernel: autograd)" if key[7:] == ("autograd",) else ""))
+                 + (" (sensitivity kernel: autograd)" if key[7:] == ("autograd",) else "")
+                 + (f" ({book['kernel'][key]})" if key in book.get("kernel", {}) else "")
+                 + (" (derivative-free Milstein)" if "grad_free" in key[7:] else ""))
         lines.append(f"[{solver}, {sde_type}, batch = {batch}, d = {d}, {dtype}] {kind}: "
                      + (route if verdict is True else f"stays stepwise: {verdict}"))
     for (_, _, solver), reason in book["refused"].items():

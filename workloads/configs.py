@@ -184,6 +184,32 @@ WORKLOADS = {
         problem="netdiag_big", method="srk", levy="space-time", B=65536, d=64, m=64, nsteps=1000, dt=2.0 ** -10,
         bytes_per_traj_step=64 * 64, bytes_moved_per_traj_step=92 * 64, kid=4, launches_per_step=4, bench_steps=200,
         kernel="tsde_srk_diag_stage<float> (4 stage kernels; user f_net, g_net: 7 evaluations per step)"),
+    # The same module under Milstein (milstein.py:52-74; the reference's default adjoint_method for diagonal Ito noise), derivative
+    # form: f, g and the vector-Jacobian product through g_net -- six layer passes per step -- in one launch; stepwise
+    # counterpart below (two user net calls and an autograd VJP per step)
+    "c2_milstein_netdiag_default_route_b65536_d64_s1000": dict(
+        problem="netdiag_big", method="milstein", levy="none", B=65536, d=64, m=64, nsteps=1000, dt=2.0 ** -10,
+        kid=8, trajectory=True, recognised=True, mfma_flops_per_traj_step=6 * 2 * 64 * 64,
+        options={"neural_milstein_kernel": True},        # (the route is off by default: DESIGN.md section 4)
+        stepwise="c2_milstein_netdiag_b65536_d64_s1000",
+        kernel="tsde_trajectory_mlp_general<64, 64, diagonal, milstein> (neural_trajectory_kernel; user module recognised)"),
+    "c2_milstein_netdiag_b65536_d64_s1000": dict(
+        problem="netdiag_big", method="milstein", levy="none", B=65536, d=64, m=64, nsteps=1000, dt=2.0 ** -10,
+        bytes_per_traj_step=20 * 64, kid=3, launches_per_step=1, bench_steps=200, kernel_match=["MilsteinDiagOp<float>"],
+        kernel="tsde_milstein_diag<float> (user f_net, g_net and autograd's VJP through g_net per step)"),
+    # ... and its derivative-free form (milstein.py:58-67, options={"grad_free": True}): a second pass of g_net instead of the VJP
+    "c2_milstein_gradfree_netdiag_default_route_b65536_d64_s1000": dict(
+        problem="netdiag_big", method="milstein", levy="none", B=65536, d=64, m=64, nsteps=1000, dt=2.0 ** -10,
+        kid=8, trajectory=True, recognised=True, options={"grad_free": True, "neural_milstein_kernel": True},
+        mfma_flops_per_traj_step=6 * 2 * 64 * 64,
+        stepwise="c2_milstein_gradfree_netdiag_b65536_d64_s1000",
+        kernel="tsde_trajectory_mlp_general<64, 64, diagonal, milstein derivative-free> (neural_trajectory_kernel; user module "
+               "recognised)"),
+    "c2_milstein_gradfree_netdiag_b65536_d64_s1000": dict(
+        problem="netdiag_big", method="milstein", levy="none", B=65536, d=64, m=64, nsteps=1000, dt=2.0 ** -10,
+        bytes_per_traj_step=20 * 64, kid=3, launches_per_step=1, bench_steps=200, options={"grad_free": True},
+        kernel_match=["MilsteinGfDiagOp<float>"],
+        kernel="tsde_milstein_gf_diag<float> (user f_net and two g_net calls per step, tsde_milstein_gf_prime between them)"),
     # The batch-broadcast diffusion of north_star's "MFMA ... for the dense g.dW batched matmul": additive noise returned
     # as sigma.expand(B, d, m) at the configs[2] shape and at a larger one. One launch of the matrix-core kernel per
     # step: reads y0, f, writes y1 (12*d bytes per trajectory-step), increments generated in registers, S in LDS.

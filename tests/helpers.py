@@ -150,6 +150,103 @@ def counter_rows_bm(rows, m, entropy, edges, dtype, levy=False):
     return bm
 
 
+# ---- the reversible-Heun pair over output-time grids (test_rheun_grids.py, test_gpu_neural_rheun*.py) -------------------------
+RHEUN_DT = 2.0 ** -5
+# Output times in units of RHEUN_DT. Every one is a multiple of DT / 4, so float32 and float64 hold the same grid (a time that
+# float32 rounds, 3.4 DT say, gives the two oracle runs different steps and their difference stops measuring rounding).
+RHEUN_GRIDS = {
+    "aligned": (0, 5, 16),                            # the grid that earns trust
+    "inside": (0, 3.5, 16),                           # one interpolated output
+    "crowded": (0, 3.25, 3.5, 3.75, 4, 16),           # three outputs inside one step and one on its right boundary
+    "first_step": (0, 0.5, 16),                       # interpolation against y0 (out_step = 1)
+    "ragged": (0, 5, 15.25),                          # a short last step
+    "one_short_step": (0, 0.75),                      # K = 1
+    "every_step": tuple(range(9)),                    # consecutive out_step
+}
+
+
+def rheun_modules():
+    """name -> (factory of the module on the CPU, d, m): the sde_gan generator at depth 2 and the reference's Neural* problems."""
+    from workloads import problems
+    return {"sde_gan_2": (lambda: problems.SdeGanGenerator(3, 16, 16, 2, seed=2), 16, 3),
+            "neural_diagonal": (lambda: problems.make("netdiag_strat", d=12, hidden=16), 12, 12),
+            "neural_scalar": (lambda: problems.make("netscalar_strat", d=6, hidden=8), 6, 1)}
+
+
+def rheun_ts(name):
+    return [u * RHEUN_DT for u in RHEUN_GRIDS[name]]
+
+
+def rheun_grid(ts_list, dt=RHEUN_DT):
+    """The solver's own grid of `ts_list` (timegrid.TimeGrid): step boundaries, and per output (k_prev, k_curr, w0, w1)."""
+    from torchsde_amd import timegrid
+    return timegrid.build(np.asarray(ts_list, dtype=np.float64), dt)
+
+
+def rheun_inside(ts_list, dt=RHEUN_DT):
+    """Per entry of `ts_list`: is that output interpolated inside a step (ys[0] never is)?"""
+    return [False] + [not (w0 == 0.0 and w1 == 1.0) for (_, _, w0, w1) in rheun_grid(ts_list, dt).outputs]
+
+
+def rheun_snapped(ts_list, dt=RHEUN_DT):
+    """`ts_list` with every interpolated output moved to its step's right boundary: what a gradient that ignores the
+    interpolation weights differentiates. Same steps, same Brownian cells."""
+    grid = rheun_grid(ts_list, dt)
+    return [ts_list[0]] + [float(grid.t[k_curr]) for (_, k_curr, _, _) in grid.outputs]
+
+
+def rheun_cotangents(ts_list, B, d, seed, dt=RHEUN_DT):
+    """[(label, (len(ts), B, d) float32 CPU tensor)]: a random cotangent on all outputs and, where the grid has an output
+    inside a step, the same one masked to those outputs. The second is what makes a misplaced cotangent visible: among
+    sixteen steps' worth of gradient from the boundary outputs it moves dL/dy0 by a few parts in a thousand only."""
+    gen = torch.Generator().manual_seed(seed)
+    w = torch.randn(len(ts_list), B, d, generator=gen)
+    inside = rheun_inside(ts_list, dt)
+    out = [("all", w)]
+    if any(inside):
+        out.append(("inside", w * torch.tensor(inside, dtype=w.dtype).reshape(-1, 1, 1)))
+    return out
+
+
+def grid_oracle(sde, m, ts_list, rows, entropy, y0, cotangents, dt=RHEUN_DT, adjoint=False, method="reversible_heun",
+                adjoint_method=None):
+    """The oracle's reversible-Heun solve of a copy of `sde` on the counter path of global batch rows `rows`, in float32
+    and in float64: ``{dtype: (ys, {label: [dL/dy0, dL/dtheta...]})}`` for L = sum(ys * cotangent), by back-propagation
+    through oracle/solvers_ref.integrate_reversible_heun -- or, `adjoint`, by the reference's own backward pass
+    (oracle/adjoint_ref.reversible_heun_adjoint_gradients, which steps to every output time). `y0`: (len(rows), d).
+    Another `method`: oracle/solvers_ref.integrate, and adjoint_ref.adjoint_gradients with `adjoint_method`."""
+    import copy
+    from oracle import adjoint_ref, solvers_ref
+    edges = rheun_grid(ts_list, dt).t_f64()
+    out = {}
+    for dtype in (torch.float32, torch.float64):
+        ref_sde = copy.deepcopy(sde).cpu().to(dtype)
+        params = [p for p in ref_sde.parameters() if p.requires_grad]
+        bm = counter_rows_bm(np.asarray(rows), m, entropy, edges, dtype)
+        ts = torch.tensor(ts_list, dtype=dtype)
+        grads = {}
+        if adjoint:
+            for label, w in cotangents:
+                if method == "reversible_heun":
+                    ys, gy, gp = adjoint_ref.reversible_heun_adjoint_gradients(ref_sde, y0.detach().cpu().to(dtype), ts, bm,
+                                                                               dt, w.to(dtype))
+                else:
+                    ys, gy, gp = adjoint_ref.adjoint_gradients(ref_sde, y0.detach().cpu().to(dtype), ts, bm, dt, method,
+                                                               adjoint_method, w.to(dtype))
+                grads[label] = [gy] + list(gp)
+        else:
+            y0_ref = y0.detach().cpu().to(dtype).requires_grad_(True)
+            if method == "reversible_heun":
+                ys, _ = solvers_ref.integrate_reversible_heun(ref_sde, bm, y0_ref, ts, dt)
+            else:
+                ys = solvers_ref.integrate(ref_sde, bm, y0_ref, ts, dt, method)
+            for label, w in cotangents:
+                got = torch.autograd.grad((ys * w.to(dtype)).sum(), [y0_ref] + params, retain_graph=True, allow_unused=True)
+                grads[label] = [torch.zeros_like(x) if g is None else g for g, x in zip(got, [y0_ref] + params)]
+        out[dtype] = (ys.detach(), grads)
+    return out
+
+
 def assert_within_reference_rounding(new32, ref32, ref64, what="", factor=4.0, floor=1e-6):
     """the float32 HIP result may differ from the float64 oracle by at most `factor` times what
     the oracle's own float32 run differs from it, plus `floor` (scaled by the magnitude of the compared quantity)."""

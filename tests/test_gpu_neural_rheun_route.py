@@ -104,6 +104,10 @@ def _grads(sde, out, y0, weights):
 
 
 def _same(got, want, rtol):
+    # (2e-3 of the largest entry, for a cotangent over all outputs, cannot be relied on to see a misplaced cotangent: moving an
+    #  interpolated output's cotangent to its step's boundary changes dL/dy0 by 4-7e-3 of its largest entry, which sits next to
+    #  this tolerance. The cases that see it: test_autograd_through_sdeint_over_output_grids and tests/test_rheun_grids.py, with
+    #  a cotangent on the interpolated outputs alone and the oracle's rounding as the yardstick.)
     for i, (a, b) in enumerate(zip(got, want)):
         scale = b.abs().max().item() + 1e-12
         err = (a - b).abs().max().item()
@@ -305,3 +309,181 @@ def test_euler_on_an_ito_deep_network():
     with torch.no_grad():
         out, launches = _launches(lambda: torchsde_amd.sdeint(sde, y0, ts, bm=_bm(48, 3, 16 * DT, 2), dt=DT))
     assert launches == 1
+
+
+# ---- gradients over output-time grids ------------------------------------------------------------------------------------------
+# Trust is keyed by form, scheme, width, dtype and batch size -- not by the time grid: whatever the kernels do with the output map
+# (an output inside a step, several in one step, a short last step) is verified only on the grid of the first solve. These cases
+# earn the trust on `aligned` and then solve every grid of helpers.RHEUN_GRIDS, against the oracle on the same Brownian path, with
+# a cotangent on all outputs and one on the interpolated outputs alone (tests/test_rheun_grids.py: why the second).
+GRID_MODULES = ["sde_gan_2", "neural_diagonal", "neural_scalar"]
+GRID_B, GRID_ENTROPY = 24, 7
+
+
+def _trusted_on_aligned(name, adjoint=False):
+    make, d, m = MODULES[name]
+    sde = make()
+    aligned = helpers.rheun_ts("aligned")
+    if adjoint:
+        _adjoint(sde, d, m, 1, B=GRID_B, ts=aligned)
+        ys, _ = _adjoint(sde, d, m, 2, B=GRID_B, ts=aligned)
+    else:
+        _sdeint(sde, d, m, 1, B=GRID_B, ts=aligned)
+        _sdeint(sde, d, m, 1, B=GRID_B, ts=aligned, grad=True)
+        ys, _ = _sdeint(sde, d, m, 2, B=GRID_B, ts=aligned, grad=True)
+    assert type(ys.grad_fn).__name__ == "ReversibleHeunFnBackward", _book(sde)
+    assert all(v is True for v in _book(sde)["trusted"].values()) and not _book(sde)["refused"], _book(sde)
+    return sde, d, m
+
+
+def _against_the_oracle(sde, m, ts_list, ys, y0, what, adjoint=False, method="reversible_heun", adjoint_method=None, factor=6.0,
+                        floor=2e-6):
+    """Values, dL/dy0 and every parameter gradient of `ys` (with its graph) for both cotangents of the grid, against the oracle's
+    float32 and float64 runs on the same rows of the same Brownian path."""
+    B, d = y0.shape
+    cotangents = helpers.rheun_cotangents(ts_list, B, d, seed=17)
+    refs = helpers.grid_oracle(sde, m, ts_list, range(B), GRID_ENTROPY, y0, cotangents, adjoint=adjoint, method=method,
+                               adjoint_method=adjoint_method)
+    params = list(sde.parameters())
+    failures = []
+    for k, (label, w) in enumerate(cotangents):
+        got = torch.autograd.grad((ys * w.to(DEV)).sum(), [y0] + params, retain_graph=k + 1 < len(cotangents), allow_unused=True)
+        got = [torch.zeros_like(x) if g is None else g for g, x in zip(got, [y0] + params)]
+        new = [ys.detach()] + got
+        r32 = [refs[torch.float32][0]] + refs[torch.float32][1][label]
+        r64 = [refs[torch.float64][0]] + refs[torch.float64][1][label]
+        assert len(new) == len(r32) == len(r64)
+        for i, (a, b32, b64) in enumerate(zip(new, r32, r64)):
+            scale = max(1.0, b64.abs().max().item())
+            err_new = (a.double().cpu() - b64).abs().max().item()
+            err_ref = (b32.double() - b64).abs().max().item()
+            print(f"{what} [{label}] quantity {i}: |new - ref64| {err_new:.3e}  |ref32 - ref64| {err_ref:.3e}  scale {scale:.3e}"
+                  f"  ratio to the allowance {err_new / (factor * err_ref + floor * scale):.2f}")
+            try:
+                helpers.assert_within_reference_rounding(a, b32, b64, f"{what} [{label}] quantity {i}", factor=factor,
+                                                         floor=floor)
+            except AssertionError as e:
+                failures.append(str(e))
+    assert not failures, "\n".join(failures)
+
+
+@pytest.mark.parametrize("grid", sorted(helpers.RHEUN_GRIDS))
+@pytest.mark.parametrize("name", GRID_MODULES)
+def test_autograd_through_sdeint_over_output_grids(name, grid):
+    """`sdeint(method="reversible_heun")` under autograd. The kernels' sweep takes exactly the grids whose outputs all sit on step
+    boundaries (it does not split an interpolated output's cotangent); there the no-grad solve is one launch, so no case passes by
+    quietly staying stepwise."""
+    sde, d, m = _trusted_on_aligned(name)
+    ts_list = helpers.rheun_ts(grid)
+    on_boundaries = not any(helpers.rheun_inside(ts_list))
+    assert on_boundaries == (grid in ("aligned", "ragged", "one_short_step", "every_step"))
+    ys, y0 = _sdeint(sde, d, m, GRID_ENTROPY, B=GRID_B, ts=ts_list, grad=True)
+    assert (type(ys.grad_fn).__name__ == "ReversibleHeunFnBackward") == on_boundaries, type(ys.grad_fn).__name__
+    if on_boundaries:
+        fast, launches = _launches(lambda: _sdeint(sde, d, m, GRID_ENTROPY, B=GRID_B, ts=ts_list))
+        assert launches == 1
+        assert torch.equal(fast, ys.detach())
+    _against_the_oracle(sde, m, ts_list, ys, y0, f"sdeint {name} {grid}")
+    assert all(v is True for v in _book(sde)["trusted"].values()) and not _book(sde)["refused"], _book(sde)
+
+
+@pytest.mark.parametrize("grid", sorted(helpers.RHEUN_GRIDS))
+@pytest.mark.parametrize("name", GRID_MODULES)
+def test_sdeint_adjoint_with_the_pair_over_output_grids(name, grid):
+    """`sdeint_adjoint` with the reversible pair against the oracle's restatement of the reference's backward pass, which steps to
+    every output time (adjoint.py:97-112): whichever route a grid takes. An output time inside a step warns and stays stepwise."""
+    import contextlib
+    sde, d, m = _trusted_on_aligned(name, adjoint=True)
+    ts_list = helpers.rheun_ts(grid)
+    off_grid = any(helpers.rheun_inside(ts_list))
+    with pytest.warns(UserWarning) if off_grid else contextlib.nullcontext():
+        ys, y0 = _adjoint(sde, d, m, GRID_ENTROPY, B=GRID_B, ts=ts_list)
+    if off_grid:
+        assert type(ys.grad_fn).__name__ != "ReversibleHeunFnBackward"
+    _against_the_oracle(sde, m, ts_list, ys, y0, f"sdeint_adjoint {name} {grid}", adjoint=True)
+    assert all(v is True for v in _book(sde)["trusted"].values()) and not _book(sde)["refused"], _book(sde)
+
+
+def test_an_off_grid_first_solve_files_no_verdict():
+    """On a fresh object, an output inside a step under autograd first: the solve stays stepwise and nothing is filed (the check
+    comes before the ledger), so the form can still earn its trust on a grid the kernels differentiate."""
+    make, d, m = MODULES["sde_gan_2"]
+    sde = make()
+    ys, _ = _sdeint(sde, d, m, 1, B=GRID_B, ts=helpers.rheun_ts("inside"), grad=True)
+    assert type(ys.grad_fn).__name__ != "ReversibleHeunFnBackward"
+    assert not _book(sde)["trusted"] and not _book(sde)["refused"], _book(sde)
+    aligned = helpers.rheun_ts("aligned")
+    ys, _ = _sdeint(sde, d, m, 2, B=GRID_B, ts=aligned, grad=True)                  # the verifying solve
+    assert type(ys.grad_fn).__name__ != "ReversibleHeunFnBackward"
+    assert list(_book(sde)["trusted"].values()) == [True] and not _book(sde)["refused"], _book(sde)
+    ys, _ = _sdeint(sde, d, m, 3, B=GRID_B, ts=aligned, grad=True)
+    assert type(ys.grad_fn).__name__ == "ReversibleHeunFnBackward"
+    assert list(_book(sde)["trusted"].values()) == [True] and not _book(sde)["refused"], _book(sde)
+
+
+@pytest.mark.parametrize("name", GRID_MODULES)
+def test_sdeint_adjoint_with_a_stock_brownian_path(name):
+    """`bm=BrownianPath(...)`: a thin wrapper around an interval. The solver unwraps it; the route must ask its questions of the
+    interval too, not of the wrapper the caller handed in. Gradients against the stepwise adjoint on the same object."""
+    import torchsde_amd
+    make, d, m = MODULES[name]
+    sde = make()
+    B = GRID_B
+    gen = torch.Generator(device=DEV).manual_seed(19)
+    weights = torch.randn(3, B, d, device=DEV, generator=gen)
+    ts = torch.tensor(helpers.rheun_ts("aligned"), device=DEV)
+
+    def solve(bm, stepwise=False):
+        y0 = torch.full((B, d), 0.2, device=DEV, requires_grad=True)
+        opts = {"trajectory_kernel": False} if stepwise else None
+        ys = torchsde_amd.sdeint_adjoint(sde, y0, ts, bm=bm, method="reversible_heun", adjoint_method="adjoint_reversible_heun",
+                                         dt=DT, options=opts, adjoint_options=opts)
+        return ys, y0
+    for k in range(2):
+        state = np.random.get_state()
+        np.random.seed(100 + k)                  # (a BrownianPath draws its entropy from numpy's global generator)
+        bm = torchsde_amd.BrownianPath(t0=0.0, w0=torch.zeros(B, m, device=DEV))
+        np.random.set_state(state)
+        ys, y0 = solve(bm)                       # (the first solve verifies and returns the stepwise result)
+        assert (type(ys.grad_fn).__name__ == "ReversibleHeunFnBackward") == (k == 1), (k, type(ys.grad_fn).__name__)
+        assert torch.isfinite(ys).all() and not torch.equal(ys[-1], ys[0])
+        grads = _grads(sde, ys, y0, weights)
+        ys_s, y0_s = solve(bm, stepwise=True)    # the same path: the interval answers a repeated query with the same increment
+        torch.testing.assert_close(ys.detach(), ys_s.detach(), rtol=5e-5, atol=5e-6)
+        _same(grads, _grads(sde, ys_s, y0_s, weights), 2e-3)
+    assert all(v is True for v in _book(sde)["trusted"].values()), _book(sde)
+
+
+# ---- the other reverse-mode sweeps (`_MlpTrajectoryFn`, `_MlpAdjointFn`) over the same grids -----------------------------------
+@pytest.mark.parametrize("grid", ["inside", "crowded", "ragged"])
+@pytest.mark.parametrize("how", ["autograd", "adjoint"])
+def test_the_perceptron_drift_module_over_output_grids(how, grid):
+    """`MLPDriftDiagonalSDE` (d 8, hidden 16), Euler: `sdeint` under autograd against back-propagation through the oracle's solver,
+    `sdeint_adjoint(adjoint_method="euler")` against the oracle's restatement of the reference's adjoint -- after a solve on
+    `aligned`, whichever route a grid takes."""
+    import torchsde_amd
+    B, d, hidden = GRID_B, 8, 16
+    gen = torch.Generator().manual_seed(5)
+    torch.manual_seed(5)
+    sde = torchsde_amd.MLPDriftDiagonalSDE(d, hidden, activation="tanh", diffusion="sigmoid", diff_scale=0.4, sde_type="ito",
+                                           diff_rate=2.0 * torch.rand(d, generator=gen) - 0.1,
+                                           diff_shift=0.1 + 0.2 * torch.rand(d, generator=gen)).to(DEV)
+
+    def solve(ts_list, entropy):
+        y0 = torch.full((B, d), 0.2, device=DEV, requires_grad=True)
+        ts = torch.tensor(ts_list, device=DEV)
+        bm = _bm(B, d, float(ts[-1]), entropy)
+        if how == "autograd":
+            return torchsde_amd.sdeint(sde, y0, ts, bm=bm, method="euler", dt=DT), y0
+        return torchsde_amd.sdeint_adjoint(sde, y0, ts, bm=bm, method="euler", adjoint_method="euler", dt=DT), y0
+    sweep = "_MlpTrajectoryFn" if how == "autograd" else "_MlpAdjointFn"
+    for entropy in (1, 2):
+        ys, _ = solve(helpers.rheun_ts("aligned"), entropy)
+    assert sweep in type(ys.grad_fn).__name__, type(ys.grad_fn).__name__       # (the sweeps these cases are about)
+    ts_list = helpers.rheun_ts(grid)
+    ys, y0 = solve(ts_list, GRID_ENTROPY)
+    print(f"MLPDriftDiagonalSDE {how} {grid}: grad_fn {type(ys.grad_fn).__name__}")
+    if grid == "ragged" and how == "autograd":
+        assert sweep in type(ys.grad_fn).__name__, type(ys.grad_fn).__name__
+    _against_the_oracle(sde, d, ts_list, ys, y0, f"MLPDriftDiagonalSDE {how} {grid}", adjoint=how == "adjoint", method="euler",
+                        adjoint_method="euler")

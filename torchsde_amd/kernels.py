@@ -569,6 +569,11 @@ def error_norm(y_full, y_half, rtol, atol, eps=1e-7, scratch=None):
     return out[0]
 
 
+def _on_boundaries(out_w):
+    """Every output on a step boundary (no interpolation): the weights as the grid gave them, before any cast."""
+    return all(float(w0) == 0.0 and float(w1) == 1.0 for (w0, w1) in out_w)
+
+
 class TrajectorySchedule:
     """Device-resident ``tsde_traj_t`` of one solve: step rows, Brownian cells and the output map."""
 
@@ -583,6 +588,7 @@ class TrajectorySchedule:
         self.rows = torch.from_numpy(rows).to(device)
         self.cells = torch.from_numpy(self.host_cells.view(np.int32)).to(device)
         self.out_step = torch.from_numpy(np.ascontiguousarray(out_step, dtype=np.int32)).to(device)
+        self.on_boundaries = _on_boundaries(out_w)
         self.out_w = torch.from_numpy(np.ascontiguousarray(out_w, dtype=np_dtype).reshape(-1, 2)).to(device)
         s = _native.Traj()
         s.step_rows, s.cells = self.rows.data_ptr(), self.cells.data_ptr()
@@ -629,8 +635,8 @@ class SolveSteps:
 
     @property
     def on_boundaries(self):
-        """Every output on a step boundary (no interpolation)."""
-        return all(w0 == 0.0 and w1 == 1.0 for (w0, w1) in self.out_w)
+        """Every output on a step boundary (no interpolation); `TrajectorySchedule.on_boundaries` of its schedules."""
+        return _on_boundaries(self.out_w)
 
     def schedule(self, device, dtype, dt=None, every_step=False):
         """The `TrajectorySchedule`. `dt`: step sizes other than the grid's (those of an adjoint's backward solve);

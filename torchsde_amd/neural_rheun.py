@@ -288,6 +288,8 @@ class ReversibleHeunFn(torch.autograd.Function):
         nf = len(drift.parameters())
         f_net, g_net = drift.rebuilt(tensors[:nf]), diffusion.rebuilt(tensors[nf:])
         noise, m, schedule, times = ctx.noise, ctx.m, ctx.schedule, ctx.times
+        if not schedule.on_boundaries:       # (`solve` refuses these up front; the function applied directly ends here)
+            raise ValueError("the reversible-Heun sweep does not differentiate a schedule that interpolates an output")
         rows, d = ys.shape[1], ys.shape[2]
         dev = ys.device
         general = noise == _native.NOISE_GENERAL
@@ -348,4 +350,11 @@ def solve(y0, drift, diffusion, noise, m, schedule, times_host, bm, z_holder=Non
     second state after the last step."""
     times = _device_times(times_host, y0.device)
     tensors = drift.parameters() + diffusion.parameters()
+    if not schedule.on_boundaries and torch.is_grad_enabled() and any(t.requires_grad for t in (y0, *tensors)):
+        # `ReversibleHeunFn.backward` adds an output's whole cotangent to a_y at its step and restarts the reconstruction from
+        # the stored output: right only where the output IS the state after that step. (Refused here, not in the function's
+        # `forward`: in there recording is always off and `needs_input_grad` does not know the caller's grad mode.)
+        raise ValueError("the reversible-Heun kernels differentiate only solves whose outputs all sit on step boundaries: "
+                         "this schedule interpolates an output inside a step (out_w != (0, 1)) and an input requires a "
+                         "gradient; solve it stepwise, or without a gradient")
     return ReversibleHeunFn.apply(drift, diffusion, int(noise), int(m), schedule, times, z_holder, bm, y0, *tensors)

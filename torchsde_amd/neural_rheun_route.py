@@ -47,7 +47,9 @@ class Route:
 def plan(solver, y0, ts, differentiable, need_boundaries=False, tag=()):
     """The `Route` of this solve, or None when it stays stepwise. `differentiable`: a gradient will be asked of the result (the
     interpretation then watches for stop-gradients); `need_boundaries`: every output must sit on a step boundary (the backward
-    sweep of `sdeint_adjoint` steps to each of them, adjoint.py:97-112)."""
+    sweep of `sdeint_adjoint` steps to each of them, adjoint.py:97-112, and the kernels' own sweep does not split an
+    interpolated output's cotangent between the two states it mixes: every solve with a gradient asks for this). Checked
+    before the ledger is consulted, so a solve that fails it files no verdict."""
     from . import recognise
     from .sde import ForwardSDE
     sde, bm = solver.sde, solver._native_bm()
@@ -120,6 +122,8 @@ def plan_adjoint(solver, sde, y0, ts, bm, dt, adjoint_params):
     held = {id(p) for p in route.parameters() if p.requires_grad}
     if wanted != held:
         return None
-    if K.backward_step_sizes(bm, timegrid.ts_to_host(ts), dt, route.cells, route.out_steps) is None:
+    # (`bm` is the caller's object, kept for the call site: it may be a BrownianPath / BrownianTree around the interval that
+    #  `plan` has just required `solver._native_bm()` to be, and only that interval has cells to walk)
+    if K.backward_step_sizes(solver._native_bm(), timegrid.ts_to_host(ts), dt, route.cells, route.out_steps) is None:
         return None
     return route

@@ -1238,7 +1238,9 @@ class ReversibleHeun(BaseSDESolver):
         tracks = self._tracks_grad(y0)
         if tracks and self.wants_extra:
             return None               # (the final (f, g, z) with a graph: the stepwise loop has it)
-        route = neural_rheun_route.plan(self, y0, ts, differentiable=tracks)
+        # (with a gradient every output must sit on a step boundary: the backward sweep places an output's whole cotangent
+        #  on its step and does not split it by the interpolation weights; such solves stay on the stepwise loop)
+        route = neural_rheun_route.plan(self, y0, ts, differentiable=tracks, need_boundaries=tracks)
         if route is None:
             return None
         z_last = []

@@ -114,12 +114,7 @@ __global__ void __launch_bounds__(NW * 64) mlp_adjoint_kernel(const MlpAdjArgs p
   const int64_t row = row0 + n < p.B ? row0 + n : p.B - 1;
   const float own_row = row0 + n < p.B ? 1.0f : 0.0f;     // (a shadow lane of the last partial wave adds nothing to the sums)
   float* wave_sums = sums + wave * 2 * D;
-  NoiseKey key = p.key;
-  if (p.key_dev != nullptr) {
-    const uint64_t ent = *p.key_dev;
-    key.k0 = (uint32_t)ent;
-    key.k1 = (uint32_t)(ent >> 32);
-  }
+  const NoiseKey key = launch_key(p.key, p.key_dev);
   const uint32_t off_d = (uint32_t)(row * dT) + 4 * part, off_h = (uint32_t)(row * hT) + 4 * part;
   const uint64_t quad0 = (key.elem0 + (uint64_t)(row * dT) + 4 * part) >> 2;
   auto real_d = [&](int t) { return FULL || R * t + 4 * part < dT; };

@@ -93,12 +93,7 @@ __global__ void __launch_bounds__(NW * 64) mlp_backward_kernel(const MlpBackArgs
   const int64_t row0 = ((int64_t)blockIdx.x * NW + wave) * R;
   if (row0 >= p.B) return;
   const int64_t row = row0 + n < p.B ? row0 + n : p.B - 1;
-  NoiseKey key = p.key;
-  if (p.key_dev != nullptr) {
-    const uint64_t ent = *p.key_dev;
-    key.k0 = (uint32_t)ent;
-    key.k1 = (uint32_t)(ent >> 32);
-  }
+  const NoiseKey key = launch_key(p.key, p.key_dev);
 
   // register r of tile t in this lane = channel 16 t + 4 part + r of batch row `row` (one 16-byte quad per tile).
   // Addresses are a wave-uniform base (SGPRs) + ONE 32-bit lane offset per row width + a constant per tile, so that

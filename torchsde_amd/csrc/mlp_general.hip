@@ -85,12 +85,6 @@ struct NoiseShape {
   static constexpr int kQuads = (M >= 16) ? M / 16 : 1;      // Philox quads of a row's increments one lane needs
 };
 
-// One normal of the field, out of line: the element-by-element paths (d % 4 != 0, m not a tile width, an unaligned field) are
-// rare and must not cost the common path registers.
-__device__ __noinline__ float draw_one(NoiseKey key, uint64_t elem, uint32_t cell, uint32_t stream) {
-  return normal1<float>(key, elem, cell, 0, stream);
-}
-
 // the diffusion net's output function (uniform over the launch: callers branch once, outside their loops)
 template <bool SIGMOID>
 TSDE_D float finalise(float z) {
@@ -98,40 +92,10 @@ TSDE_D float finalise(float z) {
   return z;
 }
 
-// Schedule of a straight-line region of READS LDS operand reads, each feeding PER matrix instructions: the first few reads
-// go out ahead, then every group of PER MFMAs is followed by one more read -- left alone, hipcc emits read -> wait -> PER
-// MFMAs and the wave (there is ONE per SIMD at the configs[2] shape, nothing else to switch to) sits out the LDS latency
-// once per read: 18.7 ms per 1000-step solve at 16384 x 32 x 16 before, see DESIGN.md for after.
-template <int READS, int PER>
-TSDE_D void reads_ahead() {
-  constexpr int AHEAD = READS < 4 ? READS : 4;
-  __builtin_amdgcn_sched_group_barrier(0x100, AHEAD, 0);
-#pragma unroll
-  for (int i = 0; i < READS; ++i) {
-    __builtin_amdgcn_sched_group_barrier(0x008, PER, 0);
-    if (i < READS - AHEAD) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-  }
-  __builtin_amdgcn_sched_barrier(0);
-}
-
-// LDS footprint in floats (rows padded by 4: the four lane quarters of a wave read rows 4 apart, see mlp_trajectory.hip)
+// LDS row strides in floats (rows padded by 4: the four lane quarters of a wave read rows 4 apart, see mlp_trajectory.hip)
 template <int D, int H>
 struct NeuralLds {
   static constexpr int S1 = H + 4, S2F = D + 4;
-  static constexpr int out_padded(int out, int group) { return (out + 16 * group - 1) / (16 * group) * (16 * group); }
-};
-
-// General noise, exact f32: the diffusion net's second layer sits in LDS with the two tiles of a PAIR interleaved -- element
-// (unit u, output o = 16 tile + c) at u * stride + 32 (tile / 2) + 2 c + (tile & 1) -- so that a lane's two A operands of a
-// unit are ONE ds_read_b64, and with a row stride of 8 (mod 16) floats: a b64 read is served in two halves of 32 lanes, the two
-// lane quarters of a half read units 4 apart, 4 * stride = 32 (mod 64) banks puts them on the two halves of the banks.
-// For D <= 32 the stride is D * M + 8 whatever the real width: every row offset of the products is then an immediate of the
-// read (the address arithmetic between the matrix instructions cost more than the reads: profiles/r6_microbench_mfma_fillers.txt).
-template <int D, int MODE, bool SPLIT>
-struct PairLayout {
-  static constexpr bool kOn = MODE >= 4 && !SPLIT;
-  static constexpr bool kFixed = kOn && D <= 32;
-  static constexpr int kPad = kOn ? 8 : 4;
 };
 
 // SPLIT (opt-in, `options={"matrix_precision": "bf16x3"}`; general noise, H = 64): the diffusion net's SECOND layer -- 512 of
@@ -174,30 +138,16 @@ __global__ void __launch_bounds__(256, (MODE >= 4 || (H <= 64 && !GENERIC)) ? 2 
   float* wtg = b1g + H;
   float* b2f = wtg + H;                 // D
   float* b2g = b2f + D;                 // outp
-  const int dT = p.d, hf = p.f.hidden, hg = p.g.hidden, outT = p.g.out;
+  const int dT = p.d, hg = p.g.hidden, outT = p.g.out;
   // weights into LDS, zero-padded to the tile sizes: padded hidden units see zero weights both ways, padded state channels
   // and padded outputs are never read back (their selectors are 0 / their channels are skipped)
-  for (int i = threadIdx.x; i < D * H; i += 256) {
-    const int k = i / H, u = i % H;
-    W1f[k * S1 + u] = (k < dT && u < hf) ? p.f.w1[k * hf + u] : 0.0f;
-    W1g[k * S1 + u] = (k < dT && u < hg) ? p.g.w1[k * hg + u] : 0.0f;
-    const int u2 = i / D, c = i % D;
-    W2f[u2 * S2F + c] = (u2 < hf && c < dT) ? p.f.w2[u2 * dT + c] : 0.0f;
-  }
+  stage_two_nets<D, H>(p.f, p.g, dT, W1f, W1g, W2f);
   __bf16* W2hi = reinterpret_cast<__bf16*>(W2g);         // SPLIT: [outp][H] heads, then [outp][H] tails (same bytes as f32)
   __bf16* W2lo = W2hi + (size_t)outp * H;
   for (int i = threadIdx.x; i < H * outp; i += 256) {
     const int u = i / outp, o = i % outp;
-    // general noise: the net's outputs are (i, j) row-major with m REAL Brownian channels; the tiles want i * M + j with M the
-    // channel count padded to 4 / 8 / 16 / 32 (padded channels: zero weights, zero bias, zero increments)
-    int src = o;
-    bool have = o < outT;
-    if constexpr (NS::kGeneral) {
-      const int ci = o / M, cj = o % M;
-      have = ci < dT && cj < p.m;
-      src = ci * p.m + cj;
-    }
-    const float w = (u < hg && have) ? p.g.w2[(int64_t)u * outT + src] : 0.0f;
+    const OutputSource from = padded_output<NS::kGeneral>(o, M, dT, p.m, outT);
+    const float w = (u < hg && from.have) ? p.g.w2[(int64_t)u * outT + from.src] : 0.0f;
     if constexpr (SPLIT) {
       // unit u = 32 b + 16 tt + 4 part + r  ->  chunk 4 b + part (swizzled by the row), position 4 tt + r
       const int b = u >> 5, tt = (u >> 4) & 1, pq = (u >> 2) & 3, r = u & 3;
@@ -205,44 +155,25 @@ __global__ void __launch_bounds__(256, (MODE >= 4 || (H <= 64 && !GENERIC)) ? 2 
       const __bf16 hi = (__bf16)w;
       W2hi[(size_t)o * H + 8 * chunk + 4 * tt + r] = hi;
       W2lo[(size_t)o * H + 8 * chunk + 4 * tt + r] = (__bf16)(w - (float)hi);
-    } else if constexpr (PL::kOn) {
-      W2g[u * S2G + 32 * (o >> 5) + 2 * (o & 15) + ((o >> 4) & 1)] = w;
     } else {
-      W2g[u * S2G + o] = w;
+      W2g[u * S2G + (PL::kOn ? pair_slot(o) : o)] = w;
     }
   }
-  for (int i = threadIdx.x; i < H; i += 256) {
-    b1f[i] = i < hf ? p.f.b1[i] : 0.0f;
-    wtf[i] = (i < hf && p.f.w1t) ? p.f.w1t[i] : 0.0f;
-    b1g[i] = i < hg ? p.g.b1[i] : 0.0f;
-    wtg[i] = (i < hg && p.g.w1t) ? p.g.w1t[i] : 0.0f;
-  }
-  for (int i = threadIdx.x; i < D; i += 256) b2f[i] = i < dT ? p.f.b2[i] : 0.0f;
+  stage_two_nets_biases<D, H>(p.f, p.g, dT, b1f, wtf, b1g, wtg, b2f);
   // (general noise with a closing sigmoid: the bias is staged as -log2(e) * b2, so that the epilogue's sigmoid argument is one
   //  fma of the accumulator, 1 / (1 + 2^(-log2(e) acc - log2(e) b2)))
   constexpr float kNegLog2e = -1.4426950408889634f;
   const bool prescaled = NS::kGeneral && p.g.final == TSDE_FINAL_SIGMOID;
   for (int i = threadIdx.x; i < outp; i += 256) {
-    int src = i;
-    bool have = i < outT;
-    if constexpr (NS::kGeneral) {
-      const int ci = i / M, cj = i % M;
-      have = ci < dT && cj < p.m;
-      src = ci * p.m + cj;
-    }
-    const float b = have ? p.g.b2[src] : 0.0f;
+    const OutputSource from = padded_output<NS::kGeneral>(i, M, dT, p.m, outT);
+    const float b = from.have ? p.g.b2[from.src] : 0.0f;
     b2g[i] = prescaled ? b * kNegLog2e : b;
   }
   __syncthreads();
 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int part = lane >> 4, n = lane & 15;
-  NoiseKey key = p.key;
-  if (p.key_dev != nullptr) {
-    const uint64_t ent = *p.key_dev;
-    key.k0 = (uint32_t)ent;
-    key.k1 = (uint32_t)(ent >> 32);
-  }
+  const NoiseKey key = launch_key(p.key, p.key_dev);
   const bool midpoint = p.method == TSDE_TRAJ_MIDPOINT;
   const bool milstein_ito = p.method == TSDE_TRAJ_MILSTEIN_ITO || p.method == TSDE_TRAJ_MILSTEIN_ITO_GF;
   const bool grad_free = p.method == TSDE_TRAJ_MILSTEIN_ITO_GF || p.method == TSDE_TRAJ_MILSTEIN_STRAT_GF;
@@ -1080,20 +1011,11 @@ __global__ void __launch_bounds__(256, (MODE >= 4 || (H <= 64 && !GENERIC)) ? 2 
   }
 }
 
-size_t neural_lds_bytes(int D, int H, int outp, int pad) {
-  // (+ 32: the general-noise pipeline requests the output biases of the pair after the last one)
-  return ((size_t)2 * D * (H + 4) + (size_t)H * (D + 4) + (size_t)H * (outp + pad) + 4 * H + D + outp + 32) * sizeof(float);
-}
-
-static size_t neural_lds_limit() {
-  static const size_t limit = [] {
-    int dev = 0, bytes = 0;
-    if (hipGetDevice(&dev) == hipSuccess &&
-        hipDeviceGetAttribute(&bytes, hipDeviceAttributeSharedMemPerBlockOptin, dev) == hipSuccess && bytes > 0)
-      return (size_t)bytes;
-    return (size_t)(64 * 1024);
-  }();
-  return limit;
+// Padded width of the diffusion's last layer. General noise (mode = the padded channel count M): a multiple of 32 -- the kernel
+// takes the output tiles NoiseShape::G = 2 at a time -- and up to 32 state channels D * M whatever the real width (PairLayout's
+// fixed stride; not in the split mode). Any other noise: the net's own width in tiles of 16.
+static int neural_outp(int D, int d, int out, int mode, bool split) {
+  return mode >= 4 ? ((D <= 32 && !split ? D : d) * mode + 31) / 32 * 32 : (out + 15) / 16 * 16;
 }
 
 template <int D, int H, int MODE, bool SPLIT = false, bool GENERIC = false, bool MILSTEIN = false>
@@ -1101,28 +1023,9 @@ static hipError_t launch_neural_mode(const NeuralArgs& p, hipStream_t s) {
   if constexpr (!SPLIT && NoiseShape<MODE>::kGeneral && H == 64) {
     if (p.split) return launch_neural_mode<D, H, MODE, true>(p, s);
   }
-  using PL = PairLayout<D, MODE, SPLIT>;
-  const int outp = PL::kFixed ? D * MODE
-                   : NoiseShape<MODE>::kGeneral ? NeuralLds<D, H>::out_padded(p.d * MODE, NoiseShape<MODE>::G)
-                                                : NeuralLds<D, H>::out_padded(p.g.out, 1);
-  const size_t lds_bytes = neural_lds_bytes(D, H, outp, PL::kPad);
-  if (lds_bytes > neural_lds_limit()) return hipErrorInvalidValue;
-  static bool configured = false;   // per instantiation
-  if (!configured) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&neural_trajectory_kernel<D, H, MODE, SPLIT, GENERIC, MILSTEIN>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
-    if (e != hipSuccess) return e;
-    configured = true;
-  }
-  const int64_t groups = (p.B + 15) / 16;
-  int64_t blocks = (groups + 3) / 4;
-  // resident blocks: the LDS of a CU holds floor(160 KiB / footprint) of them
-  const int64_t per_cu = (int64_t)((160 * 1024) / lds_bytes) < 1 ? 1 : (int64_t)((160 * 1024) / lds_bytes);
-  const int64_t resident = 256 * (per_cu > 8 ? 8 : per_cu);
-  if (blocks > resident) blocks = resident;
-  hipLaunchKernelGGL((neural_trajectory_kernel<D, H, MODE, SPLIT, GENERIC, MILSTEIN>), dim3((unsigned)blocks), dim3(256), lds_bytes, s, p,
-                     outp);
-  return hipGetLastError();
+  const int outp = neural_outp(D, p.d, p.g.out, MODE, SPLIT);
+  const size_t lds_bytes = two_net_lds_bytes(D, H, outp, PairLayout<D, MODE, SPLIT>::kPad, 0);
+  return launch_weights_resident<&neural_trajectory_kernel<D, H, MODE, SPLIT, GENERIC, MILSTEIN>>(p, outp, lds_bytes, s);
 }
 
 template <int D, int H>
@@ -1183,27 +1086,21 @@ size_t neural_footprint(int64_t d, int64_t m, int64_t hf, int64_t hg, int64_t ou
   const int64_t h = hf > hg ? hf : hg;
   const int H = h <= 32 ? 32 : h <= 64 ? 64 : (h <= 128 && noise != TSDE_NOISE_GENERAL) ? 128 : 0;
   if (D == 0 || H == 0) return 0;
-  int group = 1, pad = 4;
+  int mode = 0;
   if (noise == TSDE_NOISE_GENERAL) {
     if (m < 1 || m > 32) return 0;
-    const int64_t M = m <= 4 ? 4 : m <= 8 ? 8 : m <= 16 ? 16 : 32;
-    group = M >= 32 ? (int)M / 16 : 2;
-    out = (D <= 32 ? D : d) * M;          // (PairLayout: a fixed stride up to 32 state channels; the split mode is no larger)
-    pad = 8;
+    mode = m <= 4 ? 4 : m <= 8 ? 8 : m <= 16 ? 16 : 32;
   }
-  const int outp = (int)((out + 16 * group - 1) / (16 * group) * (16 * group));
-  return neural_lds_bytes(D, H, outp, pad);
+  // (general noise: the exact-f32 layout, rows padded by 8; the split mode is no larger)
+  return two_net_lds_bytes(D, H, neural_outp(D, (int)d, (int)out, mode, false), mode >= 4 ? 8 : 4, 0);
 }
 
-hipError_t launch_trajectory_mlp_general(void* ys, const void* y0, int64_t rows, int64_t d, int64_t m, int noise,
-                                         const tsde_mlp_t* drift, const tsde_mlp_t* diffusion, int method,
-                                         const tsde_traj_t* tr, NoiseKey key, const uint64_t* key_dev, hipStream_t s) {
-  NeuralArgs p;
-  p.split = diffusion->precision == TSDE_PRECISION_BF16X3 ? 1 : 0;
+static void fill_common(NeuralArgs& p, void* ys, const void* y0, int64_t rows, int64_t d, int64_t m, const tsde_mlp_t* drift,
+                        int method, const tsde_traj_t* tr, NoiseKey key, const uint64_t* key_dev) {
+  memset(&p, 0, sizeof(p));     // (no split products, no diffusion table)
   p.ys = (float*)ys;
   p.y0 = (const float*)y0;
   p.f = device_view(drift);
-  p.g = device_view(diffusion);
   p.rows = (const float*)tr->step_rows;
   p.cells = tr->cells;
   p.out_step = tr->out_step;
@@ -1216,13 +1113,24 @@ hipError_t launch_trajectory_mlp_general(void* ys, const void* y0, int64_t rows,
   p.method = method;
   p.key = key;
   p.key_dev = key_dev;
-  p.gtab = nullptr;
-  p.g_step_stride = p.g_slot_stride = 0;
-  if (rows <= 0 || tr->n_steps <= 0) return hipSuccess;
-  if (d <= 16) return launch_neural_d<16>(p, noise, s);
-  if (d <= 32) return launch_neural_d<32>(p, noise, s);
-  if (d <= 64) return launch_neural_d<64>(p, noise, s);
+}
+
+static hipError_t launch_neural(const NeuralArgs& p, int noise, hipStream_t s) {
+  if (p.B <= 0 || p.n_steps <= 0) return hipSuccess;
+  if (p.d <= 16) return launch_neural_d<16>(p, noise, s);
+  if (p.d <= 32) return launch_neural_d<32>(p, noise, s);
+  if (p.d <= 64) return launch_neural_d<64>(p, noise, s);
   return hipErrorInvalidValue;
+}
+
+hipError_t launch_trajectory_mlp_general(void* ys, const void* y0, int64_t rows, int64_t d, int64_t m, int noise,
+                                         const tsde_mlp_t* drift, const tsde_mlp_t* diffusion, int method,
+                                         const tsde_traj_t* tr, NoiseKey key, const uint64_t* key_dev, hipStream_t s) {
+  NeuralArgs p;
+  fill_common(p, ys, y0, rows, d, m, drift, method, tr, key, key_dev);
+  p.split = diffusion->precision == TSDE_PRECISION_BF16X3 ? 1 : 0;
+  p.g = device_view(diffusion);
+  return launch_neural(p, noise, s);
 }
 
 // Additive noise: the drift a perceptron of (t, y), the diffusion a table (see the kernel's MODE 2).
@@ -1230,32 +1138,13 @@ hipError_t launch_trajectory_mlp_additive(void* ys, const void* y0, int64_t rows
                                           const void* gtab, int time_dependent, int method, const tsde_traj_t* tr,
                                           NoiseKey key, const uint64_t* key_dev, hipStream_t s) {
   NeuralArgs p;
-  p.split = 0;
-  p.ys = (float*)ys;
-  p.y0 = (const float*)y0;
-  p.f = device_view(drift);
+  fill_common(p, ys, y0, rows, d, m, drift, method, tr, key, key_dev);
   p.g = NeuralNet{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, TSDE_ACT_TANH, TSDE_FINAL_NONE, 1.0f};
-  p.rows = (const float*)tr->step_rows;
-  p.cells = tr->cells;
-  p.out_step = tr->out_step;
-  p.out_w = (const float*)tr->out_w;
-  p.B = rows;
-  p.d = (int32_t)d;
-  p.m = (int32_t)m;
-  p.n_steps = tr->n_steps;
-  p.n_out = tr->n_out;
-  p.method = method;
-  p.key = key;
-  p.key_dev = key_dev;
   const int slots = method == TSDE_TRAJ_EULER ? 1 : 2;
   p.gtab = (const float*)gtab;
   p.g_slot_stride = time_dependent ? m * d : 0;
   p.g_step_stride = time_dependent ? (int64_t)slots * m * d : 0;
-  if (rows <= 0 || tr->n_steps <= 0) return hipSuccess;
-  if (d <= 16) return launch_neural_d<16>(p, TSDE_NOISE_ADDITIVE, s);
-  if (d <= 32) return launch_neural_d<32>(p, TSDE_NOISE_ADDITIVE, s);
-  if (d <= 64) return launch_neural_d<64>(p, TSDE_NOISE_ADDITIVE, s);
-  return hipErrorInvalidValue;
+  return launch_neural(p, TSDE_NOISE_ADDITIVE, s);
 }
 
 }  // namespace tsde

@@ -110,12 +110,7 @@ __global__ void __launch_bounds__(NW * 64) mlp_trajectory_kernel(const MlpArgs p
   const int64_t row0 = ((int64_t)blockIdx.x * NW + wave) * R;
   if (row0 >= p.B) return;
   const int64_t row = row0 + n < p.B ? row0 + n : p.B - 1;
-  NoiseKey key = p.key;
-  if (p.key_dev != nullptr) {
-    const uint64_t ent = *p.key_dev;
-    key.k0 = (uint32_t)ent;
-    key.k1 = (uint32_t)(ent >> 32);
-  }
+  const NoiseKey key = launch_key(p.key, p.key_dev);
   // Addresses are a wave-uniform base (SGPRs) + ONE 32-bit lane offset + a constant per quad, so that no per-tile
   // 64-bit address lives in vector registers across the solve (the C ABI keeps rows * d < 2^30).
   const uint32_t off_d = (uint32_t)(row * dT);

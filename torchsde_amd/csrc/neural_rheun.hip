@@ -3,17 +3,6 @@
 
 namespace tsde {
 
-static size_t rheun_lds_limit() {
-  static const size_t limit = [] {
-    int dev = 0, bytes = 0;
-    if (hipGetDevice(&dev) == hipSuccess &&
-        hipDeviceGetAttribute(&bytes, hipDeviceAttributeSharedMemPerBlockOptin, dev) == hipSuccess && bytes > 0)
-      return (size_t)bytes;
-    return (size_t)(64 * 1024);
-  }();
-  return limit;
-}
-
 // (general noise: a multiple of 32 -- the kernel takes the diffusion's output tiles two at a time)
 // (up to 32 state channels the padded width D * mode: the kernels' row stride is then a compile-time constant)
 static int rheun_outp(int D, int d, int out, int mode) {
@@ -23,22 +12,8 @@ static int rheun_outp(int D, int d, int out, int mode) {
 template <int D, int H, int MODE, bool BACKWARD>
 static hipError_t launch_rheun_mode(const RheunArgs& p, hipStream_t s) {
   const int outp = rheun_outp(D, p.d, p.g.out, MODE);
-  const size_t lds_bytes = rheun_lds_floats(D, H, outp, p.f.n_mid, p.g.n_mid) * sizeof(float);
-  if (lds_bytes > rheun_lds_limit()) return hipErrorInvalidValue;
-  static bool configured = false;   // per instantiation
-  if (!configured) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&neural_rheun_kernel<D, H, MODE, BACKWARD>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024));
-    if (e != hipSuccess) return e;
-    configured = true;
-  }
-  const int64_t groups = (p.B + 15) / 16;
-  int64_t blocks = (groups + 3) / 4;
-  const int64_t per_cu = (int64_t)((160 * 1024) / lds_bytes) < 1 ? 1 : (int64_t)((160 * 1024) / lds_bytes);
-  const int64_t resident = 256 * (per_cu > 8 ? 8 : per_cu);
-  if (blocks > resident) blocks = resident;
-  TSDE_LAUNCH((neural_rheun_kernel<D, H, MODE, BACKWARD>), dim3((unsigned)blocks), dim3(256), lds_bytes, s, p, outp);
-  return hipGetLastError();
+  const size_t lds_bytes = two_net_lds_bytes(D, H, outp, 8, p.f.n_mid + p.g.n_mid);
+  return launch_weights_resident<&neural_rheun_kernel<D, H, MODE, BACKWARD>>(p, outp, lds_bytes, s);
 }
 
 template <int D, int H, bool BACKWARD>
@@ -82,7 +57,7 @@ size_t rheun_footprint(int64_t d, int64_t m, int64_t hf, int64_t hg, int64_t out
     mode = m <= 4 ? 4 : 16;
   }
   if (mode < 0) return 0;
-  return rheun_lds_floats(D, H, rheun_outp(D, (int)d, (int)out, mode), nmf, nmg) * sizeof(float);
+  return two_net_lds_bytes(D, H, rheun_outp(D, (int)d, (int)out, mode), 8, nmf + nmg);
 }
 
 static DeepNet deep_view(const tsde_deep_mlp_t* n) {

@@ -589,12 +589,7 @@ __global__ void __launch_bounds__(kBlock) trajectory_expr_kernel(const ExprArgs<
   T y[W];
 #pragma unroll
   for (int q = 0; q < W; ++q) y[q] = y_init.v[q];
-  NoiseKey key = p.key;
-  if (p.key_dev != nullptr) {
-    const uint64_t ent = *p.key_dev;
-    key.k0 = (uint32_t)ent;
-    key.k1 = (uint32_t)(ent >> 32);
-  }
+  const NoiseKey key = launch_key(p.key, p.key_dev);
   const uint64_t elem = key.elem0 + (uint64_t)i;
   int j = 0;
   int next_out = next_output_step(p.out_step, 0, p.n_out);
@@ -968,12 +963,7 @@ __global__ void __launch_bounds__(kBlock) trajectory_prog_kernel(const ProgArgs<
   for (int q = 0; q < W; ++q) y.v[q] = y_init.v[q];
   M m;
   m.setup(p, col);
-  NoiseKey key = p.key;
-  if (p.key_dev != nullptr) {
-    const uint64_t ent = *p.key_dev;
-    key.k0 = (uint32_t)ent;
-    key.k1 = (uint32_t)(ent >> 32);
-  }
+  const NoiseKey key = launch_key(p.key, p.key_dev);
   const bool scalar_noise = p.scalar_noise != 0;
   const uint64_t elem = key.elem0 + (uint64_t)(scalar_noise ? i / p.d : i);
   int j = 0;
@@ -1192,12 +1182,7 @@ __global__ void __launch_bounds__(kBlock) trajectory_prog_sens_kernel(const Prog
   m.setup(q, i % p.d);
   S y(p.y0[i]);
   y.d[0] = (T)1;
-  NoiseKey key = p.key;
-  if (p.key_dev != nullptr) {
-    const uint64_t ent = *p.key_dev;
-    key.k0 = (uint32_t)ent;
-    key.k1 = (uint32_t)(ent >> 32);
-  }
+  const NoiseKey key = launch_key(p.key, p.key_dev);
   const uint64_t elem = key.elem0 + (uint64_t)(p.scalar_noise ? i / p.d : i);
   int j = 0;
   int next_out = next_output_step(p.out_step, 0, p.n_out);
@@ -1260,12 +1245,7 @@ __global__ void __launch_bounds__(kBlock) trajectory_prog_additive_kernel(const 
   for (int e = 0; e < W; ++e) y.v[e] = y_init.v[e];
   M m;                      // (the interpreter, or the drift program as generated code: specialise.py)
   m.setup(p, col);
-  NoiseKey key = p.key;
-  if (p.key_dev != nullptr) {
-    const uint64_t ent = *p.key_dev;
-    key.k0 = (uint32_t)ent;
-    key.k1 = (uint32_t)(ent >> 32);
-  }
+  const NoiseKey key = launch_key(p.key, p.key_dev);
   const int nm = q.m;
   const uint64_t elem = key.elem0 + (uint64_t)(i / p.d) * (uint64_t)nm;      // the row's first Brownian channel
   int j = 0;

@@ -158,13 +158,7 @@ inline void set_width(CellNoise<T>& c, double h) {
 // The key a kernel actually draws with: the baked one, or the device word if present (wave-uniform load).
 template <typename T>
 TSDE_D NoiseKey live_key(const CellNoise<T>& nz) {
-  NoiseKey k = nz.key;
-  if (nz.key_dev != nullptr) {
-    const uint64_t e = *nz.key_dev;
-    k.k0 = (uint32_t)e;
-    k.k1 = (uint32_t)(e >> 32);
-  }
-  return k;
+  return launch_key(nz.key, nz.key_dev);
 }
 
 // W and (optionally) U = h (W/2 + H) for W consecutive elements starting at local index i.

@@ -4,9 +4,59 @@
 
 #include "../../include/torchsde_amd.h"
 #include "tsde_bridge.h"
+#include "tsde_common.h"
 #include "tsde_rng.h"
 
 namespace tsde {
+
+// The dynamic LDS a block can be given, in bytes: the opt-in maximum (what hipFuncSetAttribute can raise a kernel to: 160 KiB
+// on gfx950), else the device's default maximum per block, else 64 KiB. Queried once. (The neural launchers' own copies of
+// this query went straight to 64 KiB when the opt-in attribute was not answered; they now try the default maximum first.)
+inline size_t dynamic_lds_limit() {
+  static const size_t limit = [] {
+    int dev = 0, bytes = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return (size_t)(64 * 1024);
+    if (hipDeviceGetAttribute(&bytes, hipDeviceAttributeSharedMemPerBlockOptin, dev) == hipSuccess && bytes > 0)
+      return (size_t)bytes;
+    if (hipDeviceGetAttribute(&bytes, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) == hipSuccess && bytes > 0)
+      return (size_t)bytes;
+    return (size_t)(64 * 1024);
+  }();
+  return limit;
+}
+
+// LDS bytes of the kernels that keep a drift AND a diffusion perceptron resident (mlp_general.hip, tsde_neural_rheun.h; the
+// staging is tsde_mlp.h's): both first layers, `n_mid` hidden-to-hidden layers, the drift's last layer, the diffusion's last
+// layer with its rows padded by `pad`, every bias, and 32 floats of slack behind the output biases (the general-noise
+// pipeline requests the biases of the pair after the last one). Rows are padded by 4 floats.
+inline size_t two_net_lds_bytes(int D, int H, int outp, int pad, int n_mid) {
+  const size_t S1 = H + 4;
+  return ((size_t)2 * D * S1 + (size_t)n_mid * H * S1 + (size_t)H * (D + 4) + (size_t)H * (outp + pad) + (size_t)4 * H +
+          (size_t)n_mid * H + D + outp + 32) * sizeof(float);
+}
+
+// Launch of such a kernel, `Kernel(p, outp)` with 256 threads a block: a block stages the weights once and its four waves walk
+// over groups of 16 rows, so the grid is the resident blocks -- the LDS of a CU holds floor(160 KiB / footprint) of them.
+// The kernel is allowed the 160 KiB once per instantiation.
+template <auto Kernel, typename Args>
+hipError_t launch_weights_resident(const Args& p, int outp, size_t lds_bytes, hipStream_t s) {
+  if (lds_bytes > dynamic_lds_limit()) return hipErrorInvalidValue;
+  constexpr size_t kCuLds = 160 * 1024;
+  static bool configured = false;
+  if (!configured) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             (int)kCuLds);
+    if (e != hipSuccess) return e;
+    configured = true;
+  }
+  const int64_t groups = (p.B + 15) / 16;
+  int64_t blocks = (groups + 3) / 4;
+  const int64_t per_cu = kCuLds / lds_bytes < 1 ? 1 : (int64_t)(kCuLds / lds_bytes);
+  const int64_t resident = 256 * (per_cu > 8 ? 8 : per_cu);
+  if (blocks > resident) blocks = resident;
+  TSDE_LAUNCH(Kernel, dim3((unsigned)blocks), dim3(256), lds_bytes, s, p, outp);
+  return hipGetLastError();
+}
 
 struct QueryArgs {
   const double* edges;  // device pointer, n_cells + 1 doubles

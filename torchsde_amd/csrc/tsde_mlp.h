@@ -1,5 +1,10 @@
-// Shared pieces of the perceptron-drift kernels (mlp_trajectory.hip: sampling; mlp_backward.hip: its gradient):
-// the two f32 MFMA tile shapes, the activations on the hardware transcendentals, and the LDS footprint.
+// Shared pieces of the perceptron kernels:
+//   perceptron drift (mlp_trajectory.hip: sampling; mlp_backward.hip, mlp_adjoint.hip: its gradients): the two f32 MFMA tile
+//     shapes, the activations on the hardware transcendentals, and the LDS footprint;
+//   drift AND diffusion perceptrons (mlp_general.hip, tsde_neural_rheun.h): everything the two kernels do BEFORE their step
+//     loops -- the staging of both nets into LDS, the padded (and pair-interleaved) layout of the diffusion's last layer --
+//     and the two helpers their step bodies share, the operand-read schedule and the out-of-line single draw. The step
+//     bodies themselves are hand-scheduled per kernel and are not shared.
 #pragma once
 #include "tsde_common.h"
 
@@ -95,6 +100,95 @@ TSDE_D DiffusionValue diffusion_value(bool sigmoid, float amp, float c, float e,
   }
   return v;
 }
+
+// ---- drift and diffusion perceptrons: mlp_general.hip, tsde_neural_rheun.h ------------------------------------------------
+
+// One normal of the field, out of line: the element-by-element paths (d % 4 != 0, m not a tile width, an unaligned field) are
+// rare and must not cost the common path registers.
+inline __device__ __noinline__ float draw_one(NoiseKey key, uint64_t elem, uint32_t cell, uint32_t stream) {
+  return normal1<float>(key, elem, cell, 0, stream);
+}
+
+// Schedule of a straight-line region of READS LDS operand reads, each feeding PER matrix instructions: the first few reads
+// go out ahead, then every group of PER MFMAs is followed by one more read -- left alone, hipcc emits read -> wait -> PER
+// MFMAs and the wave (there is ONE per SIMD at the configs[2] shape, nothing else to switch to) sits out the LDS latency
+// once per read: 18.7 ms per 1000-step solve at 16384 x 32 x 16 before, see DESIGN.md for after.
+template <int READS, int PER>
+TSDE_D void reads_ahead() {
+  constexpr int AHEAD = READS < 4 ? READS : 4;
+  __builtin_amdgcn_sched_group_barrier(0x100, AHEAD, 0);
+#pragma unroll
+  for (int i = 0; i < READS; ++i) {
+    __builtin_amdgcn_sched_group_barrier(0x008, PER, 0);
+    if (i < READS - AHEAD) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+}
+
+// Staging of both nets into LDS (called by all 256 threads of a block, before its barrier), zero-padded to the tile sizes D and
+// H: padded hidden units see zero weights both ways, padded state channels are never read back. Rows are padded by 4 floats
+// (the four lane quarters of a wave read rows 4 apart: conflict-free ds_read_b32). `Net`: NeuralNet or DeepNet -- the same field
+// names; `dT`: the real state width. Two calls, weights and biases: the kernels stage the diffusion's last layer in between,
+// and the order of these loops is part of what the register allocation of the step bodies depends on -- keep it (DESIGN.md
+// section 4).
+//   stage_two_nets: both first layers [input channel][hidden unit] and the drift's last layer [hidden unit][state channel]
+template <int D, int H, typename Net>
+TSDE_D void stage_two_nets(const Net& f, const Net& g, int dT, float* W1f, float* W1g, float* W2f) {
+  constexpr int S1 = H + 4, S2F = D + 4;
+  const int hf = f.hidden, hg = g.hidden;
+  for (int i = threadIdx.x; i < D * H; i += 256) {
+    const int k = i / H, u = i % H;
+    W1f[k * S1 + u] = (k < dT && u < hf) ? f.w1[k * hf + u] : 0.0f;
+    W1g[k * S1 + u] = (k < dT && u < hg) ? g.w1[k * hg + u] : 0.0f;
+    const int u2 = i / D, c = i % D;
+    W2f[u2 * S2F + c] = (u2 < hf && c < dT) ? f.w2[u2 * dT + c] : 0.0f;
+  }
+}
+//   stage_two_nets_biases: first-layer biases and time columns (b1, w1t) of both nets, and the drift's output bias
+template <int D, int H, typename Net>
+TSDE_D void stage_two_nets_biases(const Net& f, const Net& g, int dT, float* b1f, float* wtf, float* b1g, float* wtg,
+                                  float* b2f) {
+  const int hf = f.hidden, hg = g.hidden;
+  for (int i = threadIdx.x; i < H; i += 256) {
+    b1f[i] = i < hf ? f.b1[i] : 0.0f;
+    wtf[i] = (i < hf && f.w1t) ? f.w1t[i] : 0.0f;
+    b1g[i] = i < hg ? g.b1[i] : 0.0f;
+    wtg[i] = (i < hg && g.w1t) ? g.w1t[i] : 0.0f;
+  }
+  for (int i = threadIdx.x; i < D; i += 256) b2f[i] = i < dT ? f.b2[i] : 0.0f;
+}
+
+// Where output o of the diffusion's padded last layer comes from in the net's own last layer (weights and biases alike).
+// General noise: the net's outputs are (i, j) row-major with m REAL Brownian channels; the tiles want i * M + j with M the
+// channel count padded to a tile width (padded channels: zero weights, zero bias, zero increments). Any other noise: output o
+// itself, up to the net's width outT.
+struct OutputSource {
+  bool have;
+  int src;
+};
+template <bool GENERAL>
+TSDE_D OutputSource padded_output(int o, int M, int dT, int m, int outT) {
+  if constexpr (GENERAL) {
+    const int ci = o / M, cj = o % M;
+    return {ci < dT && cj < m, ci * m + cj};
+  }
+  return {o < outT, o};
+}
+
+// General noise, exact f32: the diffusion net's second layer sits in LDS with the two tiles of a PAIR interleaved -- element
+// (unit u, output o = 16 tile + c) at u * stride + 32 (tile / 2) + 2 c + (tile & 1), which is pair_slot(o) -- so that a lane's
+// two A operands of a unit are ONE ds_read_b64, and with a row stride of 8 (mod 16) floats: a b64 read is served in two halves
+// of 32 lanes, the two lane quarters of a half read units 4 apart, 4 * stride = 32 (mod 64) banks puts them on the two halves of
+// the banks. For D <= 32 the stride is D * M + 8 whatever the real width: every row offset of the products is then an immediate
+// of the read (the address arithmetic between the matrix instructions cost more than the reads:
+// profiles/r6_microbench_mfma_fillers.txt).
+template <int D, int MODE, bool SPLIT>
+struct PairLayout {
+  static constexpr bool kOn = MODE >= 4 && !SPLIT;
+  static constexpr bool kFixed = kOn && D <= 32;
+  static constexpr int kPad = kOn ? 8 : 4;
+};
+TSDE_D int pair_slot(int o) { return 32 * (o >> 5) + 2 * (o & 15) + ((o >> 4) & 1); }
 
 template <int R>
 struct MlpLds {

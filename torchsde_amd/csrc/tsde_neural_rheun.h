@@ -72,25 +72,6 @@ struct RheunArgs {
   RheunStash st;
 };
 
-__device__ __noinline__ float rheun_draw_one(NoiseKey key, uint64_t elem, uint32_t cell) {
-  return normal1<float>(key, elem, cell, 0, kStreamW);
-}
-
-// Schedule of a straight-line region of READS LDS operand reads, each feeding PER matrix instructions: the first few reads go out
-// ahead, then every group of PER MFMAs is followed by one more read (cf. mlp_general.hip: left alone, hipcc emits read -> wait ->
-// MFMAs, and with one wave per SIMD nothing else hides the LDS latency).
-template <int READS, int PER>
-TSDE_D void rheun_reads_ahead() {
-  constexpr int AHEAD = READS < 4 ? READS : 4;
-  __builtin_amdgcn_sched_group_barrier(0x100, AHEAD, 0);
-#pragma unroll
-  for (int i = 0; i < READS; ++i) {
-    __builtin_amdgcn_sched_group_barrier(0x008, PER, 0);
-    if (i < READS - AHEAD) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-  }
-  __builtin_amdgcn_sched_barrier(0);
-}
-
 // value and slope of a hidden activation / of a net's closing function
 template <int ACT>
 TSDE_D void hidden_act(float x, float c, float& value, float& slope) {
@@ -120,15 +101,6 @@ TSDE_D void final_act(float x, float& value, float& slope) {
   }
 }
 
-// LDS floats of a shape: both first layers, the hidden-to-hidden layers, both last layers, every bias
-// (the diffusion's last layer: rows padded by 8 and 32 floats of slack behind the output biases -- what the forward kernel's
-//  paired layout and its one-pair-ahead requests need, see `kPaired`; the backward kernel pads by 4 and leaves the rest unused)
-inline size_t rheun_lds_floats(int D, int H, int outp, int nmf, int nmg) {
-  const size_t S1 = H + 4;
-  return (size_t)2 * D * S1 + (size_t)(nmf + nmg) * H * S1 + (size_t)H * (D + 4) + (size_t)H * (outp + 8) + (size_t)4 * H +
-         (size_t)(nmf + nmg) * H + D + outp + 32;
-}
-
 // MODE: 0 = diagonal noise, 1 = scalar noise, else general noise with the Brownian channels padded to MODE (4 or 16).
 template <int D, int H, int MODE, bool BACKWARD>
 __global__ void __launch_bounds__(256, (!BACKWARD && D <= 32) ? 2 : 1) neural_rheun_kernel(const RheunArgs p, const int outp) {
@@ -139,11 +111,9 @@ __global__ void __launch_bounds__(256, (!BACKWARD && D <= 32) ? 2 : 1) neural_rh
   constexpr int M = kGeneral ? MODE : 1;
   constexpr int kQuads = M >= 16 ? M / 16 : 1;
   constexpr int TD = D / 16, TH = H / 16, S1 = H + 4, S2F = D + 4;
-  // general noise, forward: the two tiles of a PAIR interleaved in the diffusion's last layer -- element (unit u, output
-  // o = 16 tile + c) at u * S2G + 32 (tile / 2) + 2 c + (tile & 1), rows padded by 8 -- one ds_read_b64 per unit and pair,
-  // conflict-free (mlp_general.hip, PairLayout); the backward kernel reads the same weights transposed, four consecutive
-  // outputs at a time, and keeps them in output order. Up to 32 state channels the stride is a compile-time constant
-  // (the launcher passes outp = D * M), so every row offset is an immediate of its read.
+  // general noise, forward: the diffusion's last layer in the pair-interleaved layout, rows padded by 8 (tsde_mlp.h,
+  // PairLayout); the backward kernel reads the same weights transposed, four consecutive outputs at a time, and keeps them
+  // in output order. Up to 32 state channels the stride is a compile-time constant (the launcher passes outp = D * M).
   constexpr bool kPaired = kGeneral && !BACKWARD;
   constexpr int kPad = kPaired ? 8 : 4;
   const int S2G = (kGeneral && D <= 32) ? D * M + kPad : outp + kPad;
@@ -178,13 +148,7 @@ __global__ void __launch_bounds__(256, (!BACKWARD && D <= 32) ? 2 : 1) neural_rh
 
   const int dT = p.d, hf = p.f.hidden, hg = p.g.hidden, outT = p.g.out;
   // weights into LDS, zero-padded to the tile sizes (padded units see zero weights both ways; padded outputs are never used)
-  for (int i = threadIdx.x; i < D * H; i += 256) {
-    const int k = i / H, u = i % H;
-    W1f[k * S1 + u] = (k < dT && u < hf) ? p.f.w1[k * hf + u] : 0.0f;
-    W1g[k * S1 + u] = (k < dT && u < hg) ? p.g.w1[k * hg + u] : 0.0f;
-    const int u2 = i / D, c = i % D;
-    W2f[u2 * S2F + c] = (u2 < hf && c < dT) ? p.f.w2[u2 * dT + c] : 0.0f;
-  }
+  stage_two_nets<D, H>(p.f, p.g, dT, W1f, W1g, W2f);
 #pragma unroll
   for (int l = 0; l < kMaxMid; ++l) {
     for (int i = threadIdx.x; i < H * H; i += 256) {
@@ -199,44 +163,19 @@ __global__ void __launch_bounds__(256, (!BACKWARD && D <= 32) ? 2 : 1) neural_rh
   }
   for (int i = threadIdx.x; i < H * outp; i += 256) {
     const int u = i / outp, o = i % outp;
-    // general noise: the net's outputs are (i, j) row-major with m REAL channels; the tiles want i * M + j
-    int src = o;
-    bool have = o < outT;
-    if constexpr (kGeneral) {
-      const int ci = o / M, cj = o % M;
-      have = ci < dT && cj < p.m;
-      src = ci * p.m + cj;
-    }
-    const int at = kPaired ? 32 * (o >> 5) + 2 * (o & 15) + ((o >> 4) & 1) : o;
-    W2g[u * S2G + at] = (u < hg && have) ? p.g.w2[(int64_t)u * outT + src] : 0.0f;
+    const OutputSource from = padded_output<kGeneral>(o, M, dT, p.m, outT);
+    W2g[u * S2G + (kPaired ? pair_slot(o) : o)] = (u < hg && from.have) ? p.g.w2[(int64_t)u * outT + from.src] : 0.0f;
   }
-  for (int i = threadIdx.x; i < H; i += 256) {
-    b1f[i] = i < hf ? p.f.b1[i] : 0.0f;
-    wtf[i] = (i < hf && p.f.w1t) ? p.f.w1t[i] : 0.0f;
-    b1g[i] = i < hg ? p.g.b1[i] : 0.0f;
-    wtg[i] = (i < hg && p.g.w1t) ? p.g.w1t[i] : 0.0f;
-  }
-  for (int i = threadIdx.x; i < D; i += 256) b2f[i] = i < dT ? p.f.b2[i] : 0.0f;
+  stage_two_nets_biases<D, H>(p.f, p.g, dT, b1f, wtf, b1g, wtg, b2f);
   for (int i = threadIdx.x; i < outp; i += 256) {
-    int src = i;
-    bool have = i < outT;
-    if constexpr (kGeneral) {
-      const int ci = i / M, cj = i % M;
-      have = ci < dT && cj < p.m;
-      src = ci * p.m + cj;
-    }
-    b2g[i] = have ? p.g.b2[src] : 0.0f;
+    const OutputSource from = padded_output<kGeneral>(i, M, dT, p.m, outT);
+    b2g[i] = from.have ? p.g.b2[from.src] : 0.0f;
   }
   __syncthreads();
 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int part = lane >> 4, n = lane & 15;
-  NoiseKey key = p.key;
-  if (p.key_dev != nullptr) {
-    const uint64_t ent = *p.key_dev;
-    key.k0 = (uint32_t)ent;
-    key.k1 = (uint32_t)(ent >> 32);
-  }
+  const NoiseKey key = launch_key(p.key, p.key_dev);
   const int K = p.n_steps;
   const float f_scale = p.f.scale, g_scale = p.g.scale;
   const int64_t n_groups = (p.B + 15) / 16;
@@ -305,7 +244,7 @@ __global__ void __launch_bounds__(256, (!BACKWARD && D <= 32) ? 2 : 1) neural_rh
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
               const int cj = 4 * quad_of_row + r;
-              if (cj < p.m) z[r] = rheun_draw_one(key, key.elem0 + (uint64_t)row * (uint64_t)p.m + (uint64_t)cj, cell);
+              if (cj < p.m) z[r] = draw_one(key, key.elem0 + (uint64_t)row * (uint64_t)p.m + (uint64_t)cj, cell, kStreamW);
             }
           }
 #pragma unroll
@@ -325,7 +264,7 @@ __global__ void __launch_bounds__(256, (!BACKWARD && D <= 32) ? 2 : 1) neural_rh
           } else {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-              if (ch + r < dT) z[r] = rheun_draw_one(key, key.elem0 + (uint64_t)off_d + (uint64_t)(ch + r), cell);
+              if (ch + r < dT) z[r] = draw_one(key, key.elem0 + (uint64_t)off_d + (uint64_t)(ch + r), cell, kStreamW);
             }
           }
 #pragma unroll
@@ -709,7 +648,7 @@ __global__ void __launch_bounds__(256, (!BACKWARD && D <= 32) ? 2 : 1) neural_rh
                   }
                 }
                 __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
-                rheun_reads_ahead<TH * 2, 4>();          // (one 16-byte read feeds four MFMAs)
+                reads_ahead<TH * 2, 4>();          // (one 16-byte read feeds four MFMAs)
                 f_lo += 128;
                 f_up += 128;
                 t_lo += 128;

@@ -106,6 +106,19 @@ struct NoiseKey {
   uint64_t elem0;    // global index of this shard's element 0 in the (B_global * m) noise tensor
 };
 
+#if defined(__HIPCC__)
+// The key a kernel draws with: entropy that lives in device memory (a captured graph replayed with fresh entropy)
+// replaces the entropy the launch was given.
+TSDE_D NoiseKey launch_key(NoiseKey key, const uint64_t* key_dev) {
+  if (key_dev != nullptr) {
+    const uint64_t ent = *key_dev;
+    key.k0 = (uint32_t)ent;
+    key.k1 = (uint32_t)(ent >> 32);
+  }
+  return key;
+}
+#endif
+
 // Counter layout:
 //   c0 = quad[31:0]            quad = global element index >> 2 (4 normals per Philox call)
 //   c1 = cell                  top-level cell of the Brownian grid

@@ -228,7 +228,7 @@ __global__ void __launch_bounds__(NW * 64) mlp_adjoint_kernel(const MlpAdjArgs p
         float zn[4] = {0.0f, 0.0f, 0.0f, 0.0f};
         uint64_t quad = quad0 + 4 * t;
         asm volatile("" : "+v"(quad));          // (keeps the step-invariant first Philox round inside the loop)
-        if (real_d(t)) normal4<float>(key, quad, cell, 0, kStreamW, zn);
+        if (real_d(t)) normal4_pairs<float>(key, quad, cell, 0, kStreamW, zn);
         const f32x4 cq = lds_quad(cs, ch);
         const f32x4 eq = lds_quad(es, ch);
         const f32x4 bq = lds_quad(b2s, ch);

@@ -201,7 +201,7 @@ __global__ void __launch_bounds__(NW * 64) mlp_backward_kernel(const MlpBackArgs
       //  sweep and pinned in ~4 registers per tile)
       uint64_t quad = quad0 + 4 * t;
       asm volatile("" : "+v"(quad));
-      if (real_d(t)) normal4<float>(key, quad, cell, 0, kStreamW, zn);
+      if (real_d(t)) normal4_pairs<float>(key, quad, cell, 0, kStreamW, zn);
       const f32x4 yt = y[t];
       const f32x4 cq = lds_quad(cs, ch);
       const f32x4 eq = lds_quad(es, ch);

@@ -286,7 +286,7 @@ __global__ void __launch_bounds__(256, (MODE >= 4 || (H <= 64 && !GENERIC)) ? 2 
           asm volatile("" : "+v"(quad));
           float z[4] = {0.0f, 0.0f, 0.0f, 0.0f};
           if (p.m == M && (key.elem0 & 3) == 0) {
-            normal4<float>(key, quad, cell, 0, kStreamW, z);
+            normal4_pairs<float>(key, quad, cell, 0, kStreamW, z);
           } else {          // m not one of the tile widths (or an unaligned field): the row's REAL channels one by one
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -480,7 +480,7 @@ __global__ void __launch_bounds__(256, (MODE >= 4 || (H <= 64 && !GENERIC)) ? 2 
             uint64_t quad = (key.elem0 + (uint64_t)off_d + (uint64_t)ch) >> 2;
             asm volatile("" : "+v"(quad));
             if constexpr (noise_quads) {
-              if (real(ch)) normal4<float>(key, quad, cell, 0, kStreamW, z);
+              if (real(ch)) normal4_pairs<float>(key, quad, cell, 0, kStreamW, z);
             } else {
 #pragma unroll
               for (int r = 0; r < 4; ++r) {
@@ -558,8 +558,8 @@ __global__ void __launch_bounds__(256, (MODE >= 4 || (H <= 64 && !GENERIC)) ? 2 
           float zw[4] = {0.0f, 0.0f, 0.0f, 0.0f}, zh[4] = {0.0f, 0.0f, 0.0f, 0.0f};
           if constexpr (noise_quads) {
             if (real(ch)) {
-              normal4<float>(key, quad, cell, 0, kStreamW, zw);
-              normal4<float>(key, quad, cell, 0, kStreamH, zh);
+              normal4_pairs<float>(key, quad, cell, 0, kStreamW, zw);
+              normal4_pairs<float>(key, quad, cell, 0, kStreamH, zh);
             }
           } else {
 #pragma unroll
@@ -595,7 +595,7 @@ __global__ void __launch_bounds__(256, (MODE >= 4 || (H <= 64 && !GENERIC)) ? 2 
           asm volatile("" : "+v"(quad));
           float zw[4] = {0.0f, 0.0f, 0.0f, 0.0f};
           if constexpr (noise_quads) {
-            if (real(ch)) normal4<float>(key, quad, cell, 0, kStreamW, zw);
+            if (real(ch)) normal4_pairs<float>(key, quad, cell, 0, kStreamW, zw);
           } else {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {

@@ -290,7 +290,7 @@ __global__ void __launch_bounds__(NW * 64) mlp_trajectory_kernel(const MlpArgs p
           for (int r = 0; r < 4; ++r) acc = TL::mfma(a[r], hid[th][r], acc);
         }
         float z[4];
-        normal4<float>(key, quad, cell, 0, kStreamW, z);
+        normal4_pairs<float>(key, quad, cell, 0, kStreamW, z);
         __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);      // operand reads two ahead
 #pragma unroll
         for (int i = 0; i < TH; ++i) {
@@ -351,8 +351,8 @@ __global__ void __launch_bounds__(NW * 64) mlp_trajectory_kernel(const MlpArgs p
           uint64_t quad = quad_row + (ch >> 2);
           asm volatile("" : "+v"(quad));
           if (real(ch)) {
-            normal4<float>(key, quad, cell, 0, kStreamW, zw);
-            normal4<float>(key, quad, cell, 0, kStreamH, zh);
+            normal4_pairs<float>(key, quad, cell, 0, kStreamW, zw);
+            normal4_pairs<float>(key, quad, cell, 0, kStreamH, zh);
           }
           const f32x4 b2q = lds_quad(b2s, ch), cq = lds_quad(cs, ch), eq = lds_quad(es, ch);
 #pragma unroll
@@ -449,7 +449,7 @@ __global__ void __launch_bounds__(NW * 64) mlp_trajectory_kernel(const MlpArgs p
           //  of the step loop and pinned in ~4 registers per quad)
           uint64_t quad = quad_row + (ch >> 2);
           asm volatile("" : "+v"(quad));
-          if (real(ch)) normal4<float>(key, quad, cell, 0, kStreamW, z);
+          if (real(ch)) normal4_pairs<float>(key, quad, cell, 0, kStreamW, z);
           const f32x4 b2q = lds_quad(b2s, ch), cq = lds_quad(cs, ch), eq = lds_quad(es, ch);
           Pack<float, 4> o;
 #pragma unroll
@@ -490,7 +490,7 @@ __global__ void __launch_bounds__(NW * 64) mlp_trajectory_kernel(const MlpArgs p
           //  of the step loop and pinned in ~4 registers per quad)
           uint64_t quad = quad_row + (ch >> 2);
           asm volatile("" : "+v"(quad));
-          if (real(ch)) normal4<float>(key, quad, cell, 0, kStreamW, z);
+          if (real(ch)) normal4_pairs<float>(key, quad, cell, 0, kStreamW, z);
           const f32x4 b2q = lds_quad(b2s, ch), cq = lds_quad(cs, ch), eq = lds_quad(es, ch);
 #pragma unroll
           for (int s = 0; s < 4; ++s) {

@@ -372,8 +372,8 @@ TSDE_D void stage_noise(const GeneralArgs<T>& a, T* lds, int64_t row0, int rows)
     const uint64_t q0 = e0 >> 2, q1 = (e0 + (uint64_t)cnt + 3) >> 2;
     for (uint64_t q = q0 + threadIdx.x; q < q1; q += kBlock) {
       T n[4], hn[4] = {(T)0, (T)0, (T)0, (T)0};
-      normal4<T>(key, q, nz.cell, 0, kStreamW, n);
-      if (need_u) normal4<T>(key, q, nz.cell, 0, kStreamH, hn);
+      normal4_pairs<T>(key, q, nz.cell, 0, kStreamW, n);
+      if (need_u) normal4_pairs<T>(key, q, nz.cell, 0, kStreamH, hn);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int64_t t = (int64_t)(q * 4 + j) - (int64_t)e0;
@@ -412,11 +412,11 @@ TSDE_D void lane_weights(const GeneralArgs<T>& a, int64_t row, int lp, T (&wq)[4
     const NoiseKey key = live_key(nz);
     const uint64_t quad = (key.elem0 + (uint64_t)off) >> 2;
     T n[4];
-    normal4<T>(key, quad, nz.cell, 0, kStreamW, n);
+    normal4_pairs<T>(key, quad, nz.cell, 0, kStreamW, n);
 #pragma unroll
     for (int j = 0; j < 4; ++j) W[j] = n[j] * sw;
     if (need_u) {
-      normal4<T>(key, quad, nz.cell, 0, kStreamH, n);
+      normal4_pairs<T>(key, quad, nz.cell, 0, kStreamH, n);
 #pragma unroll
       for (int j = 0; j < 4; ++j) Uv[j] = th * ((T)0.5 * W[j] + n[j] * sh);
     }

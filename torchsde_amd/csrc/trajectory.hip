@@ -390,11 +390,12 @@ __global__ void __launch_bounds__(kBlock) trajectory_kernel(const TrajArgs<T> p)
     Pack<T, W> w, u;
     if constexpr (W == 4) {
       T z[4];
-      noise.normal4(elem >> 2, kStreamW, z);
+      if constexpr (kNeedU) noise.normal4_pairs(elem >> 2, kStreamW, z);   // (SRK: the shared series costs it a wave)
+      else noise.normal4(elem >> 2, kStreamW, z);
 #pragma unroll
       for (int q = 0; q < 4; ++q) w.v[q] = z[q] * sw;
       if constexpr (kNeedU) {
-        noise.normal4(elem >> 2, kStreamH, z);
+        noise.normal4_pairs(elem >> 2, kStreamH, z);
 #pragma unroll
         for (int q = 0; q < 4; ++q) u.v[q] = th * ((T)0.5 * w.v[q] + z[q] * sh);
       }
@@ -1262,11 +1263,12 @@ __global__ void __launch_bounds__(kBlock) trajectory_prog_additive_kernel(const 
       for (int c = 0; c < MP / 4; ++c) {
         if (4 * c < nm) {
           T z[4];
-          normal4<T>(key, (elem >> 2) + (uint64_t)c, cell, 0, kStreamW, z);
+          if constexpr (kNeedU) normal4_pairs<T>(key, (elem >> 2) + (uint64_t)c, cell, 0, kStreamW, z);   // (SRK: as above)
+          else normal4<T>(key, (elem >> 2) + (uint64_t)c, cell, 0, kStreamW, z);
 #pragma unroll
           for (int e = 0; e < 4; ++e) wv[4 * c + e] = z[e] * sw;
           if constexpr (kNeedU) {
-            normal4<T>(key, (elem >> 2) + (uint64_t)c, cell, 0, kStreamH, z);
+            normal4_pairs<T>(key, (elem >> 2) + (uint64_t)c, cell, 0, kStreamH, z);
 #pragma unroll
             for (int e = 0; e < 4; ++e) uv[4 * c + e] = th * ((T)0.5 * wv[4 * c + e] + z[e] * sh);
           }

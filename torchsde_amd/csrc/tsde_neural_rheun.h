@@ -239,7 +239,7 @@ __global__ void __launch_bounds__(256, (!BACKWARD && D <= 32) ? 2 : 1) neural_rh
           const int quad_of_row = M >= 16 ? 4 * q + part : 0;
           float z[4] = {0.0f, 0.0f, 0.0f, 0.0f};
           if (noise_quads) {
-            normal4<float>(key, quad_row + quad_of_row, cell, 0, kStreamW, z);
+            normal4_pairs<float>(key, quad_row + quad_of_row, cell, 0, kStreamW, z);
           } else {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -260,7 +260,7 @@ __global__ void __launch_bounds__(256, (!BACKWARD && D <= 32) ? 2 : 1) neural_rh
           const int ch = 16 * t + 4 * part;
           float z[4] = {0.0f, 0.0f, 0.0f, 0.0f};
           if (noise_quads) {
-            if (ch < dT) normal4<float>(key, (key.elem0 + (uint64_t)off_d + (uint64_t)ch) >> 2, cell, 0, kStreamW, z);
+            if (ch < dT) normal4_pairs<float>(key, (key.elem0 + (uint64_t)off_d + (uint64_t)ch) >> 2, cell, 0, kStreamW, z);
           } else {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {

@@ -145,10 +145,13 @@ TSDE_HD u32x4 noise_bits(const NoiseKey& key, uint64_t quad, uint32_t cell, uint
 // fp32: v_log_f32 / v_sqrt_f32 / v_sin_f32 / v_cos_f32 (the latter two take revolutions, so theta
 // needs no range reduction). Near u1 -> 1 the log is replaced by the series of -ln(1-w), w = 1-u1
 // computed exactly from ~a, so small radii keep full relative accuracy.
-TSDE_D void box_muller(uint32_t a, uint32_t b, float& n0, float& n1) {
-  const float u1 = fmaf((float)a, 0x1p-32f, 0x1p-33f);
+
+// First words at and above this take the series: u1 >= 15/16, one pair in 16.
+constexpr uint32_t kSeriesFrom = 0xF0000000u;
+
+// The small-radius value of -2 ln u1 as a function of the pair's first word.
+TSDE_D float box_muller_series(uint32_t a) {
   const float w = fmaf((float)(~a), 0x1p-32f, 0x1p-33f);
-  const float s_log = -1.3862943611198906f * __builtin_amdgcn_logf(u1);  // -2 ln2 * log2(u1)
   // Horner of 2 * (1 + w/2 + w^2/3 + w^3/4 + w^4/5 + w^5/6) with the 2 folded into the coefficients. Doubling a float is
   // exact (nothing here is near overflow or subnormal), so each coefficient is exactly twice the plain one, doubling
   // commutes with the single rounding of every fmaf, and p is bit for bit twice the plain polynomial; w * p then rounds
@@ -158,12 +161,52 @@ TSDE_D void box_muller(uint32_t a, uint32_t b, float& n0, float& n1) {
   p = fmaf(w, p, 2.0f / 3.0f);
   p = fmaf(w, p, 1.0f);
   p = fmaf(w, p, 2.0f);
-  const float s_ser = w * p;
-  const float s = (a >= 0xF0000000u) ? s_ser : s_log;
+  return w * p;
+}
+
+// -2 ln u1 on the log path.
+TSDE_D float box_muller_log(uint32_t a) {
+  const float u1 = fmaf((float)a, 0x1p-32f, 0x1p-33f);
+  return -1.3862943611198906f * __builtin_amdgcn_logf(u1);  // -2 ln2 * log2(u1)
+}
+
+// One pair (normal1 and the one-element-per-lane paths): every lane evaluates both the log and the series.
+TSDE_D void box_muller(uint32_t a, uint32_t b, float& n0, float& n1) {
+  const float s_log = box_muller_log(a);
+  const float s_ser = box_muller_series(a);
+  const float s = (a >= kSeriesFrom) ? s_ser : s_log;
   const float r = __builtin_amdgcn_sqrtf(s);
   const float t = (float)b * 0x1p-32f;
   n0 = r * __builtin_amdgcn_cosf(t);
   n1 = r * __builtin_amdgcn_sinf(t);
+}
+
+// Both pairs of one Philox call, the series evaluated once. The series value is kept for 1 pair in 16, so a lane needs
+// it for both of its pairs only 1 time in 256: the lane evaluates it on whichever pair is hot (the first if both are),
+// and the second pair of a both-hot lane is redone in a block that the wave enters only when some lane has one
+// (1 - (255/256)^64 = 22 % of the draws of a full wave). The same floats as box_muller on each pair, bit for bit, by
+// construction: a hot pair gets series(its own word) through the same operations in the same order, a cold pair its
+// log value, and the selects only choose between those.
+TSDE_D void box_muller2(const u32x4& r, float (&n)[4]) {
+  float s0 = box_muller_log(r.x);
+  float s1 = box_muller_log(r.z);
+  const bool h0 = r.x >= kSeriesFrom;
+  const bool h1 = r.z >= kSeriesFrom;
+  const float ser = box_muller_series(h0 ? r.x : r.z);
+  s0 = h0 ? ser : s0;
+  s1 = (h1 && !h0) ? ser : s1;
+  if (__builtin_expect(__builtin_amdgcn_ballot_w64(h0 && h1) != 0, 0)) {
+    asm volatile("" ::: "memory");   // keeps the block a branch: without it the compiler folds it back into selects
+    s1 = (h0 && h1) ? box_muller_series(r.z) : s1;
+  }
+  const float r0 = __builtin_amdgcn_sqrtf(s0);
+  const float r1 = __builtin_amdgcn_sqrtf(s1);
+  const float t0 = (float)r.y * 0x1p-32f;
+  const float t1 = (float)r.w * 0x1p-32f;
+  n[0] = r0 * __builtin_amdgcn_cosf(t0);
+  n[1] = r0 * __builtin_amdgcn_sinf(t0);
+  n[2] = r1 * __builtin_amdgcn_cosf(t1);
+  n[3] = r1 * __builtin_amdgcn_sinf(t1);
 }
 
 TSDE_D void box_muller(uint32_t a, uint32_t b, double& n0, double& n1) {
@@ -175,9 +218,23 @@ TSDE_D void box_muller(uint32_t a, uint32_t b, double& n0, double& n1) {
   n1 = r * s;
 }
 
+TSDE_D void box_muller2(const u32x4& r, double (&n)[4]) {
+  box_muller(r.x, r.y, n[0], n[1]);
+  box_muller(r.z, r.w, n[2], n[3]);
+}
+
 // Four standard normals of one (quad, cell, node, stream).
 template <typename T>
 TSDE_D void normal4(const NoiseKey& key, uint64_t quad, uint32_t cell, uint64_t node, uint32_t stream, T (&n)[4]) {
+  const u32x4 r = noise_bits(key, quad, cell, node, stream);
+  box_muller2(r, n);
+}
+
+// The same four normals with the series evaluated on both pairs: the entry point of callers whose register allocation the
+// branch of box_muller2 upsets (scratch, spills or a lost wave of occupancy in profiles/bm_shared_series_resource_usage_*.txt:
+// the matrix-core kernels, the general-noise step kernels and the SRK forms of the trajectory kernels).
+template <typename T>
+TSDE_D void normal4_pairs(const NoiseKey& key, uint64_t quad, uint32_t cell, uint64_t node, uint32_t stream, T (&n)[4]) {
   const u32x4 r = noise_bits(key, quad, cell, node, stream);
   box_muller(r.x, r.y, n[0], n[1]);
   box_muller(r.z, r.w, n[2], n[3]);
@@ -206,6 +263,11 @@ struct StepNoise {
   }
   template <typename T>
   TSDE_D void normal4(uint64_t quad, uint32_t stream, T (&n)[4]) const {
+    const u32x4 r = bits(quad, stream);
+    box_muller2(r, n);
+  }
+  template <typename T>
+  TSDE_D void normal4_pairs(uint64_t quad, uint32_t stream, T (&n)[4]) const {
     const u32x4 r = bits(quad, stream);
     box_muller(r.x, r.y, n[0], n[1]);
     box_muller(r.z, r.w, n[2], n[3]);

@@ -103,6 +103,59 @@ TSDE_D Dual<T> operator+(const Dual<T>& x, const Seed<T, K>& p) {
   return r;
 }
 
+// ---- what the five kernels of this file share --------------------------------------------------------------------------
+// Every kernel below is the same loop: a lane loads its elements of y0, and per step reads the step's scalars (`step_row`),
+// draws its Brownian increments (`draw_increment`), advances its state with its own model, and at the few steps that meet
+// an output time writes the outputs (`emit_outputs`). The host side is shared likewise: `traj_common` fills the common
+// arguments, `may_vec` decides on the 4-elements-per-lane form, `dispatch_method` turns the method code into a template
+// argument and `launch_lanes` launches. A kernel owns its model, its state type, how it addresses the noise field and (the
+// affine kernel) the in-place advance.
+
+// The twelve arguments every kernel takes -- `ys, y0, rows, cells, out_step, out_w, n, d, n_steps, n_out, key, key_dev` of
+// TrajArgs, ExprArgs and ProgArgs -- filled from one place. Each block declares them where it always had them: a kernel's
+// argument offsets decide how the compiler groups its scalar loads, and moving the fields into one leading sub-block changed
+// the instruction count of 224 of this file's 246 kernels (profiles/traj_skeleton_resource_usage_notes.txt). The helpers
+// below therefore take any of the three blocks.
+template <typename T, typename Args>
+static void traj_common(Args& p, void* ys, const void* y0, int64_t rows, int64_t d, const tsde_traj_t* tr, NoiseKey key,
+                        const uint64_t* key_dev) {
+  p.ys = (T*)ys;
+  p.y0 = (const T*)y0;
+  p.rows = (const T*)tr->step_rows;
+  p.cells = tr->cells;
+  p.out_step = tr->out_step;
+  p.out_w = (const T*)tr->out_w;
+  p.n = rows * d;
+  p.d = d;
+  p.n_steps = tr->n_steps;
+  p.n_out = tr->n_out;
+  p.key = key;
+  p.key_dev = key_dev;
+}
+
+// Below this many 16-byte groups the one-element-per-lane form is used even when the vector form is legal:
+// the kernel is ALU/latency bound per lane, so a half-empty chip finishes sooner with 4x the lanes.
+constexpr int64_t kTrajVecMinGroups = 256 * 8 * 64;
+
+// May a lane own 4 consecutive elements? Rows of whole 16-byte groups, the state and every `extra` table of the family
+// aligned to them (a null pointer counts as aligned), and enough groups. What a family's noise addressing or coefficient
+// tables demand on top, the family adds itself.
+template <typename Args, typename... P>
+static bool may_vec(const Args& c, const P*... extra) {
+  return (c.d % 4 == 0) && aligned16(c.ys) && aligned16(c.y0) && (aligned16(extra) && ...) &&
+         ((c.n * sizeof(*c.ys)) % 16 == 0) && (c.n >> 2) >= kTrajVecMinGroups;
+}
+
+template <typename Args>
+static bool nothing_to_do(const Args& c) { return c.n <= 0 || c.n_steps <= 0; }
+
+// One lane per W elements: `lanes` of them in blocks of kBlock.
+template <typename Args>
+static hipError_t launch_lanes(void (*kernel)(const Args), int64_t lanes, hipStream_t s, const Args& args) {
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((lanes + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, args);
+  return hipGetLastError();
+}
+
 template <typename T>
 struct TrajArgs {
   T* ys;                    // (n_out, n) outputs after t0
@@ -122,6 +175,21 @@ struct TrajArgs {
 
 enum : int { kEuler = TSDE_TRAJ_EULER, kMilIto = TSDE_TRAJ_MILSTEIN_ITO, kMilStrat = TSDE_TRAJ_MILSTEIN_STRAT,
              kMidpoint = TSDE_TRAJ_MIDPOINT, kSrk = TSDE_TRAJ_SRK, kHeun = TSDE_TRAJ_HEUN, kEulerHeun = TSDE_TRAJ_EULER_HEUN };
+
+// The method code as a template argument: `fn(std::integral_constant<int, kEuler>{})` ...
+template <typename F>
+static hipError_t dispatch_method(int method, F fn) {
+  switch (method) {
+    case kEuler: return fn(std::integral_constant<int, kEuler>{});
+    case kMilIto: return fn(std::integral_constant<int, kMilIto>{});
+    case kMilStrat: return fn(std::integral_constant<int, kMilStrat>{});
+    case kMidpoint: return fn(std::integral_constant<int, kMidpoint>{});
+    case kSrk: return fn(std::integral_constant<int, kSrk>{});
+    case kHeun: return fn(std::integral_constant<int, kHeun>{});
+    case kEulerHeun: return fn(std::integral_constant<int, kEulerHeun>{});
+    default: return hipErrorInvalidValue;
+  }
+}
 
 // One step of one element of a diagonal SDE whose drift and diffusion the kernel can evaluate itself. `w` = W, `u` = U
 // (SRK only). S is T (values only) or Dual<T>. `M` supplies f(x), g(x) and gdg(x, g, v) = (g * v) * g'(x), the
@@ -310,20 +378,117 @@ struct ExprModelTimed {
   }
 };
 
-// Step count at which output j is due, as a wave-uniform (scalar) value; -1 past the last output.
-TSDE_D int next_output_step(const int32_t* out_step, int j, int n_out) {
-  return j < n_out ? __builtin_amdgcn_readfirstlane(out_step[j]) : -1;
-}
-
-// ... read through the constant address space (`uniform_load`): the affine kernel's
-TSDE_D int next_output_uniform(const int32_t* out_step, int j, int n_out) {
-  return j < n_out ? uniform_load(out_step, j) : -1;
-}
-
 template <typename T>
 TSDE_D T primal(const T& x) { return x; }
 template <typename T>
 TSDE_D T primal(const Dual<T>& x) { return x.v; }
+
+// ---- the step loop's shared pieces ------------------------------------------------------------------------------------
+// Element i of one of a solve's host-written tables. UNIFORM: through the constant address space (`uniform_load`), as the
+// affine kernel reads them; the other kernels read them plainly.
+template <bool UNIFORM, typename X>
+TSDE_D X table_read(const X* p, int64_t i) {
+  if constexpr (UNIFORM) return uniform_load(p, i);
+  else return p[i];
+}
+
+// Step count at which output j is due, as a wave-uniform (scalar) value; -1 past the last output.
+template <bool UNIFORM>
+TSDE_D int next_output_step(const int32_t* out_step, int j, int n_out) {
+  if constexpr (UNIFORM) return j < n_out ? uniform_load(out_step, j) : -1;
+  else return j < n_out ? __builtin_amdgcn_readfirstlane(out_step[j]) : -1;
+}
+
+// The scalars of step k (a row of `rows`: what a kernel does not use costs it nothing) and its Brownian cell. The eighth
+// scalar, the time t0 the step starts at, is read on demand: only the program kernels use it, after their draws.
+template <typename T>
+struct StepRow {
+  T dt, half_dt, rdt, sqrt_dt, sw, sh, th;
+  uint32_t cell;
+  const T* row;
+  TSDE_D T t0() const { return row[7]; }
+};
+
+// `row`: the caller's `p.rows + (int64_t)k * 8` (wave-uniform: scalar loads); the TIMED kernels address their coefficient
+// rows from the same k, and the address arithmetic stays theirs.
+template <bool UNIFORM, typename T>
+TSDE_D StepRow<T> step_row(const T* row, const uint32_t* cells, int k) {
+  StepRow<T> r;
+  r.dt = table_read<UNIFORM>(row, 0);
+  r.half_dt = table_read<UNIFORM>(row, 1);
+  r.rdt = table_read<UNIFORM>(row, 2);
+  r.sqrt_dt = table_read<UNIFORM>(row, 3);
+  r.sw = table_read<UNIFORM>(row, 4);
+  r.sh = table_read<UNIFORM>(row, 5);
+  r.th = table_read<UNIFORM>(row, 6);
+  r.cell = table_read<UNIFORM>(cells, k);
+  r.row = row;
+  return r;
+}
+
+// W = z sqrt(h) and, NEED_U (SRK), U = h (W / 2 + z' sqrt(h / 12)) from standard normals z of stream W and z' of stream H,
+// for the single element `elem`.
+template <typename T, bool NEED_U, typename Noise>
+TSDE_D void draw_one(const Noise& noise, const StepRow<T>& r, uint64_t elem, T& w, T& u) {
+  w = noise.template normal1<T>(elem, kStreamW) * r.sw;
+  if constexpr (NEED_U) u = r.th * ((T)0.5 * w + noise.template normal1<T>(elem, kStreamH) * r.sh);
+}
+
+// The increments of a lane's W elements, the first of which meets element `elem` of the noise field; `u` is written only
+// when NEED_U. W = 4: one Philox quad -- PAIRS: through `normal4_pairs` in place of `normal4`, the SRK form of the affine
+// kernel, whose registers the shared series costs a wave (profiles/bm_shared_series_resource_usage_notes.txt). Otherwise
+// element by element: one element per lane, or (W = d, a generated row model: specialise.py) a lane that owns a whole ROW
+// of a small coupled system and draws its d increments one by one. `row_noise` (scalar noise): `elem` is the lane's row and
+// all W elements meet its one increment.
+template <typename T, int W, bool NEED_U, bool PAIRS, typename Noise>
+TSDE_D void draw_increment(const Noise& noise, const StepRow<T>& r, uint64_t elem, bool row_noise, T (&w)[W], T (&u)[W]) {
+  if (row_noise) {
+    T w_row, u_row;
+    draw_one<T, NEED_U>(noise, r, elem, w_row, u_row);
+#pragma unroll
+    for (int q = 0; q < W; ++q) {
+      w[q] = w_row;
+      if constexpr (NEED_U) u[q] = u_row;
+    }
+  } else if constexpr (W == 4) {
+    T z[4];
+    if constexpr (PAIRS) noise.normal4_pairs(elem >> 2, kStreamW, z);
+    else noise.normal4(elem >> 2, kStreamW, z);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) w[q] = z[q] * r.sw;
+    if constexpr (NEED_U) {
+      if constexpr (PAIRS) noise.normal4_pairs(elem >> 2, kStreamH, z);
+      else noise.normal4(elem >> 2, kStreamH, z);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) u[q] = r.th * ((T)0.5 * w[q] + z[q] * r.sh);
+    }
+  } else {
+#pragma unroll
+    for (int q = 0; q < W; ++q) draw_one<T, NEED_U>(noise, r, elem + (uint64_t)q, w[q], u[q]);
+  }
+}
+
+// The outputs due once step k is complete: the cold block of the loop, entered when `k + 1 == next_out` (the step count of
+// the next output lives in a scalar register: a step that is not an output time -- all but a few of them -- pays one scalar
+// compare). `p`: the kernel's argument block; `y_old`, `y_new`: the lane's W elements (from index i) at the start and at the end
+// of the step -- an output time inside the step interpolates between them. Advances `j` past the outputs written and `next_out`
+// to the step count of the next one. Values only: the two sites whose state is a dual number (the SENS form of the affine
+// kernel, `trajectory_prog_sens_kernel`) keep this block written out with their tangent planes -- through a function their
+// register allocation came out wider, a wave of occupancy for the float64 forms.
+template <bool UNIFORM, int W, typename Args, typename T>
+TSDE_D void emit_outputs(const Args& p, int64_t i, int k, int& j, int& next_out, const T* y_old, const T* y_new) {
+  if (!__builtin_expect(k + 1 == next_out, 0)) return;
+  while (j < p.n_out && table_read<UNIFORM>(p.out_step, j) == k + 1) {
+    const T w0 = table_read<UNIFORM>(p.out_w, 2 * j), w1 = table_read<UNIFORM>(p.out_w, 2 * j + 1);
+    const bool exact = (w0 == (T)0 && w1 == (T)1);
+    Pack<T, W> ov;
+#pragma unroll
+    for (int q = 0; q < W; ++q) ov.v[q] = exact ? y_new[q] : (w0 * y_old[q] + w1 * y_new[q]);
+    store<T, W>(p.ys + (int64_t)j * p.n, i, ov);
+    ++j;
+  }
+  next_out = next_output_step<UNIFORM>(p.out_step, j, p.n_out);
+}
 
 // W = 4: a lane owns one 16-byte group (needs d % 4 == 0 so the group stays inside one row).
 // W = 1: a lane owns one element (any d; also used for small problems, where it exposes 4x the lanes).
@@ -368,12 +533,9 @@ __global__ void __launch_bounds__(kBlock) trajectory_kernel(const TrajArgs<T> p)
   }
   const uint64_t elem = key.elem0 + (uint64_t)i;
   int j = 0;
-  int next_out = next_output_uniform(p.out_step, 0, p.n_out);
+  int next_out = next_output_step<true>(p.out_step, 0, p.n_out);
   for (int k = 0; k < p.n_steps; ++k) {
-    const T* row = p.rows + (int64_t)k * 8;   // wave-uniform: scalar loads
-    const T dt = uniform_load(row, 0), half_dt = uniform_load(row, 1), rdt = uniform_load(row, 2),
-            sqrt_dt = uniform_load(row, 3), sw = uniform_load(row, 4), sh = uniform_load(row, 5), th = uniform_load(row, 6);
-    const uint32_t cell = uniform_load(p.cells, k);
+    const StepRow<T> r = step_row<true>(p.rows + (int64_t)k * 8, p.cells, k);
     constexpr int NS = stage_slots<METHOD>();
     Pack<T, W> ta[NS], tb[NS], tc[NS], te[NS];      // TIMED: the coefficient rows of this step's stage times
     if constexpr (TIMED) {
@@ -386,28 +548,14 @@ __global__ void __launch_bounds__(kBlock) trajectory_kernel(const TrajArgs<T> p)
         te[sl] = load<T, W>(p.e, at);
       }
     }
-    const StepNoise noise(key, cell);               // (the uniform head of this step's Philox calls: scalar unit)
+    const StepNoise noise(key, r.cell);             // (the uniform head of this step's Philox calls: scalar unit)
     Pack<T, W> w, u;
-    if constexpr (W == 4) {
-      T z[4];
-      if constexpr (kNeedU) noise.normal4_pairs(elem >> 2, kStreamW, z);   // (SRK: the shared series costs it a wave)
-      else noise.normal4(elem >> 2, kStreamW, z);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) w.v[q] = z[q] * sw;
-      if constexpr (kNeedU) {
-        noise.normal4_pairs(elem >> 2, kStreamH, z);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) u.v[q] = th * ((T)0.5 * w.v[q] + z[q] * sh);
-      }
-    } else {
-      w.v[0] = noise.template normal1<T>(elem, kStreamW) * sw;
-      if constexpr (kNeedU) u.v[0] = th * ((T)0.5 * w.v[0] + noise.template normal1<T>(elem, kStreamH) * sh);
-    }
+    draw_increment<T, W, kNeedU, /*PAIRS=*/kNeedU>(noise, r, elem, false, w.v, u.v);   // (SRK: the shared series costs it a wave)
     // Values-only kernels with constant coefficients advance the state IN PLACE: a step that ends at or after an output
     // time -- all but a few do not -- first sets the state it starts from aside (the interpolation inside a step needs both
     // ends) in a cold block, and the hot loop has no register copies at its latch. The others (dual numbers, coefficient
     // rows: wide states, where the copy's registers cost occupancy) keep both states and copy at the latch.
-    const bool due = k + 1 == next_out;
+    const bool due = k + 1 == next_out;   // (also what `emit_outputs` tests after the step)
     S y1[W];
     if constexpr (kInPlace) {
       if (__builtin_expect(due, 0)) {
@@ -429,7 +577,7 @@ __global__ void __launch_bounds__(kBlock) trajectory_kernel(const TrajArgs<T> p)
           m.c[sl] = tc[sl].v[q];
           m.e[sl] = te[sl].v[q];
         }
-        y_new[q] = scheme_step<T, METHOD, S>(y[q], m, w.v[q], kNeedU ? u.v[q] : (T)0, dt, half_dt, rdt, sqrt_dt);
+        y_new[q] = scheme_step<T, METHOD, S>(y[q], m, w.v[q], kNeedU ? u.v[q] : (T)0, r.dt, r.half_dt, r.rdt, r.sqrt_dt);
       } else {
         B bq;
         E eq;
@@ -438,33 +586,33 @@ __global__ void __launch_bounds__(kBlock) trajectory_kernel(const TrajArgs<T> p)
           eq = E{e.v[q]};
         }
         y_new[q] = affine_step<T, METHOD, S, A, B, C, E>(y[q], A{a.v[q]}, bq, C{c.v[q]}, eq, w.v[q],
-                                                          kNeedU ? u.v[q] : (T)0, dt, half_dt, rdt, sqrt_dt);
+                                                          kNeedU ? u.v[q] : (T)0, r.dt, r.half_dt, r.rdt, r.sqrt_dt);
       }
     }
-    // (the step count of the next output lives in a scalar register: a step that is not an output time -- all but a few
-    //  of them -- pays one scalar compare, and the output code is a cold block of its own)
-    if (__builtin_expect(due, 0)) {
-      while (j < p.n_out && uniform_load(p.out_step, j) == k + 1) {
-        const T w0 = uniform_load(p.out_w, 2 * j), w1 = uniform_load(p.out_w, 2 * j + 1);
-        const bool exact = (w0 == (T)0 && w1 == (T)1);
-        S o[W];
+    if constexpr (SENS) {
+      if (__builtin_expect(due, 0)) {
+        while (j < p.n_out && uniform_load(p.out_step, j) == k + 1) {
+          const T w0 = uniform_load(p.out_w, 2 * j), w1 = uniform_load(p.out_w, 2 * j + 1);
+          const bool exact = (w0 == (T)0 && w1 == (T)1);
+          S o[W];
 #pragma unroll
-        for (int q = 0; q < W; ++q) o[q] = exact ? y_new[q] : (w0 * y_old[q] + w1 * y_new[q]);
-        Pack<T, W> ov;
+          for (int q = 0; q < W; ++q) o[q] = exact ? y_new[q] : (w0 * y_old[q] + w1 * y_new[q]);
+          Pack<T, W> ov;
 #pragma unroll
-        for (int q = 0; q < W; ++q) ov.v[q] = primal<T>(o[q]);
-        store<T, W>(p.ys + (int64_t)j * p.n, i, ov);
-        if constexpr (SENS) {
+          for (int q = 0; q < W; ++q) ov.v[q] = primal<T>(o[q]);
+          store<T, W>(p.ys + (int64_t)j * p.n, i, ov);
 #pragma unroll
           for (int s = 0; s < kSens; ++s) {
 #pragma unroll
             for (int q = 0; q < W; ++q) ov.v[q] = o[q].d[s];
             store<T, W>(p.sens + ((int64_t)j * kSens + s) * p.n, i, ov);
           }
+          ++j;
         }
-        ++j;
+        next_out = next_output_step<true>(p.out_step, j, p.n_out);
       }
-      next_out = next_output_uniform(p.out_step, j, p.n_out);
+    } else {
+      emit_outputs<true, W>(p, i, k, j, next_out, y_old, y_new);   // (tests `due` itself: next_out is unchanged since)
     }
     if constexpr (!kInPlace) {
 #pragma unroll
@@ -473,89 +621,44 @@ __global__ void __launch_bounds__(kBlock) trajectory_kernel(const TrajArgs<T> p)
   }
 }
 
-template <typename T, int METHOD, bool SENS, bool LINEAR = false>
-static hipError_t launch_traj_ms(const TrajArgs<T>& p, bool vec, hipStream_t s) {
-  if (vec) {
-    const int64_t lanes = p.n >> 2;
-    hipLaunchKernelGGL((trajectory_kernel<T, METHOD, 4, SENS, false, LINEAR>),
-                       dim3((unsigned)((lanes + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, p);
-  } else {
-    hipLaunchKernelGGL((trajectory_kernel<T, METHOD, 1, SENS, false, LINEAR>),
-                       dim3((unsigned)((p.n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, p);
-  }
-  return hipGetLastError();
-}
-
-template <typename T, int METHOD>
-static hipError_t launch_traj_timed(const TrajArgs<T>& p, bool vec, hipStream_t s) {
-  if (vec) {
-    const int64_t lanes = p.n >> 2;
-    hipLaunchKernelGGL((trajectory_kernel<T, METHOD, 4, false, true>), dim3((unsigned)((lanes + kBlock - 1) / kBlock)),
-                       dim3(kBlock), 0, s, p);
-  } else {
-    hipLaunchKernelGGL((trajectory_kernel<T, METHOD, 1, false, true>), dim3((unsigned)((p.n + kBlock - 1) / kBlock)),
-                       dim3(kBlock), 0, s, p);
-  }
-  return hipGetLastError();
+template <typename T, int METHOD, bool SENS, bool TIMED = false, bool LINEAR = false>
+static hipError_t launch_traj_form(const TrajArgs<T>& p, bool vec, hipStream_t s) {
+  if (vec) return launch_lanes(trajectory_kernel<T, METHOD, 4, SENS, TIMED, LINEAR>, p.n >> 2, s, p);
+  return launch_lanes(trajectory_kernel<T, METHOD, 1, SENS, TIMED, LINEAR>, p.n, s, p);
 }
 
 template <typename T, int METHOD>
 static hipError_t launch_traj_m(const TrajArgs<T>& p, bool vec, hipStream_t s) {
   if (p.cstride != 0) {            // coefficient tables (values only)
     if (p.sens) return hipErrorNotSupported;
-    return launch_traj_timed<T, METHOD>(p, vec, s);
+    return launch_traj_form<T, METHOD, false, true>(p, vec, s);
   }
   if (p.b == nullptr && p.e == nullptr) {   // both shifts zero: the linear form (values only)
     if (p.sens) return hipErrorNotSupported;
-    return launch_traj_ms<T, METHOD, false, true>(p, vec, s);
+    return launch_traj_form<T, METHOD, false, false, true>(p, vec, s);
   }
-  return p.sens ? launch_traj_ms<T, METHOD, true>(p, vec, s) : launch_traj_ms<T, METHOD, false>(p, vec, s);
+  return p.sens ? launch_traj_form<T, METHOD, true>(p, vec, s) : launch_traj_form<T, METHOD, false>(p, vec, s);
 }
-
-// Below this many 16-byte groups the one-element-per-lane form is used even when the vector form is legal:
-// the kernel is ALU/latency bound per lane, so a half-empty chip finishes sooner with 4x the lanes.
-constexpr int64_t kTrajVecMinGroups = 256 * 8 * 64;
 
 template <typename T>
 hipError_t launch_trajectory_affine_diag(void* ys, void* sens, const void* y0, int64_t rows, int64_t d, const void* a,
                                          const void* b, const void* c, const void* e, int64_t cstride, int method,
                                          const tsde_traj_t* tr, NoiseKey key, const uint64_t* key_dev, hipStream_t s) {
   TrajArgs<T> p;
-  p.cstride = cstride;
-  p.ys = (T*)ys;
+  traj_common<T>(p, ys, y0, rows, d, tr, key, key_dev);
   p.sens = (T*)sens;
-  p.y0 = (const T*)y0;
   p.a = (const T*)a;
   p.b = (const T*)b;
   p.c = (const T*)c;
   p.e = (const T*)e;
-  p.rows = (const T*)tr->step_rows;
-  p.cells = tr->cells;
-  p.out_step = tr->out_step;
-  p.out_w = (const T*)tr->out_w;
-  p.n = rows * d;
-  p.d = d;
-  p.n_steps = tr->n_steps;
-  p.n_out = tr->n_out;
-  p.key = key;
-  p.key_dev = key_dev;
+  p.cstride = cstride;
   if ((b == nullptr) != (e == nullptr)) return hipErrorInvalidValue;   // the linear form takes BOTH shifts as null
   if (b == nullptr && (cstride != 0 || sens)) return hipErrorInvalidValue;
-  if (p.n <= 0 || p.n_steps <= 0) return hipSuccess;
-  const bool can_vec = (d % 4 == 0) && (key.elem0 % 4 == 0) && aligned16(ys) && aligned16(y0) && aligned16(a) &&
-                       aligned16(b) && aligned16(c) && aligned16(e) && ((p.n * sizeof(T)) % 16 == 0) &&
-                       (!sens || aligned16(sens)) && (cstride % 4 == 0);
-  const bool vec = can_vec && (p.n >> 2) >= kTrajVecMinGroups;
-  switch (method) {
-    case kEuler: return launch_traj_m<T, kEuler>(p, vec, s);
-    case kMilIto: return launch_traj_m<T, kMilIto>(p, vec, s);
-    case kMilStrat: return launch_traj_m<T, kMilStrat>(p, vec, s);
-    case kMidpoint: return launch_traj_m<T, kMidpoint>(p, vec, s);
-    case kSrk: return launch_traj_m<T, kSrk>(p, vec, s);
-    case kHeun: return launch_traj_m<T, kHeun>(p, vec, s);
-    case kEulerHeun: return launch_traj_m<T, kEulerHeun>(p, vec, s);
-    default: return hipErrorInvalidValue;
-  }
+  if (nothing_to_do(p)) return hipSuccess;
+  const bool vec = may_vec(p, p.a, p.b, p.c, p.e, p.sens) &&
+                   (key.elem0 % 4 == 0) &&   // diagonal noise: a lane's 4 elements are one Philox quad
+                   (cstride % 4 == 0);       // coefficient tables: every row starts on a 16-byte group
+  return dispatch_method(method, [&](auto m) { return launch_traj_m<T, decltype(m)::value>(p, vec, s); });
 }
 
 template <typename T>
@@ -593,11 +696,9 @@ __global__ void __launch_bounds__(kBlock) trajectory_expr_kernel(const ExprArgs<
   const NoiseKey key = launch_key(p.key, p.key_dev);
   const uint64_t elem = key.elem0 + (uint64_t)i;
   int j = 0;
-  int next_out = next_output_step(p.out_step, 0, p.n_out);
+  int next_out = next_output_step<false>(p.out_step, 0, p.n_out);
   for (int k = 0; k < p.n_steps; ++k) {
-    const T* row = p.rows + (int64_t)k * 8;   // wave-uniform
-    const T dt = row[0], half_dt = row[1], rdt = row[2], sqrt_dt = row[3], sw = row[4], sh = row[5], th = row[6];
-    const uint32_t cell = p.cells[k];
+    const StepRow<T> r = step_row<false>(p.rows + (int64_t)k * 8, p.cells, k);
     constexpr int NS = stage_slots<METHOD>();
     Pack<T, W> tcf[NS][8];                          // TIMED: the coefficient rows of this step's stage times
     if constexpr (TIMED) {
@@ -609,20 +710,7 @@ __global__ void __launch_bounds__(kBlock) trajectory_expr_kernel(const ExprArgs<
       }
     }
     Pack<T, W> w, u;
-    if constexpr (W == 4) {
-      T z[4];
-      normal4<T>(key, elem >> 2, cell, 0, kStreamW, z);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) w.v[q] = z[q] * sw;
-      if constexpr (kNeedU) {
-        normal4<T>(key, elem >> 2, cell, 0, kStreamH, z);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) u.v[q] = th * ((T)0.5 * w.v[q] + z[q] * sh);
-      }
-    } else {
-      w.v[0] = normal1<T>(key, elem, cell, 0, kStreamW) * sw;
-      if constexpr (kNeedU) u.v[0] = th * ((T)0.5 * w.v[0] + normal1<T>(key, elem, cell, 0, kStreamH) * sh);
-    }
+    draw_increment<T, W, kNeedU, /*PAIRS=*/false>(PlainStepNoise(key, r.cell), r, elem, false, w.v, u.v);
     T y1[W];
 #pragma unroll
     for (int q = 0; q < W; ++q) {
@@ -635,25 +723,14 @@ __global__ void __launch_bounds__(kBlock) trajectory_expr_kernel(const ExprArgs<
         }
         m.fk = p.f_kind;
         m.gk = p.g_kind;
-        y1[q] = scheme_step<T, METHOD, T>(y[q], m, w.v[q], kNeedU ? u.v[q] : (T)0, dt, half_dt, rdt, sqrt_dt);
+        y1[q] = scheme_step<T, METHOD, T>(y[q], m, w.v[q], kNeedU ? u.v[q] : (T)0, r.dt, r.half_dt, r.rdt, r.sqrt_dt);
       } else {
         const ExprModel<T> m{cf[0].v[q], cf[1].v[q], cf[2].v[q], cf[3].v[q], cf[4].v[q], cf[5].v[q],
                              cf[6].v[q], cf[7].v[q], p.f_kind,  p.g_kind};
-        y1[q] = scheme_step<T, METHOD, T>(y[q], m, w.v[q], kNeedU ? u.v[q] : (T)0, dt, half_dt, rdt, sqrt_dt);
+        y1[q] = scheme_step<T, METHOD, T>(y[q], m, w.v[q], kNeedU ? u.v[q] : (T)0, r.dt, r.half_dt, r.rdt, r.sqrt_dt);
       }
     }
-    if (__builtin_expect(k + 1 == next_out, 0)) {
-      while (j < p.n_out && p.out_step[j] == k + 1) {
-        const T w0 = p.out_w[2 * j], w1 = p.out_w[2 * j + 1];
-        const bool exact = (w0 == (T)0 && w1 == (T)1);
-        Pack<T, W> ov;
-#pragma unroll
-        for (int q = 0; q < W; ++q) ov.v[q] = exact ? y1[q] : (w0 * y[q] + w1 * y1[q]);
-        store<T, W>(p.ys + (int64_t)j * p.n, i, ov);
-        ++j;
-      }
-      next_out = next_output_step(p.out_step, j, p.n_out);
-    }
+    emit_outputs<false, W>(p, i, k, j, next_out, y, y1);
 #pragma unroll
     for (int q = 0; q < W; ++q) y[q] = y1[q];
   }
@@ -663,25 +740,11 @@ template <typename T, int METHOD>
 static hipError_t launch_expr_m(const ExprArgs<T>& p, bool vec, hipStream_t s) {
   if (p.cstride != 0) {
     // (SRK holds 4 slots x 8 coefficients per element: one element per lane keeps that in registers)
-    if (vec && METHOD != kSrk) {
-      const int64_t lanes = p.n >> 2;
-      hipLaunchKernelGGL((trajectory_expr_kernel<T, METHOD, 4, true>), dim3((unsigned)((lanes + kBlock - 1) / kBlock)),
-                         dim3(kBlock), 0, s, p);
-    } else {
-      hipLaunchKernelGGL((trajectory_expr_kernel<T, METHOD, 1, true>), dim3((unsigned)((p.n + kBlock - 1) / kBlock)),
-                         dim3(kBlock), 0, s, p);
-    }
-    return hipGetLastError();
+    if (vec && METHOD != kSrk) return launch_lanes(trajectory_expr_kernel<T, METHOD, 4, true>, p.n >> 2, s, p);
+    return launch_lanes(trajectory_expr_kernel<T, METHOD, 1, true>, p.n, s, p);
   }
-  if (vec) {
-    const int64_t lanes = p.n >> 2;
-    hipLaunchKernelGGL((trajectory_expr_kernel<T, METHOD, 4>), dim3((unsigned)((lanes + kBlock - 1) / kBlock)),
-                       dim3(kBlock), 0, s, p);
-  } else {
-    hipLaunchKernelGGL((trajectory_expr_kernel<T, METHOD, 1>), dim3((unsigned)((p.n + kBlock - 1) / kBlock)),
-                       dim3(kBlock), 0, s, p);
-  }
-  return hipGetLastError();
+  if (vec) return launch_lanes(trajectory_expr_kernel<T, METHOD, 4>, p.n >> 2, s, p);
+  return launch_lanes(trajectory_expr_kernel<T, METHOD, 1>, p.n, s, p);
 }
 
 template <typename T>
@@ -689,40 +752,16 @@ hipError_t launch_trajectory_expr_diag(void* ys, const void* y0, int64_t rows, i
                                        int64_t cstride, int f_kind, int g_kind, int method, const tsde_traj_t* tr,
                                        NoiseKey key, const uint64_t* key_dev, hipStream_t s) {
   ExprArgs<T> p;
+  traj_common<T>(p, ys, y0, rows, d, tr, key, key_dev);
+  for (int c = 0; c < 8; ++c) p.coef[c] = (const T*)coef[c];
   p.cstride = cstride;
-  p.ys = (T*)ys;
-  p.y0 = (const T*)y0;
-  bool aligned = aligned16(ys) && aligned16(y0);
-  for (int c = 0; c < 8; ++c) {
-    p.coef[c] = (const T*)coef[c];
-    aligned = aligned && aligned16(coef[c]);
-  }
   p.f_kind = f_kind;
   p.g_kind = g_kind;
-  p.rows = (const T*)tr->step_rows;
-  p.cells = tr->cells;
-  p.out_step = tr->out_step;
-  p.out_w = (const T*)tr->out_w;
-  p.n = rows * d;
-  p.d = d;
-  p.n_steps = tr->n_steps;
-  p.n_out = tr->n_out;
-  p.key = key;
-  p.key_dev = key_dev;
-  if (p.n <= 0 || p.n_steps <= 0) return hipSuccess;
-  const bool can_vec = (d % 4 == 0) && (key.elem0 % 4 == 0) && aligned && ((p.n * sizeof(T)) % 16 == 0) &&
-                       (cstride % 4 == 0);
-  const bool vec = can_vec && (p.n >> 2) >= kTrajVecMinGroups;
-  switch (method) {
-    case kEuler: return launch_expr_m<T, kEuler>(p, vec, s);
-    case kMilIto: return launch_expr_m<T, kMilIto>(p, vec, s);
-    case kMilStrat: return launch_expr_m<T, kMilStrat>(p, vec, s);
-    case kMidpoint: return launch_expr_m<T, kMidpoint>(p, vec, s);
-    case kSrk: return launch_expr_m<T, kSrk>(p, vec, s);
-    case kHeun: return launch_expr_m<T, kHeun>(p, vec, s);
-    case kEulerHeun: return launch_expr_m<T, kEulerHeun>(p, vec, s);
-    default: return hipErrorInvalidValue;
-  }
+  if (nothing_to_do(p)) return hipSuccess;
+  const bool vec = may_vec(p, p.coef[0], p.coef[1], p.coef[2], p.coef[3], p.coef[4], p.coef[5], p.coef[6], p.coef[7]) &&
+                   (key.elem0 % 4 == 0) &&   // diagonal noise: a lane's 4 elements are one Philox quad
+                   (cstride % 4 == 0);       // coefficient tables: every row starts on a 16-byte group
+  return dispatch_method(method, [&](auto m) { return launch_expr_m<T, decltype(m)::value>(p, vec, s); });
 }
 
 // ---- expression PROGRAMS ------------------------------------------------------------------------------------------------
@@ -968,49 +1007,14 @@ __global__ void __launch_bounds__(kBlock) trajectory_prog_kernel(const ProgArgs<
   const bool scalar_noise = p.scalar_noise != 0;
   const uint64_t elem = key.elem0 + (uint64_t)(scalar_noise ? i / p.d : i);
   int j = 0;
-  int next_out = next_output_step(p.out_step, 0, p.n_out);
+  int next_out = next_output_step<false>(p.out_step, 0, p.n_out);
   for (int k = 0; k < p.n_steps; ++k) {
-    const T* row = p.rows + (int64_t)k * 8;   // wave-uniform
-    const T dt = row[0], half_dt = row[1], rdt = row[2], sqrt_dt = row[3], sw = row[4], sh = row[5], th = row[6];
-    const uint32_t cell = p.cells[k];
+    const StepRow<T> r = step_row<false>(p.rows + (int64_t)k * 8, p.cells, k);
     V w((T)0), u((T)0);
-    if (scalar_noise) {
-      const T w_row = normal1<T>(key, elem, cell, 0, kStreamW) * sw;
-      w = V(w_row);
-      if constexpr (kNeedU) u = V(th * ((T)0.5 * w_row + normal1<T>(key, elem, cell, 0, kStreamH) * sh));
-    } else if constexpr (W == 4) {
-      T z[4];
-      normal4<T>(key, elem >> 2, cell, 0, kStreamW, z);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) w.v[q] = z[q] * sw;
-      if constexpr (kNeedU) {
-        normal4<T>(key, elem >> 2, cell, 0, kStreamH, z);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) u.v[q] = th * ((T)0.5 * w.v[q] + z[q] * sh);
-      }
-    } else {
-      // one element per lane -- or (W = d, a generated row model: specialise.py) a lane that owns a whole ROW of a small
-      // coupled system and draws its d increments one by one
-#pragma unroll
-      for (int q = 0; q < W; ++q) {
-        w.v[q] = normal1<T>(key, elem + (uint64_t)q, cell, 0, kStreamW) * sw;
-        if constexpr (kNeedU) u.v[q] = th * ((T)0.5 * w.v[q] + normal1<T>(key, elem + (uint64_t)q, cell, 0, kStreamH) * sh);
-      }
-    }
-    stage_times<T, METHOD>(row[7], dt, m.tslot);
-    const V y1 = scheme_step<T, METHOD, V, M, V>(y, m, w, u, dt, half_dt, rdt, sqrt_dt);
-    if (__builtin_expect(k + 1 == next_out, 0)) {
-      while (j < p.n_out && p.out_step[j] == k + 1) {
-        const T w0 = p.out_w[2 * j], w1 = p.out_w[2 * j + 1];
-        const bool exact = (w0 == (T)0 && w1 == (T)1);
-        Pack<T, W> ov;
-#pragma unroll
-        for (int q = 0; q < W; ++q) ov.v[q] = exact ? y1.v[q] : (w0 * y.v[q] + w1 * y1.v[q]);
-        store<T, W>(p.ys + (int64_t)j * p.n, i, ov);
-        ++j;
-      }
-      next_out = next_output_step(p.out_step, j, p.n_out);
-    }
+    draw_increment<T, W, kNeedU, /*PAIRS=*/false>(PlainStepNoise(key, r.cell), r, elem, scalar_noise, w.v, u.v);
+    stage_times<T, METHOD>(r.t0(), r.dt, m.tslot);
+    const V y1 = scheme_step<T, METHOD, V, M, V>(y, m, w, u, r.dt, r.half_dt, r.rdt, r.sqrt_dt);
+    emit_outputs<false, W>(p, i, k, j, next_out, y.v, y1.v);
     y = y1;
   }
 }
@@ -1186,16 +1190,13 @@ __global__ void __launch_bounds__(kBlock) trajectory_prog_sens_kernel(const Prog
   const NoiseKey key = launch_key(p.key, p.key_dev);
   const uint64_t elem = key.elem0 + (uint64_t)(p.scalar_noise ? i / p.d : i);
   int j = 0;
-  int next_out = next_output_step(p.out_step, 0, p.n_out);
+  int next_out = next_output_step<false>(p.out_step, 0, p.n_out);
   for (int k = 0; k < p.n_steps; ++k) {
-    const T* row = p.rows + (int64_t)k * 8;
-    const T dt = row[0], half_dt = row[1], rdt = row[2], sqrt_dt = row[3], sw = row[4], sh = row[5], th = row[6];
-    const uint32_t cell = p.cells[k];
-    const T w = normal1<T>(key, elem, cell, 0, kStreamW) * sw;
-    T u = (T)0;
-    if constexpr (kNeedU) u = th * ((T)0.5 * w + normal1<T>(key, elem, cell, 0, kStreamH) * sh);
-    stage_times<T, METHOD>(row[7], dt, m.tslot);
-    const S y1 = scheme_step<T, METHOD, S, M>(y, m, w, u, dt, half_dt, rdt, sqrt_dt);
+    const StepRow<T> r = step_row<false>(p.rows + (int64_t)k * 8, p.cells, k);
+    T w[1], u[1] = {(T)0};   // (scalar noise: `elem` is the row, and one element meets one increment either way)
+    draw_increment<T, 1, kNeedU, /*PAIRS=*/false>(PlainStepNoise(key, r.cell), r, elem, false, w, u);
+    stage_times<T, METHOD>(r.t0(), r.dt, m.tslot);
+    const S y1 = scheme_step<T, METHOD, S, M>(y, m, w[0], u[0], r.dt, r.half_dt, r.rdt, r.sqrt_dt);
     if (__builtin_expect(k + 1 == next_out, 0)) {
       while (j < p.n_out && p.out_step[j] == k + 1) {
         const T w0 = p.out_w[2 * j], w1 = p.out_w[2 * j + 1];
@@ -1206,7 +1207,7 @@ __global__ void __launch_bounds__(kBlock) trajectory_prog_sens_kernel(const Prog
         for (int s = 0; s < kSens; ++s) q.sens[((int64_t)j * kSens + s) * p.n + i] = o.d[s];
         ++j;
       }
-      next_out = next_output_step(p.out_step, j, p.n_out);
+      next_out = next_output_step<false>(p.out_step, j, p.n_out);
     }
     y = y1;
   }
@@ -1250,7 +1251,7 @@ __global__ void __launch_bounds__(kBlock) trajectory_prog_additive_kernel(const 
   const int nm = q.m;
   const uint64_t elem = key.elem0 + (uint64_t)(i / p.d) * (uint64_t)nm;      // the row's first Brownian channel
   int j = 0;
-  int next_out = next_output_step(p.out_step, 0, p.n_out);
+  int next_out = next_output_step<false>(p.out_step, 0, p.n_out);
   for (int k = 0; k < p.n_steps; ++k) {
     const T* row = p.rows + (int64_t)k * 8;   // wave-uniform
     const T dt = row[0], half_dt = row[1], rdt = row[2], sw = row[4], sh = row[5], th = row[6], t0 = row[7];
@@ -1326,7 +1327,7 @@ __global__ void __launch_bounds__(kBlock) trajectory_prog_additive_kernel(const 
         store<T, W>(p.ys + (int64_t)j * p.n, i, ov);
         ++j;
       }
-      next_out = next_output_step(p.out_step, j, p.n_out);
+      next_out = next_output_step<false>(p.out_step, j, p.n_out);
     }
     y = y1;
   }
@@ -1351,24 +1352,13 @@ static ProgArgs<T> prog_args(void* ys, const void* y0, int64_t rows, int64_t d, 
                              int scalar_noise, const tsde_traj_t* tr, NoiseKey key, const uint64_t* key_dev,
                              const uint32_t* code = nullptr, int f_len = 0, int g_len = 0, int dg_len = 0) {
   ProgArgs<T> p;
-  p.ys = (T*)ys;
-  p.y0 = (const T*)y0;
+  traj_common<T>(p, ys, y0, rows, d, tr, key, key_dev);
   p.consts = (const T*)consts;
   p.f_len = f_len;
   p.g_len = g_len;
   p.dg_len = dg_len;
   p.n_const = n_const;
   p.scalar_noise = scalar_noise;
-  p.rows = (const T*)tr->step_rows;
-  p.cells = tr->cells;
-  p.out_step = tr->out_step;
-  p.out_w = (const T*)tr->out_w;
-  p.n = rows * d;
-  p.d = d;
-  p.n_steps = tr->n_steps;
-  p.n_out = tr->n_out;
-  p.key = key;
-  p.key_dev = key_dev;
   for (int w = 0; w < kProgWords; ++w) p.code[w] = (code && w < f_len + g_len + dg_len) ? code[w] : 0u;
   return p;
 }
@@ -1397,56 +1387,34 @@ static ProgAdditiveArgs<T> prog_additive_args(const ProgArgs<T>& base, int64_t m
   return q;
 }
 
-// May a lane own 4 consecutive elements? (Scalar noise addresses the field by row: no alignment condition on elem0.)
-template <typename T>
-static bool prog_may_vec(const ProgArgs<T>& p) {
-  return (p.d % 4 == 0) && (p.scalar_noise || p.key.elem0 % 4 == 0) && aligned16(p.ys) && aligned16(p.y0) &&
-         ((p.n * sizeof(T)) % 16 == 0) && (p.n >> 2) >= kTrajVecMinGroups;
-}
-
-template <typename T>
-static bool prog_additive_may_vec(const ProgAdditiveArgs<T>& q) {
-  const ProgArgs<T>& p = q.base;
-  return (p.d % 4 == 0) && aligned16(p.ys) && aligned16(p.y0) && aligned16(q.gtab) && ((p.n * sizeof(T)) % 16 == 0) &&
-         (p.n >> 2) >= kTrajVecMinGroups;
-}
-
 // One lane per W elements (W = d: per row, the row-coupled systems of specialise.source_rows). An empty problem launches nothing.
 template <typename T, int METHOD, int W, typename M = ProgModel<T, W>>
 static hipError_t launch_prog_w(const ProgArgs<T>& p, hipStream_t s) {
-  if (p.n <= 0 || p.n_steps <= 0) return hipSuccess;
-  hipLaunchKernelGGL((trajectory_prog_kernel<T, METHOD, W, M>), dim3((unsigned)((p.n / W + kBlock - 1) / kBlock)), dim3(kBlock),
-                     0, s, p);
-  return hipGetLastError();
+  if (nothing_to_do(p)) return hipSuccess;
+  return launch_lanes(trajectory_prog_kernel<T, METHOD, W, M>, p.n / W, s, p);
 }
 
 template <typename T, int METHOD, template <typename, int> class M = ProgModel>
 static hipError_t launch_prog_m(const ProgArgs<T>& p, hipStream_t s) {
-  return prog_may_vec(p) ? launch_prog_w<T, METHOD, 4, M<T, 4>>(p, s) : launch_prog_w<T, METHOD, 1, M<T, 1>>(p, s);
+  const bool vec = may_vec(p) &&
+                   (p.scalar_noise || p.key.elem0 % 4 == 0);   // scalar noise addresses the field by row: any elem0
+  return vec ? launch_prog_w<T, METHOD, 4, M<T, 4>>(p, s) : launch_prog_w<T, METHOD, 1, M<T, 1>>(p, s);
 }
 
 template <typename T, int METHOD, typename M = ProgSensModel<T>>
 static hipError_t launch_prog_sens_m(const ProgSensArgs<T>& q, hipStream_t s) {
-  const int64_t n = q.base.n;
-  if (n <= 0 || q.base.n_steps <= 0) return hipSuccess;
-  hipLaunchKernelGGL((trajectory_prog_sens_kernel<T, METHOD, M>), dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0,
-                     s, q);
-  return hipGetLastError();
+  if (nothing_to_do(q.base)) return hipSuccess;
+  return launch_lanes(trajectory_prog_sens_kernel<T, METHOD, M>, q.base.n, s, q);
 }
 
 // `MP`: the channel-count class (4, 8, 16), q.m <= MP
 template <typename T, int METHOD, int MP, template <typename, int> class M = ProgModel>
 static hipError_t launch_additive_mp(const ProgAdditiveArgs<T>& q, hipStream_t s) {
-  const int64_t n = q.base.n;
-  if (n <= 0 || q.base.n_steps <= 0) return hipSuccess;
-  if (prog_additive_may_vec(q)) {
-    hipLaunchKernelGGL((trajectory_prog_additive_kernel<T, METHOD, 4, MP, M<T, 4>>),
-                       dim3((unsigned)(((n >> 2) + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, q);
-  } else {
-    hipLaunchKernelGGL((trajectory_prog_additive_kernel<T, METHOD, 1, MP, M<T, 1>>), dim3((unsigned)((n + kBlock - 1) / kBlock)),
-                       dim3(kBlock), 0, s, q);
-  }
-  return hipGetLastError();
+  const ProgArgs<T>& p = q.base;
+  if (nothing_to_do(p)) return hipSuccess;
+  const bool vec = may_vec(p, q.gtab);   // (the field is addressed by row and channel: no condition on elem0)
+  if (vec) return launch_lanes(trajectory_prog_additive_kernel<T, METHOD, 4, MP, M<T, 4>>, p.n >> 2, s, q);
+  return launch_lanes(trajectory_prog_additive_kernel<T, METHOD, 1, MP, M<T, 1>>, p.n, s, q);
 }
 
 template <typename T, int METHOD>
@@ -1465,12 +1433,12 @@ hipError_t launch_trajectory_prog_additive(void* ys, const void* y0, int64_t row
   if (f_len > kProgWords) return hipErrorInvalidValue;
   const ProgAdditiveArgs<T> q = prog_additive_args(
       prog_args<T>(ys, y0, rows, d, consts, n_const, 0, tr, key, key_dev, code, f_len), m, gtab, time_dependent, method);
-  switch (method) {
-    case kEuler: return launch_additive_m<T, kEuler>(q, s);
-    case kMidpoint: return launch_additive_m<T, kMidpoint>(q, s);
-    case kSrk: return launch_additive_m<T, kSrk>(q, s);
-    default: return hipErrorInvalidValue;
-  }
+  // Euler, midpoint and SRK only (the kernel has no other scheme, and none is instantiated)
+  return dispatch_method(method, [&](auto m) {
+    constexpr int METHOD = decltype(m)::value;
+    if constexpr (METHOD == kEuler || METHOD == kMidpoint || METHOD == kSrk) return launch_additive_m<T, METHOD>(q, s);
+    else return hipErrorInvalidValue;
+  });
 }
 
 #ifndef TSDE_SPECIALISE_TU
@@ -1496,16 +1464,7 @@ hipError_t launch_trajectory_prog_diag(void* ys, void* sens, const int8_t* param
                                        const uint64_t* key_dev, hipStream_t s) {
   if (f_len + g_len + dg_len > kProgWords) return hipErrorInvalidValue;
   const ProgArgs<T> p = prog_args<T>(ys, y0, rows, d, consts, n_const, scalar_noise, tr, key, key_dev, code, f_len, g_len, dg_len);
-  switch (method) {
-    case kEuler: return launch_prog_diag_m<T, kEuler>(p, sens, param_slot, s);
-    case kMilIto: return launch_prog_diag_m<T, kMilIto>(p, sens, param_slot, s);
-    case kMilStrat: return launch_prog_diag_m<T, kMilStrat>(p, sens, param_slot, s);
-    case kMidpoint: return launch_prog_diag_m<T, kMidpoint>(p, sens, param_slot, s);
-    case kSrk: return launch_prog_diag_m<T, kSrk>(p, sens, param_slot, s);
-    case kHeun: return launch_prog_diag_m<T, kHeun>(p, sens, param_slot, s);
-    case kEulerHeun: return launch_prog_diag_m<T, kEulerHeun>(p, sens, param_slot, s);
-    default: return hipErrorInvalidValue;
-  }
+  return dispatch_method(method, [&](auto m) { return launch_prog_diag_m<T, decltype(m)::value>(p, sens, param_slot, s); });
 }
 
 #ifndef TSDE_SPECIALISE_TU

@@ -283,6 +283,22 @@ struct StepNoise {
     return (lane & 1u) ? n1 : n0;
   }
 };
+
+// The same three draws through the free functions above, nothing precomputed: the source of the step loops that have not
+// moved onto the shared Philox head.
+struct PlainStepNoise {
+  NoiseKey key;
+  uint32_t cell;
+  TSDE_D PlainStepNoise(const NoiseKey& k, uint32_t cell_) : key(k), cell(cell_) {}
+  template <typename T>
+  TSDE_D void normal4(uint64_t quad, uint32_t stream, T (&n)[4]) const { tsde::normal4<T>(key, quad, cell, 0, stream, n); }
+  template <typename T>
+  TSDE_D void normal4_pairs(uint64_t quad, uint32_t stream, T (&n)[4]) const {
+    tsde::normal4_pairs<T>(key, quad, cell, 0, stream, n);
+  }
+  template <typename T>
+  TSDE_D T normal1(uint64_t elem, uint32_t stream) const { return tsde::normal1<T>(key, elem, cell, 0, stream); }
+};
 #endif  // __HIPCC__
 
 }  // namespace tsde

@@ -136,14 +136,19 @@ def counter_rows_bm(rows, m, entropy, edges, dtype, levy=False):
     npdt = np.float32 if dtype == torch.float32 else np.float64
     edges = np.ascontiguousarray(edges, dtype=np.float64)
 
+    rows = np.asarray(rows, dtype=np.int64)
+    # runs of consecutive rows are consecutive elements of the field: one query each
+    starts = [0] + [k for k in range(1, len(rows)) if rows[k] != rows[k - 1] + 1] + [len(rows)]
+
     def bm(ta, tb, return_U=False, return_A=False):
         W = np.empty((len(rows), m), dtype=npdt)
         U = np.empty((len(rows), m), dtype=npdt) if levy else None
-        for k, r in enumerate(rows):
-            w, u, _ = counter.query(m, entropy, edges, float(ta), float(tb), dtype=npdt, elem0=int(r) * m, have_h=levy)
-            W[k] = w
+        for k0, k1 in zip(starts[:-1], starts[1:]):
+            w, u, _ = counter.query((k1 - k0) * m, entropy, edges, float(ta), float(tb), dtype=npdt,
+                                    elem0=int(rows[k0]) * m, have_h=levy)
+            W[k0:k1] = w.reshape(k1 - k0, m)
             if levy:
-                U[k] = u
+                U[k0:k1] = u.reshape(k1 - k0, m)
         W = torch.from_numpy(W)
         return (W, torch.from_numpy(U)) if return_U else W
 
@@ -209,12 +214,13 @@ def rheun_cotangents(ts_list, B, d, seed, dt=RHEUN_DT):
 
 
 def grid_oracle(sde, m, ts_list, rows, entropy, y0, cotangents, dt=RHEUN_DT, adjoint=False, method="reversible_heun",
-                adjoint_method=None):
+                adjoint_method=None, levy=False):
     """The oracle's reversible-Heun solve of a copy of `sde` on the counter path of global batch rows `rows`, in float32
     and in float64: ``{dtype: (ys, {label: [dL/dy0, dL/dtheta...]})}`` for L = sum(ys * cotangent), by back-propagation
     through oracle/solvers_ref.integrate_reversible_heun -- or, `adjoint`, by the reference's own backward pass
     (oracle/adjoint_ref.reversible_heun_adjoint_gradients, which steps to every output time). `y0`: (len(rows), d).
-    Another `method`: oracle/solvers_ref.integrate, and adjoint_ref.adjoint_gradients with `adjoint_method`."""
+    Another `method`: oracle/solvers_ref.integrate, and adjoint_ref.adjoint_gradients with `adjoint_method`. `levy`: the path
+    also serves the space-time Levy area (SRK)."""
     import copy
     from oracle import adjoint_ref, solvers_ref
     edges = rheun_grid(ts_list, dt).t_f64()
@@ -222,7 +228,7 @@ def grid_oracle(sde, m, ts_list, rows, entropy, y0, cotangents, dt=RHEUN_DT, adj
     for dtype in (torch.float32, torch.float64):
         ref_sde = copy.deepcopy(sde).cpu().to(dtype)
         params = [p for p in ref_sde.parameters() if p.requires_grad]
-        bm = counter_rows_bm(np.asarray(rows), m, entropy, edges, dtype)
+        bm = counter_rows_bm(np.asarray(rows), m, entropy, edges, dtype, levy=levy)
         ts = torch.tensor(ts_list, dtype=dtype)
         grads = {}
         if adjoint:
@@ -257,3 +263,145 @@ def assert_within_reference_rounding(new32, ref32, ref64, what="", factor=4.0, f
     assert err_new <= factor * err_ref + floor * scale, \
         f"{what}: |hip32 - ref64| = {err_new:.3e} > {factor} * |ref32 - ref64| ({err_ref:.3e}) + {floor * scale:.1e}"
     return err_new, err_ref
+
+
+# ---- the perceptron training kernels held to float32 rounding (test_mlp_gradient_criterion.py, --------------------------------
+# ---- test_gpu_mlp_gradient_rounding.py): autograd through `sdeint` (_MlpTrajectoryFn) and `sdeint_adjoint` (_MlpAdjointFn) ----
+MLP_GRAD_DT = 2.0 ** -5
+MLP_GRAD_STEPS = 16
+# Output times in steps: the first step, two consecutive boundaries, an interior one and the last. Both routes take outputs
+# on step boundaries only.
+MLP_GRAD_OUTPUTS = (0, 1, 2, 9, 16)
+# (B, d, hidden): each the smallest that reaches one edge of the kernels.
+MLP_GRAD_SHAPES = (
+    (16, 128, 128),      # one exact tile
+    (37, 20, 36),        # ragged batch, padded channels
+    (129, 4, 16),        # one row past a 128-row block
+    (33, 64, 256),       # wide hidden layer
+    (48, 124, 120),      # both widths just under a tile multiple
+)
+# route, forward method, adjoint method, sde type, diffusion. method None: every default (SRK forward with the space-time
+# Levy area; Milstein backward for diagonal Ito noise).
+MLP_GRAD_SCHEMES = (
+    ("backprop", "euler", None, "ito", "affine"),
+    ("backprop", "euler", None, "ito", "sigmoid"),
+    ("backprop", "milstein", None, "ito", "affine"),
+    ("backprop", "milstein", None, "stratonovich", "affine"),
+    ("adjoint", "euler", "euler", "ito", "sigmoid"),
+    ("adjoint", "euler", "milstein", "ito", "affine"),
+    ("adjoint", "milstein", None, "ito", "sigmoid"),
+    ("adjoint", "midpoint", "milstein", "stratonovich", "affine"),
+    ("adjoint", None, None, "ito", "sigmoid"),
+)
+# The kernels' result may differ from the float64 oracle by MLP_GRAD_FACTOR times the float32 oracle's own difference from it,
+# plus MLP_GRAD_FLOOR of the quantity's scale. The factor is twice the worst ratio measured on an MI355X over every case,
+# cotangent and quantity below (profiles/mlp_gradient_rounding_ratios.txt), rounded up, and at least 4.
+MLP_GRAD_FACTOR = 4.0
+MLP_GRAD_FLOOR = 1e-6
+MLP_GRAD_QUANTITIES = ("ys", "y0", "lin1.weight", "lin1.bias", "lin2.weight", "lin2.bias", "diff_rate", "diff_shift")
+
+
+class MlpGradCase:
+    def __init__(self, index, shape, scheme, activation, scalar=False):
+        self.B, self.d, self.hidden = shape
+        self.route, self.method, self.adjoint_method, self.sde_type, self.diffusion = scheme
+        self.activation, self.scalar = activation, scalar
+        self.seed = 100 + index
+        self.entropy = 7000 + index
+        self.levy = self.method is None
+        self.id = "-".join([self.route, self.method or "default", *([self.adjoint_method or "default"] * (self.route == "adjoint")),
+                            self.sde_type, self.diffusion, activation, "x".join(str(v) for v in shape)]
+                           + ["scalar"] * scalar)
+
+    def module(self):
+        """On the CPU, float32."""
+        return mlp_grad_module(self.d, self.hidden, self.activation, seed=self.seed, scalar_diffusion=self.scalar,
+                               sde_type=self.sde_type, diffusion=self.diffusion)
+
+    def y0(self):
+        gen = torch.Generator().manual_seed(self.seed)
+        return 0.5 * torch.randn(self.B, self.d, generator=gen)
+
+    def ts(self, outputs=MLP_GRAD_OUTPUTS):
+        return [k * MLP_GRAD_DT for k in outputs]
+
+    def cotangents(self):
+        """[(label, (outputs, B, d) float32 CPU tensor)]: random on every output (ys[0] included), and the same one masked to
+        the first, a middle and the last output in turn."""
+        gen = torch.Generator().manual_seed(self.seed + 1)
+        w = torch.randn(len(MLP_GRAD_OUTPUTS), self.B, self.d, generator=gen)
+        out = [("all", w)]
+        for label, j in (("first", 0), ("middle", len(MLP_GRAD_OUTPUTS) // 2), ("last", len(MLP_GRAD_OUTPUTS) - 1)):
+            mask = torch.zeros(len(MLP_GRAD_OUTPUTS), 1, 1)
+            mask[j] = 1.0
+            out.append((label, w * mask))
+        return out
+
+
+def mlp_grad_module(d, hidden, activation, seed=0, scalar_diffusion=False, sde_type="ito", diffusion="affine"):
+    """The recipe of tests/test_gpu_mlp_backward.py::_sde on the CPU: asymmetric, well-scaled weights (a transposed operand
+    cannot pass) and per-channel diffusion parameters -- or, `scalar_diffusion`, 0-d ones."""
+    import torchsde_amd
+    gen = torch.Generator().manual_seed(seed)
+    sigmoid = diffusion == "sigmoid"
+    rate = torch.tensor(0.05) if scalar_diffusion else (2.0 if sigmoid else 0.2) * torch.rand(d, generator=gen) - 0.1
+    shift = torch.tensor(0.2) if scalar_diffusion else 0.1 + 0.2 * torch.rand(d, generator=gen)
+    sde = torchsde_amd.MLPDriftDiagonalSDE(d, hidden, activation=activation, diff_rate=rate, diff_shift=shift,
+                                           sde_type=sde_type, diffusion=diffusion, diff_scale=0.4 if sigmoid else 1.0)
+    with torch.no_grad():
+        sde.lin1.weight.copy_(torch.randn(hidden, d, generator=gen) / d ** 0.5)
+        sde.lin2.weight.copy_(torch.randn(d, hidden, generator=gen) / hidden ** 0.5)
+        sde.lin1.bias.copy_(0.3 * torch.randn(hidden, generator=gen))
+        sde.lin2.bias.copy_(0.3 * torch.randn(d, generator=gen))
+    return sde
+
+
+def mlp_grad_cases():
+    """Every shape under every scheme; the activation alternates along the table so that each shape and each scheme meets
+    both (five shapes and nine schemes: an odd stride)."""
+    cases = []
+    for scheme in MLP_GRAD_SCHEMES:
+        for shape in MLP_GRAD_SHAPES:
+            cases.append(MlpGradCase(len(cases), shape, scheme, ("tanh", "softplus")[len(cases) % 2]))
+    return cases
+
+
+def mlp_grad_scalar_cases():
+    """0-d diffusion parameters, on each route (affine and sigmoid), at the ragged shape."""
+    return [MlpGradCase(900 + i, MLP_GRAD_SHAPES[1], MLP_GRAD_SCHEMES[k], act, scalar=True)
+            for i, (k, act) in enumerate(((0, "softplus"), (2, "tanh"), (4, "tanh"), (5, "softplus")))]
+
+
+def mlp_grad_oracle(case, sde=None, outputs=MLP_GRAD_OUTPUTS, cotangents=None):
+    """``{dtype: {label: {quantity: tensor}}}`` over MLP_GRAD_QUANTITIES from `grid_oracle` for `case`: autograd through
+    oracle/solvers_ref.integrate, or oracle/adjoint_ref.adjoint_gradients, in float32 and float64, on the counter path of
+    rows 0 .. B-1. `sde`: another module than the case's own (a mutant); `outputs`: another grid, in steps."""
+    sde = case.module() if sde is None else sde
+    cotangents = case.cotangents() if cotangents is None else cotangents
+    names = [name for name, _ in sde.named_parameters()]
+    threads = torch.get_num_threads()
+    torch.set_num_threads(1)       # tensors this small only wait for a thread pool; and one summation order on every machine
+    try:
+        refs = grid_oracle(sde, case.d, case.ts(outputs), range(case.B), case.entropy, case.y0(), cotangents,
+                           dt=MLP_GRAD_DT, adjoint=case.route == "adjoint", method=case.method or "srk",
+                           adjoint_method=case.adjoint_method, levy=case.levy)
+    finally:
+        torch.set_num_threads(threads)
+    out = {}
+    for dtype, (ys, grads) in refs.items():
+        out[dtype] = {label: dict([("ys", ys), ("y0", g[0])] + list(zip(names, g[1:]))) for label, g in grads.items()}
+    return out
+
+
+def mlp_grad_ragged_slices(case, quantity):
+    """The sub-blocks of `quantity` to compare on their own (a max-norm over the whole tensor can hide an error confined to
+    one): the rows of the ragged last 16-row tile of dL/dy0, the last partial 16-wide tile of rows and of columns of each
+    weight gradient. {label: index tuple}."""
+    def last_tile(n):
+        return slice(16 * ((n - 1) // 16), n)
+    if quantity == "y0":
+        return {"last row tile": (last_tile(case.B),)}
+    if quantity in ("lin1.weight", "lin2.weight"):
+        rows, cols = (case.hidden, case.d) if quantity == "lin1.weight" else (case.d, case.hidden)
+        return {"last tile of rows": (last_tile(rows),), "last tile of columns": (slice(None), last_tile(cols))}
+    return {}

@@ -432,6 +432,23 @@ int tsde_trajectory_mlp_diag(void* ys, const void* y0, int64_t rows, int64_t d, 
                              const tsde_traj_t* traj, uint64_t entropy, uint64_t elem0, const uint64_t* entropy_dev,
                              int dtype, void* stream);
 
+/* tsde_trajectory_mlp_diag carrying the KL column of `sdeint(..., logqp=True)` (torchsde/_core/base_sde.py:240-306,
+ * `SDELogqp`) for a per-channel affine prior drift h = prior_rate * y + prior_shift: beside the state, per row,
+ *     l_{k+1} = l_k + 0.5 sum_i u_i^2 dt_k,   u = (f - h) / safe(g) at y_k,   safe(g) = g, or 1e-7 sign(g) where |g| <= 1e-7
+ * (misc.py:66-68; f the drift itself, without Milstein's correction; the column's diffusion is 0, so Euler and Milstein
+ * advance it alike). l_0 = 0.
+ *   logqp        (traj->n_out, rows)  out: l at the outputs (interpolated like ys)
+ *   prior_rate, prior_shift (d)
+ *   method in {TSDE_TRAJ_EULER, TSDE_TRAJ_MILSTEIN_ITO}
+ * Increments: the Brownian motion of such a solve has d + 1 columns, so element (row, channel) of the field is
+ * elem0 + row * (d + 1) + channel (column d drives nothing); elem0 may be any value. rows * (d + 1) < 2^30. Everything
+ * else as tsde_trajectory_mlp_diag. The row sum is an f32 sum in the kernel's own order. */
+int tsde_trajectory_mlp_diag_logqp(void* ys, void* logqp, const void* y0, int64_t rows, int64_t d, int64_t hidden,
+                                   const void* w1, const void* b1, const void* w2, const void* b2, const void* diff_rate,
+                                   const void* diff_shift, const void* prior_rate, const void* prior_shift, int diff_kind,
+                                   double diff_amp, int activation, int method, const tsde_traj_t* traj, uint64_t entropy,
+                                   uint64_t elem0, const uint64_t* entropy_dev, int dtype, void* stream);
+
 /* tsde_trajectory_affine_diag for drift and diffusion given as expression PROGRAMS: any elementwise code -- sums and
  * products of several functions of the state, powers, quotients (the reference's ExScalar, tests/problems.py:75-103:
  * f = -p^2 sin(y) cos(y)^3, g = p cos(y)^2) -- as postfix instruction streams over a four-deep value stack.
@@ -621,6 +638,24 @@ int tsde_adjoint_mlp_diag(void* y, void* a, void* stash_a, void* stash_hid, void
                           int diff_kind, double diff_amp, int activation, int ito, const tsde_traj_t* traj, int32_t k_lo,
                           int32_t k_hi, uint64_t entropy, uint64_t elem0, const uint64_t* entropy_dev, int dtype,
                           void* stream);
+
+/* tsde_adjoint_mlp_diag for the solve of tsde_trajectory_mlp_diag_logqp: the stochastic adjoint of `SDELogqp` around the
+ * perceptron-drift SDE (Ito only: bit 0 of `ito` must be set). a_l (rows), the cotangent of the column l, is constant
+ * between outputs and is not written; with u as above and w = a_l u / safe(g), per step
+ *     the drift network's cotangent is a + w:   delta = (W2 (a + w)) * act'(W1^T y + b1) * dt,   stash_a = dt (a + w)
+ *     a <- ... + dt (-prior_rate w - a_l u^2 g' / safe)          (the last term only where |g| > 1e-7)
+ *   row_rate, row_shift            gain  -a_l dt (u^2 / safe) dg/dc, ... dg/de  (where |g| > 1e-7)
+ *   row_prior_rate, row_prior_shift (rows, d)  accumulated like row_rate: -dt w y and -dt w; their sums over all rows are
+ *                dL/d prior_rate, dL/d prior_shift
+ * The Ito correction and the Milstein terms are those of tsde_adjoint_mlp_diag (the column's diffusion is 0). Increments
+ * from the field of row stride d + 1, any elem0. Everything else as tsde_adjoint_mlp_diag. */
+int tsde_adjoint_mlp_diag_logqp(void* y, void* a, const void* a_l, void* stash_a, void* stash_hid, void* stash_delta,
+                                void* stash_y, void* row_rate, void* row_shift, void* row_prior_rate, void* row_prior_shift,
+                                int64_t rows, int64_t d, int64_t hidden, const void* w1, const void* b1, const void* w2,
+                                const void* b2, const void* diff_rate, const void* diff_shift, const void* prior_rate,
+                                const void* prior_shift, int diff_kind, double diff_amp, int activation, int ito,
+                                const tsde_traj_t* traj, int32_t k_lo, int32_t k_hi, uint64_t entropy, uint64_t elem0,
+                                const uint64_t* entropy_dev, int dtype, void* stream);
 
 /* Reverse sweep of the gradient of tsde_trajectory_mlp_diag with method TSDE_TRAJ_EULER or TSDE_TRAJ_MILSTEIN_*:
  * back-propagation through the solver, i.e. what loss.backward() computes when autograd records the reference's

@@ -165,6 +165,9 @@ SIGNATURES = {
     "tsde_trajectory_mlp_diag": (_c_int, [_c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr,
                                           _c_ptr, _c_int, _c_dbl, _c_int, _c_int, ctypes.POINTER(Traj), _c_u64, _c_u64, _c_ptr, _c_int,
                                           _c_ptr]),
+    "tsde_trajectory_mlp_diag_logqp": (_c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_ptr, _c_ptr, _c_ptr, _c_ptr,
+                                                _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_int, _c_dbl, _c_int, _c_int,
+                                                ctypes.POINTER(Traj), _c_u64, _c_u64, _c_ptr, _c_int, _c_ptr]),
     "tsde_trajectory_prog_diag": (_c_int, [_c_ptr, _c_ptr, _c_i64, _c_i64, _c_ptr, _c_i32, _c_i32, _c_i32, _c_ptr, _c_i32, _c_int,
                                            _c_int, ctypes.POINTER(Traj), _c_u64, _c_u64, _c_ptr, _c_int, _c_ptr]),
     "tsde_trajectory_prog_diag_sens": (_c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_ptr, _c_i32, _c_i32, _c_i32, _c_ptr, _c_i32,
@@ -187,6 +190,9 @@ SIGNATURES = {
     "tsde_adjoint_mlp_diag": (_c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64,
                                        _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_int, _c_dbl, _c_int, _c_int,
                                        ctypes.POINTER(Traj), _c_i32, _c_i32, _c_u64, _c_u64, _c_ptr, _c_int, _c_ptr]),
+    "tsde_adjoint_mlp_diag_logqp": (_c_int, [_c_ptr] * 11 + [_c_i64, _c_i64, _c_i64] + [_c_ptr] * 8 +
+                                    [_c_int, _c_dbl, _c_int, _c_int, ctypes.POINTER(Traj), _c_i32, _c_i32, _c_u64, _c_u64,
+                                     _c_ptr, _c_int, _c_ptr]),
     "tsde_rheun_mlp_forward": (_c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_int, ctypes.POINTER(DeepMlp),
                                         ctypes.POINTER(DeepMlp), ctypes.POINTER(Traj), _c_ptr, _c_u64, _c_u64, _c_ptr, _c_int,
                                         _c_ptr]),

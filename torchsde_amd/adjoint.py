@@ -822,7 +822,7 @@ def _sdeint_adjoint(sde, y0, ts, bm, method, adjoint_method, dt, adaptive, adjoi
     if torch.is_grad_enabled() and (y0.requires_grad or adjoint_params):
         from . import mlp_adjoint
         ys = mlp_adjoint.route(sde, y0, ts, bm, method, adjoint_method, dt, adaptive, adjoint_adaptive, options,
-                               adjoint_options, adjoint_params, extra_solver_state, solver=solver)
+                               adjoint_options, adjoint_params, extra_solver_state, solver=solver, logqp=logqp)
         if ys is not None:
             return contract.parse_return(y0, ys, (), extra, logqp)
     # the reversible pair on networks of (t, y): forward one launch, backward the exact-gradient sweep on the matrix cores
@@ -834,6 +834,14 @@ def _sdeint_adjoint(sde, y0, ts, bm, method, adjoint_method, dt, adaptive, adjoi
             and y0.numel() > 0):
         from . import neural_rheun_route
         kernels_route = neural_rheun_route.plan_adjoint(solver, sde, y0, ts, bm, dt, adjoint_params)
+        if kernels_route is not None and kernels_route.trusted:
+            return contract.parse_return(y0, kernels_route.solve(y0), (), extra, logqp)
+    # logqp=True on the perceptron-drift module with an affine prior: the KL instantiations of the same kernels; trust is earned
+    # like the reversible pair's (mlp_adjoint.plan_logqp)
+    if logqp and torch.is_grad_enabled() and (y0.requires_grad or adjoint_params):
+        from . import mlp_adjoint
+        kernels_route = mlp_adjoint.plan_logqp(sde, y0, ts, bm, method, adjoint_method, dt, adaptive, adjoint_adaptive,
+                                               options, adjoint_options, adjoint_params, extra_solver_state, solver)
         if kernels_route is not None and kernels_route.trusted:
             return contract.parse_return(y0, kernels_route.solve(y0), (), extra, logqp)
     if hasattr(solver, "wants_extra"):

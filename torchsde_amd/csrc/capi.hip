@@ -576,6 +576,33 @@ int tsde_trajectory_mlp_diag(void* ys, const void* y0, int64_t rows, int64_t d, 
               where);
 }
 
+int tsde_trajectory_mlp_diag_logqp(void* ys, void* logqp, const void* y0, int64_t rows, int64_t d, int64_t hidden,
+                                   const void* w1, const void* b1, const void* w2, const void* b2, const void* diff_rate,
+                                   const void* diff_shift, const void* prior_rate, const void* prior_shift, int diff_kind,
+                                   double diff_amp, int activation, int method, const tsde_traj_t* traj, uint64_t entropy,
+                                   uint64_t elem0, const uint64_t* entropy_dev, int dtype, void* stream) {
+  const char* where = "tsde_trajectory_mlp_diag_logqp";
+  if (diff_kind != TSDE_DIFF_AFFINE && diff_kind != TSDE_DIFF_SIGMOID) return bad_arg(where, "unknown diffusion kind");
+  if (!ys || !logqp || !y0 || !w1 || !b1 || !w2 || !b2 || !diff_rate || !diff_shift || !prior_rate || !prior_shift || !traj)
+    return bad_arg(where, "null argument");
+  if (dtype != TSDE_F32) return bad_arg(where, "dtype must be TSDE_F32");
+  if (rows < 0) return bad_arg(where, "need rows >= 0");
+  if (d < 4 || d > 128 || d % 4 != 0 || hidden < 1 || hidden > 256 || (hidden > 128 && d > 64))
+    return bad_arg(where, "need d a multiple of 4 in [4, 128] and hidden in [1, 128] (up to 256 for d <= 64)");
+  if ((reinterpret_cast<uintptr_t>(y0) | reinterpret_cast<uintptr_t>(ys)) & 15u)
+    return bad_arg(where, "ys and y0 must be 16-byte aligned");
+  if (rows * (d + 1) >= (int64_t(1) << 30)) return bad_arg(where, "need rows * (d + 1) < 2^30 (32-bit lane offsets)");
+  if (activation != TSDE_ACT_TANH && activation != TSDE_ACT_SOFTPLUS) return bad_arg(where, "unknown activation");
+  if (method != TSDE_TRAJ_EULER && method != TSDE_TRAJ_MILSTEIN_ITO) return bad_arg(where, "method must be Euler or Ito Milstein");
+  if (const char* bad = schedule_problem(traj)) return bad_arg(where, bad);
+  const hipStream_t s = (hipStream_t)stream;
+  ProfScope p(TSDE_KID_TRAJECTORY, s);
+  return fail(tsde::launch_trajectory_mlp_diag_logqp(ys, logqp, y0, rows, d, hidden, w1, b1, w2, b2, diff_rate, diff_shift,
+                                                     prior_rate, prior_shift, diff_kind, diff_amp, activation, method, traj,
+                                                     make_key(entropy, elem0), entropy_dev, s),
+              where);
+}
+
 static int prog_diag(const char* where, void* ys, void* sens, const int8_t* param_slot, const void* y0, int64_t rows,
                      int64_t d, const uint32_t* code, int32_t f_len, int32_t g_len, int32_t dg_len, const void* consts,
                      int32_t n_const, int scalar_noise, int method, const tsde_traj_t* traj, uint64_t entropy, uint64_t elem0,
@@ -794,6 +821,40 @@ int tsde_adjoint_mlp_diag(void* y, void* a, void* stash_a, void* stash_hid, void
                                             hidden, w1, b1, w2, b2, diff_rate, diff_shift, diff_kind, diff_amp,
                                             activation, ito & 3, traj, k_lo, k_hi, make_key(entropy, elem0),
                                             entropy_dev, s),
+              where);
+}
+
+int tsde_adjoint_mlp_diag_logqp(void* y, void* a, const void* a_l, void* stash_a, void* stash_hid, void* stash_delta,
+                                void* stash_y, void* row_rate, void* row_shift, void* row_prior_rate, void* row_prior_shift,
+                                int64_t rows, int64_t d, int64_t hidden, const void* w1, const void* b1, const void* w2,
+                                const void* b2, const void* diff_rate, const void* diff_shift, const void* prior_rate,
+                                const void* prior_shift, int diff_kind, double diff_amp, int activation, int ito,
+                                const tsde_traj_t* traj, int32_t k_lo, int32_t k_hi, uint64_t entropy, uint64_t elem0,
+                                const uint64_t* entropy_dev, int dtype, void* stream) {
+  const char* where = "tsde_adjoint_mlp_diag_logqp";
+  if (!y || !a || !a_l || !stash_a || !stash_hid || !stash_delta || !stash_y || !row_rate || !row_shift || !row_prior_rate ||
+      !row_prior_shift || !w1 || !b1 || !w2 || !b2 || !diff_rate || !diff_shift || !prior_rate || !prior_shift || !traj)
+    return bad_arg(where, "null argument");
+  if (diff_kind != TSDE_DIFF_AFFINE && diff_kind != TSDE_DIFF_SIGMOID) return bad_arg(where, "unknown diffusion kind");
+  if (dtype != TSDE_F32) return bad_arg(where, "dtype must be TSDE_F32");
+  if (rows < 0) return bad_arg(where, "need rows >= 0");
+  if (d < 4 || d > 128 || d % 4 != 0 || hidden < 4 || hidden > 256 || hidden % 4 != 0 || (hidden > 128 && d > 64))
+    return bad_arg(where, "need d and hidden multiples of 4, d in [4, 128], hidden in [4, 128] (up to 256 for d <= 64)");
+  if (rows * ((d > hidden ? d : hidden) + 1) >= (int64_t(1) << 30))
+    return bad_arg(where, "need rows * (max(d, hidden) + 1) < 2^30 (32-bit lane offsets)");
+  const void* aligned[] = {y, a, stash_a, stash_hid, stash_delta, stash_y, row_rate, row_shift, row_prior_rate, row_prior_shift};
+  for (const void* q : aligned)
+    if (reinterpret_cast<uintptr_t>(q) & 15u) return bad_arg(where, "state-shaped buffers must be 16-byte aligned");
+  if (activation != TSDE_ACT_TANH && activation != TSDE_ACT_SOFTPLUS) return bad_arg(where, "unknown activation");
+  if (!(ito & 1)) return bad_arg(where, "the KL column is carried for Ito SDEs only");
+  if (k_lo < 0 || k_hi < k_lo || k_hi > traj->n_steps) return bad_arg(where, "need 0 <= k_lo <= k_hi <= n_steps");
+  if (traj->n_steps > 0 && (!traj->step_rows || !traj->cells)) return bad_arg(where, "schedule without step rows");
+  const hipStream_t s = (hipStream_t)stream;
+  ProfScope p(TSDE_KID_MLP_ADJOINT, s);
+  return fail(tsde::launch_adjoint_mlp_diag_logqp(y, a, a_l, stash_a, stash_hid, stash_delta, stash_y, row_rate, row_shift,
+                                                  row_prior_rate, row_prior_shift, rows, d, hidden, w1, b1, w2, b2, diff_rate,
+                                                  diff_shift, prior_rate, prior_shift, diff_kind, diff_amp, activation,
+                                                  ito & 3, traj, k_lo, k_hi, make_key(entropy, elem0), entropy_dev, s),
               where);
 }
 

@@ -67,6 +67,25 @@ struct MlpAdjArgs {
   const uint64_t* key_dev;
 };
 
+// The KL instantiation (`sdeint_adjoint(..., logqp=True)` with a per-channel affine prior drift h = hr * y + hs): the forward
+// solve carried the column l, l' = f_l = 0.5 sum_i u_i^2, u = (f - h) / safe(g) (base_sde.py:240-306). Its cotangent a_l
+// is constant between outputs (nothing depends on l) and reaches the rest of the adjoint through d f_l / d(y, theta): with
+// w = a_l u / safe (per channel)
+//
+//   the drift network sees the cotangent a + w instead of a     (u^T = W2 (a + w)^T; the stash holds dt (a + w))
+//   a      <- ... + dt (-hr w - a_l u^2 g' / safe)
+//   a_th_g <- ... - a_l dt (u^2 / safe) dg/dtheta_g            (no such term where the divisor is clamped)
+//   a_hr   <- a_hr - dt w y        a_hs <- a_hs - dt w          (the prior's coefficients)
+//
+// The column's diffusion is 0: the Ito correction and the Milstein terms of the step are unchanged.
+struct MlpAdjKlArgs : MlpAdjArgs {
+  const float* a_l;         // (B) cotangent of the column l, unchanged by the launch
+  const float *hr, *hs;     // (d) prior drift coefficients
+  float* row_hrate;         // (B, d) as row_rate, for dL/dhr
+  float* row_hshift;        // (B, d) ... for dL/dhs
+  int64_t bm_stride;        // row stride of the Brownian field: d + 1
+};
+
 // Sum of `v` over the 16 lanes of a DPP row, valid in the row's last lane (inclusive scan by row_shr 1, 2, 4, 8; lanes
 // shifted in from outside the row read 0).
 TSDE_D float row_total(float v) {
@@ -77,9 +96,10 @@ TSDE_D float row_total(float v) {
   return v;
 }
 
-template <int D, int H, int ACT, int NW, bool FULL, bool MILSTEIN>
-__global__ void __launch_bounds__(NW * 64) mlp_adjoint_kernel(const MlpAdjArgs p) {
-  constexpr int R = 16;
+template <int D, int H, int ACT, int NW, bool FULL, bool MILSTEIN, bool KL = false>
+__global__ void __launch_bounds__(NW * 64)
+    mlp_adjoint_kernel(const std::conditional_t<KL, MlpAdjKlArgs, MlpAdjArgs> p) {
+  constexpr int R = 16, kSums = KL ? 4 : 2;
   using TL = Tile<R>;
   constexpr int TD = D / R, TH = H / R, kThreads = NW * 64;
   constexpr int S1 = H + MlpLds<R>::kPad, S2 = D + MlpLds<R>::kPad;
@@ -91,6 +111,9 @@ __global__ void __launch_bounds__(NW * 64) mlp_adjoint_kernel(const MlpAdjArgs p
   float* cs = b2s + D;              // D
   float* es = cs + D;               // D
   float* sums = es + D;             // NW x 2 x D: per wave, the diffusion-parameter sums (rate, shift) of its 16 rows
+  //                                   (KL: NW x 4 x D, the prior's (hr, hs) after them, then hr and hs themselves)
+  [[maybe_unused]] float* hrs = sums + NW * kSums * D;      // D
+  [[maybe_unused]] float* hss = hrs + D;                    // D
   const int dT = p.d, hT = p.h;
   for (int i = threadIdx.x; i < D * H; i += kThreads) {
     const int k1 = i / H, m1 = i % H, k2 = i / D, m2 = i % D;
@@ -102,8 +125,12 @@ __global__ void __launch_bounds__(NW * 64) mlp_adjoint_kernel(const MlpAdjArgs p
     b2s[i] = i < dT ? p.b2[i] : 0.0f;
     cs[i] = i < dT ? p.c[i] : 0.0f;
     es[i] = i < dT ? p.e[i] : 0.0f;
+    if constexpr (KL) {
+      hrs[i] = i < dT ? p.hr[i] : 0.0f;
+      hss[i] = i < dT ? p.hs[i] : 0.0f;
+    }
   }
-  for (int i = threadIdx.x; i < NW * 2 * D; i += kThreads) sums[i] = 0.0f;
+  for (int i = threadIdx.x; i < NW * kSums * D; i += kThreads) sums[i] = 0.0f;
   __syncthreads();
 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -113,10 +140,17 @@ __global__ void __launch_bounds__(NW * 64) mlp_adjoint_kernel(const MlpAdjArgs p
   if (row0 >= p.B) return;
   const int64_t row = row0 + n < p.B ? row0 + n : p.B - 1;
   const float own_row = row0 + n < p.B ? 1.0f : 0.0f;     // (a shadow lane of the last partial wave adds nothing to the sums)
-  float* wave_sums = sums + wave * 2 * D;
+  float* wave_sums = sums + wave * kSums * D;
   const NoiseKey key = launch_key(p.key, p.key_dev);
   const uint32_t off_d = (uint32_t)(row * dT) + 4 * part, off_h = (uint32_t)(row * hT) + 4 * part;
   const uint64_t quad0 = (key.elem0 + (uint64_t)(row * dT) + 4 * part) >> 2;
+  // KL: the lane's first element of the field, quad-aligned on every fourth row only (normal4_straddle)
+  [[maybe_unused]] uint64_t elem0_lane = 0;
+  [[maybe_unused]] float al = 0.0f;
+  if constexpr (KL) {
+    elem0_lane = key.elem0 + (uint64_t)row * (uint64_t)p.bm_stride + 4 * part;
+    al = p.a_l[row];
+  }
   auto real_d = [&](int t) { return FULL || R * t + 4 * part < dT; };
   auto real_h = [&](int th) { return FULL || R * th + 4 * part < hT; };
   auto load_tile = [&](const float* base, int t) {
@@ -148,7 +182,7 @@ __global__ void __launch_bounds__(NW * 64) mlp_adjoint_kernel(const MlpAdjArgs p
 
 #pragma unroll
     for (int t = 0; t < TD; ++t) {
-      store_tile(p.stash_a + slot * p.B * dT, t, a[t] * dt);
+      if constexpr (!KL) store_tile(p.stash_a + slot * p.B * dT, t, a[t] * dt);     // (KL: once f is known, below)
       store_tile(p.stash_y + slot * p.B * dT, t, y[t]);
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -199,6 +233,33 @@ __global__ void __launch_bounds__(NW * 64) mlp_adjoint_kernel(const MlpAdjArgs p
       __builtin_amdgcn_sched_barrier(0);
     }
 
+    // ---- KL: the cotangent the drift network sees, a + w with w = a_l u / safe; dt (a + w) to the stash ------------------
+    [[maybe_unused]] f32x4 ap[KL ? TD : 1];
+    if constexpr (KL) {
+      auto cotangent = [&](auto is_sigmoid) {
+        constexpr bool kSigmoid = decltype(is_sigmoid)::value;
+#pragma unroll
+        for (int t = 0; t < TD; ++t) {
+          const int ch = R * t + 4 * part;
+          const f32x4 cq = lds_quad(cs, ch), eq = lds_quad(es, ch), bq = lds_quad(b2s, ch);
+          const f32x4 hrq = lds_quad(hrs, ch), hsq = lds_quad(hss, ch);
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float yt = y[t][r];
+            const float g = diffusion_value(kSigmoid, p.diff_amp, cq[r], eq[r], yt).g;
+            const float safe = stable_divisor(g);
+            const float uk = ((f[t][r] + bq[r]) - (hrq[r] * yt + hsq[r])) / safe;
+            const float wk = (al * uk) / safe;
+            ap[t][r] = real_d(t) ? a[t][r] + wk : a[t][r];       // (a padded channel: g may be 0 there; no share)
+          }
+          store_tile(p.stash_a + slot * p.B * dT, t, ap[t] * dt);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      };
+      if (sigmoid) cotangent(std::true_type{});
+      else cotangent(std::false_type{});
+    }
+
     // ---- u^T = W2 a^T (rows of W2s, four consecutive channels per lane); delta = u * act'(z) * dt --------------------
 #pragma unroll
     for (int th = 0; th < TH; ++th) {
@@ -207,7 +268,10 @@ __global__ void __launch_bounds__(NW * 64) mlp_adjoint_kernel(const MlpAdjArgs p
       for (int t = 0; t < TD; ++t) {
         const f32x4 w = *reinterpret_cast<const f32x4*>(&W2s[(R * th + n) * S2 + R * t + 4 * part]);
 #pragma unroll
-        for (int r = 0; r < 4; ++r) u = TL::mfma(w[r], a[t][r], u);
+        for (int r = 0; r < 4; ++r) {
+          if constexpr (KL) u = TL::mfma(w[r], ap[t][r], u);
+          else u = TL::mfma(w[r], a[t][r], u);
+        }
         if ((t + 1) % 4 == 0) __builtin_amdgcn_sched_barrier(0);
       }
       hid[th] = (u * hid[th]) * dt;
@@ -226,13 +290,25 @@ __global__ void __launch_bounds__(NW * 64) mlp_adjoint_kernel(const MlpAdjArgs p
       for (int t = 0; t < TD; ++t) {
         const int ch = R * t + 4 * part;
         float zn[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        uint64_t quad = quad0 + 4 * t;
-        asm volatile("" : "+v"(quad));          // (keeps the step-invariant first Philox round inside the loop)
-        if (real_d(t)) normal4_pairs<float>(key, quad, cell, 0, kStreamW, zn);
+        if constexpr (KL) {
+          uint64_t elem = elem0_lane + R * t;
+          asm volatile("" : "+v"(elem));
+          if (real_d(t)) normal4_straddle<float>(key, elem, cell, 0, kStreamW, zn);
+        } else {
+          uint64_t quad = quad0 + 4 * t;
+          asm volatile("" : "+v"(quad));          // (keeps the step-invariant first Philox round inside the loop)
+          if (real_d(t)) normal4_pairs<float>(key, quad, cell, 0, kStreamW, zn);
+        }
         const f32x4 cq = lds_quad(cs, ch);
         const f32x4 eq = lds_quad(es, ch);
         const f32x4 bq = lds_quad(b2s, ch);
+        [[maybe_unused]] f32x4 hrq, hsq;
+        if constexpr (KL) {
+          hrq = lds_quad(hrs, ch);
+          hsq = lds_quad(hss, ch);
+        }
         float rate_terms[4], shift_terms[4];
+        [[maybe_unused]] float hrate_terms[4], hshift_terms[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const float yt = y[t][r], at = a[t][r], cc = cq[r];
@@ -264,6 +340,20 @@ __global__ void __launch_bounds__(NW * 64) mlp_adjoint_kernel(const MlpAdjArgs p
             to_shift += av * (gp * q - g * dgp_de);
             to_rate += av * (gp * (q * yt) - g * dgp_dc);
           }
+          if constexpr (KL) {
+            // the column's share (see MlpAdjKlArgs): u and w as the cotangent phase formed them
+            const float safe = stable_divisor(g);
+            const float uk = ((f[t][r] + bq[r]) - (hrq[r] * yt + hsq[r])) / safe;
+            const float wk = (al * uk) / safe;
+            // a_l dt u^2 / safe: none where the divisor is clamped (d safe / d g = 0), none in a padded channel (g may be 0)
+            const float kq = (real_d(t) && fabsf(g) > 1e-7f) ? ((al * dt) * (uk * uk)) / safe : 0.0f;
+            const float dtw = real_d(t) ? dt * wk : 0.0f;
+            a1 = a1 - (hrq[r] * dtw + kq * gp);
+            to_shift -= kq * q;
+            to_rate -= (kq * q) * yt;
+            hrate_terms[r] = row_total(-(dtw * yt) * own_row);
+            hshift_terms[r] = row_total(-dtw * own_row);
+          }
           rate_terms[r] = row_total(to_rate * own_row);
           shift_terms[r] = row_total(to_shift * own_row);
           a[t][r] = a1;
@@ -279,6 +369,10 @@ __global__ void __launch_bounds__(NW * 64) mlp_adjoint_kernel(const MlpAdjArgs p
           for (int r = 0; r < 4; ++r) {
             atomicAdd(&wave_sums[ch + r], rate_terms[r]);
             atomicAdd(&wave_sums[D + ch + r], shift_terms[r]);
+            if constexpr (KL) {
+              atomicAdd(&wave_sums[2 * D + ch + r], hrate_terms[r]);
+              atomicAdd(&wave_sums[3 * D + ch + r], hshift_terms[r]);
+            }
           }
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -312,6 +406,10 @@ __global__ void __launch_bounds__(NW * 64) mlp_adjoint_kernel(const MlpAdjArgs p
   for (int i = lane; i < dT; i += 64) {
     p.row_rate[row0 * dT + i] += wave_sums[i];
     p.row_shift[row0 * dT + i] += wave_sums[D + i];
+    if constexpr (KL) {
+      p.row_hrate[row0 * dT + i] += wave_sums[2 * D + i];
+      p.row_hshift[row0 * dT + i] += wave_sums[3 * D + i];
+    }
   }
 }
 
@@ -377,12 +475,67 @@ static hipError_t launch_adj_h(const MlpAdjArgs& p, int act, hipStream_t s) {
   return hipErrorInvalidValue;
 }
 
-hipError_t launch_adjoint_mlp_diag(void* y, void* a, void* stash_a, void* stash_hid, void* stash_delta, void* stash_y,
-                                   void* row_rate, void* row_shift, int64_t rows, int64_t d, int64_t h, const void* W1,
-                                   const void* b1, const void* W2, const void* b2, const void* c, const void* e,
-                                   int diff_kind, double diff_amp, int act, int ito, const tsde_traj_t* tr, int32_t k_lo,
-                                   int32_t k_hi, NoiseKey key, const uint64_t* key_dev, hipStream_t s) {
-  MlpAdjArgs p;
+// The KL instantiation. Five state-sized register arrays are live across the u product (y, a, f, act'(z), a + w): at
+// d = hidden = 128 the 8-wave block spills 31-34 dwords (the aligned instantiation: 10), the 4-wave block none -- and the 8-wave
+// block is still the faster one (32768 x 128 x 500 forward + backward: 58.0 ms against 61.4 ms,
+// profiles/logqp_adjoint_ab.txt), so every shape runs as 8-wave blocks and TSDE_ADJ_WAVES does not reach this instantiation.
+template <int D, int H, int ACT, int NW, bool FULL, bool MILSTEIN>
+static hipError_t launch_adj_kl_scheme(const MlpAdjKlArgs& p, hipStream_t s) {
+  constexpr int R = 16;
+  const size_t lds_bytes =
+      (size_t)(D * (H + MlpLds<R>::kPad) + H * (D + MlpLds<R>::kPad) + H + 3 * D + NW * 4 * D + 2 * D) * sizeof(float);
+  static bool configured = false;   // per instantiation
+  if (!configured) {
+    const hipError_t e =
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_adjoint_kernel<D, H, ACT, NW, FULL, MILSTEIN, true>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    if (e != hipSuccess) return e;
+    configured = true;
+  }
+  const int64_t rows_per_block = NW * R;
+  const int64_t blocks = (p.B + rows_per_block - 1) / rows_per_block;
+  hipLaunchKernelGGL((mlp_adjoint_kernel<D, H, ACT, NW, FULL, MILSTEIN, true>), dim3((unsigned)blocks), dim3(NW * 64),
+                     lds_bytes, s, p);
+  return hipGetLastError();
+}
+
+template <int D, int H, int ACT, int NW>
+static hipError_t launch_adj_kl_waves(const MlpAdjKlArgs& p, hipStream_t s) {
+  const bool full = p.d == D && p.h == H, milstein = (p.ito & 2) != 0;
+  if (full)
+    return milstein ? launch_adj_kl_scheme<D, H, ACT, NW, true, true>(p, s)
+                    : launch_adj_kl_scheme<D, H, ACT, NW, true, false>(p, s);
+  return milstein ? launch_adj_kl_scheme<D, H, ACT, NW, false, true>(p, s)
+                  : launch_adj_kl_scheme<D, H, ACT, NW, false, false>(p, s);
+}
+
+template <int D, int H, int ACT>
+static hipError_t launch_adj_kl_shape(const MlpAdjKlArgs& p, hipStream_t s) {
+  return launch_adj_kl_waves<D, H, ACT, 8>(p, s);
+}
+
+template <int D, int H>
+static hipError_t launch_adj_kl_act(const MlpAdjKlArgs& p, int act, hipStream_t s) {
+  if (act == TSDE_ACT_TANH) return launch_adj_kl_shape<D, H, TSDE_ACT_TANH>(p, s);
+  if (act == TSDE_ACT_SOFTPLUS) return launch_adj_kl_shape<D, H, TSDE_ACT_SOFTPLUS>(p, s);
+  return hipErrorInvalidValue;
+}
+
+template <int D>
+static hipError_t launch_adj_kl_h(const MlpAdjKlArgs& p, int act, hipStream_t s) {
+  if (p.h <= 32) return launch_adj_kl_act<D, 32>(p, act, s);
+  if (p.h <= 64) return launch_adj_kl_act<D, 64>(p, act, s);
+  if (p.h <= 128) return launch_adj_kl_act<D, 128>(p, act, s);
+  if constexpr (D <= 64) {
+    if (p.h <= 256) return launch_adj_kl_act<D, 256>(p, act, s);
+  }
+  return hipErrorInvalidValue;
+}
+
+static void fill_adj_args(MlpAdjArgs& p, void* y, void* a, void* stash_a, void* stash_hid, void* stash_delta, void* stash_y,
+                          void* row_rate, void* row_shift, int64_t rows, int64_t d, int64_t h, const void* W1, const void* b1,
+                          const void* W2, const void* b2, const void* c, const void* e, int diff_kind, double diff_amp,
+                          int ito, const tsde_traj_t* tr, int32_t k_lo, int32_t k_hi, NoiseKey key, const uint64_t* key_dev) {
   p.y = (float*)y;
   p.a = (float*)a;
   p.stash_a = (float*)stash_a;
@@ -409,6 +562,39 @@ hipError_t launch_adjoint_mlp_diag(void* y, void* a, void* stash_a, void* stash_
   p.k_hi = k_hi;
   p.key = key;
   p.key_dev = key_dev;
+}
+
+hipError_t launch_adjoint_mlp_diag_logqp(void* y, void* a, const void* a_l, void* stash_a, void* stash_hid,
+                                         void* stash_delta, void* stash_y, void* row_rate, void* row_shift, void* row_hrate,
+                                         void* row_hshift, int64_t rows, int64_t d, int64_t h, const void* W1,
+                                         const void* b1, const void* W2, const void* b2, const void* c, const void* e,
+                                         const void* hr, const void* hs, int diff_kind, double diff_amp, int act, int ito,
+                                         const tsde_traj_t* tr, int32_t k_lo, int32_t k_hi, NoiseKey key,
+                                         const uint64_t* key_dev, hipStream_t s) {
+  MlpAdjKlArgs p;
+  fill_adj_args(p, y, a, stash_a, stash_hid, stash_delta, stash_y, row_rate, row_shift, rows, d, h, W1, b1, W2, b2, c, e,
+                diff_kind, diff_amp, ito, tr, k_lo, k_hi, key, key_dev);
+  p.a_l = (const float*)a_l;
+  p.hr = (const float*)hr;
+  p.hs = (const float*)hs;
+  p.row_hrate = (float*)row_hrate;
+  p.row_hshift = (float*)row_hshift;
+  p.bm_stride = d + 1;
+  if (rows <= 0 || k_hi <= k_lo) return hipSuccess;
+  if (d <= 32) return launch_adj_kl_h<32>(p, act, s);
+  if (d <= 64) return launch_adj_kl_h<64>(p, act, s);
+  if (d <= 128) return launch_adj_kl_h<128>(p, act, s);
+  return hipErrorInvalidValue;
+}
+
+hipError_t launch_adjoint_mlp_diag(void* y, void* a, void* stash_a, void* stash_hid, void* stash_delta, void* stash_y,
+                                   void* row_rate, void* row_shift, int64_t rows, int64_t d, int64_t h, const void* W1,
+                                   const void* b1, const void* W2, const void* b2, const void* c, const void* e,
+                                   int diff_kind, double diff_amp, int act, int ito, const tsde_traj_t* tr, int32_t k_lo,
+                                   int32_t k_hi, NoiseKey key, const uint64_t* key_dev, hipStream_t s) {
+  MlpAdjArgs p;
+  fill_adj_args(p, y, a, stash_a, stash_hid, stash_delta, stash_y, row_rate, row_shift, rows, d, h, W1, b1, W2, b2, c, e,
+                diff_kind, diff_amp, ito, tr, k_lo, k_hi, key, key_dev);
   if (rows <= 0 || k_hi <= k_lo) return hipSuccess;
   hipError_t r = hipErrorInvalidValue;
   if (d <= 32) r = launch_adj_h<32>(p, act, s);

@@ -54,6 +54,14 @@ struct MlpArgs {
   const uint64_t* key_dev;
 };
 
+// The KL instantiation (`sdeint_adjoint(..., logqp=True)`, base_sde.py:240-306 with a per-channel affine prior drift
+// h = hr * y + hs): the solve also carries l, the running integral of 0.5 |(f - h) / g|^2, one value per row.
+struct MlpKlArgs : MlpArgs {
+  const float *hr, *hs;     // (d) prior drift coefficients
+  float* logqp;             // (n_out, B): l at the outputs
+  int64_t bm_stride;        // row stride of the Brownian field: d + 1 (column d drives nothing)
+};
+
 
 // NW = waves per block: all of them share one copy of the weights in LDS.
 // SCHEME: 0 = the one-stage Euler / Milstein step, 1 = the two-stage Stratonovich midpoint scheme (midpoint.py:31-43),
@@ -61,8 +69,12 @@ struct MlpArgs {
 // FULL: d == D and h == H (no channel padding inside the kernel), which removes every per-tile bounds test.
 // IL: explicitly scheduled step (operand reads ahead of use, noise generation between the matrix instructions) for
 // one-stage schemes, unpadded shapes, 16-row waves: see the step loop. TSDE_MLP_INTERLEAVE=0 selects the plain form.
-template <int D, int H, int ACT, int R, int NW, int SCHEME, bool FULL, bool IL = false>
-__global__ void __launch_bounds__(NW * 64) mlp_trajectory_kernel(const MlpArgs p) {
+// KL: the logqp instantiation (MlpKlArgs; one-stage schemes, plain form): the extra column l of SDELogqp beside the state,
+// the Brownian increments drawn from a field of row stride d + 1.
+template <int D, int H, int ACT, int R, int NW, int SCHEME, bool FULL, bool IL = false, bool KL = false>
+__global__ void __launch_bounds__(NW * 64)
+    mlp_trajectory_kernel(const std::conditional_t<KL, MlpKlArgs, MlpArgs> p) {
+  static_assert(!KL || (SCHEME == 0 && !IL && R == 16), "KL instantiation: one-stage schemes, plain 16-row form");
   constexpr bool MID = SCHEME == 1, SRK = SCHEME == 2;
   using TL = Tile<R>;
   using acc_t = typename TL::acc_t;
@@ -78,6 +90,8 @@ __global__ void __launch_bounds__(NW * 64) mlp_trajectory_kernel(const MlpArgs p
   float* b2s = b1s + H;             // D
   float* cs = b2s + D;              // D
   float* es = cs + D;               // D
+  [[maybe_unused]] float* hrs = es + D;      // D  (KL) prior drift h = hr * y + hs
+  [[maybe_unused]] float* hss = hrs + D;     // D  (KL)
   // weights into LDS, zero-padded from (d, h) to the tile sizes (D, H): padded hidden units feed zero rows of W2 and
   // padded state channels have zero drift, zero diffusion and no noise, so they stay exactly 0
   const int dT = p.d, hT = p.h;
@@ -100,6 +114,10 @@ __global__ void __launch_bounds__(NW * 64) mlp_trajectory_kernel(const MlpArgs p
     b2s[i] = i < dT ? p.b2[i] : 0.0f;
     cs[i] = i < dT ? p.c[i] : 0.0f;
     es[i] = i < dT ? p.e[i] : 0.0f;
+    if constexpr (KL) {
+      hrs[i] = i < dT ? p.hr[i] : 0.0f;
+      hss[i] = i < dT ? p.hs[i] : 0.0f;
+    }
   }
   __syncthreads();
 
@@ -115,6 +133,10 @@ __global__ void __launch_bounds__(NW * 64) mlp_trajectory_kernel(const MlpArgs p
   // 64-bit address lives in vector registers across the solve (the C ABI keeps rows * d < 2^30).
   const uint32_t off_d = (uint32_t)(row * dT);
   const uint64_t quad_row = (key.elem0 + (uint64_t)(row * dT)) >> 2;      // RNG quad of channel 0 of this row
+  // KL: element (row, ch) of the field is elem_row + ch, quad-aligned on every fourth row only (normal4_straddle)
+  [[maybe_unused]] uint64_t elem_row = 0;
+  [[maybe_unused]] float logqp = 0.0f;                                     // l of this lane's row (every lane of a row: the same)
+  if constexpr (KL) elem_row = key.elem0 + (uint64_t)row * (uint64_t)p.bm_stride;
   auto real = [&](int ch) { return FULL || ch < dT; };                    // a quad of channels is real or padding
 
   // state in accumulator layout: y[t][r] = y(row, R t + TL::row(r, part))
@@ -438,6 +460,7 @@ __global__ void __launch_bounds__(NW * 64) mlp_trajectory_kernel(const MlpArgs p
     } else if constexpr (!MID) {
       // one stage; in place: tile t of the state is only read by its own update
       hidden_layer(y);
+      [[maybe_unused]] float kl = 0.0f;       // KL: this lane's share of sum_i u_i^2, u = (f - h) / g at y_k
 #pragma unroll
       for (int t = 0; t < TD; ++t) {
         const acc_t acc = drift_tile(t);
@@ -447,10 +470,21 @@ __global__ void __launch_bounds__(NW * 64) mlp_trajectory_kernel(const MlpArgs p
           float z[4] = {0.0f, 0.0f, 0.0f, 0.0f};
           // (opaque to the optimiser: otherwise the step-invariant first Philox round of every quad is hoisted out
           //  of the step loop and pinned in ~4 registers per quad)
-          uint64_t quad = quad_row + (ch >> 2);
-          asm volatile("" : "+v"(quad));
-          if (real(ch)) normal4_pairs<float>(key, quad, cell, 0, kStreamW, z);
+          if constexpr (KL) {
+            uint64_t elem = elem_row + ch;
+            asm volatile("" : "+v"(elem));
+            if (real(ch)) normal4_straddle<float>(key, elem, cell, 0, kStreamW, z);
+          } else {
+            uint64_t quad = quad_row + (ch >> 2);
+            asm volatile("" : "+v"(quad));
+            if (real(ch)) normal4_pairs<float>(key, quad, cell, 0, kStreamW, z);
+          }
           const f32x4 b2q = lds_quad(b2s, ch), cq = lds_quad(cs, ch), eq = lds_quad(es, ch);
+          [[maybe_unused]] f32x4 hrq, hsq;
+          if constexpr (KL) {
+            hrq = lds_quad(hrs, ch);
+            hsq = lds_quad(hss, ch);
+          }
           Pack<float, 4> o;
 #pragma unroll
           for (int s = 0; s < 4; ++s) {
@@ -460,6 +494,15 @@ __global__ void __launch_bounds__(NW * 64) mlp_trajectory_kernel(const MlpArgs p
             const float cc = cq[s];
             const DiffusionValue dv = diffusion_value(sigmoid_diffusion, p.diff_amp, cc, eq[s], yy);
             const float g = dv.g;
+            if constexpr (KL) {
+              // misc.stable_division (misc.py:66-68); a padded channel (g may be 0 there) has no share
+              const float safe = stable_divisor(g);
+              const float u = (f - (hrq[s] * yy + hsq[s])) / safe;
+              kl += real(ch) ? u * u : 0.0f;
+              // (materialised HERE: left alone, the compiler defers every term of the sum to the end of the step and keeps
+              //  its inputs alive until then -- 110 spilled dwords at d = hidden = 128 instead of none)
+              asm volatile("" : "+v"(kl));
+            }
             const float w = z[s] * sw;
             float yn;
             if (p.method == TSDE_TRAJ_EULER) {
@@ -473,6 +516,21 @@ __global__ void __launch_bounds__(NW * 64) mlp_trajectory_kernel(const MlpArgs p
           }
           if (due && real(ch)) emit(ch, o);
           __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+      if constexpr (KL) {
+        // the row's sum over the `part` lanes that hold it (lanes n, n + 16, n + 32, n + 48), in one fixed butterfly order:
+        // every lane of the row ends with the same total. The column's diffusion is 0, so Euler and Milstein both give
+        // l_{k+1} = l_k + f_l dt.
+        kl += __shfl_xor(kl, 16);
+        kl += __shfl_xor(kl, 32);
+        const float previous = logqp;
+        logqp = logqp + (0.5f * kl) * dt;
+        if (due && part == 0 && row0 + n < p.B) {
+          for (int j = jout; j < p.n_out && p.out_step[j] == k + 1; ++j) {
+            const float w0 = p.out_w[2 * j], w1 = p.out_w[2 * j + 1];
+            p.logqp[(int64_t)j * p.B + row] = (w0 == 0.0f && w1 == 1.0f) ? logqp : w0 * previous + w1 * logqp;
+          }
         }
       }
     } else {
@@ -621,11 +679,51 @@ static hipError_t launch_mlp_h(const MlpArgs& p, int act, hipStream_t s) {
   return hipErrorInvalidValue;
 }
 
-hipError_t launch_trajectory_mlp_diag(void* ys, const void* y0, int64_t rows, int64_t d, int64_t h, const void* W1,
-                                      const void* b1, const void* W2, const void* b2, const void* c, const void* e,
-                                      int diff_kind, double diff_amp, int act, int method, const tsde_traj_t* tr,
-                                      NoiseKey key, const uint64_t* key_dev, hipStream_t s) {
-  MlpArgs p;
+// The KL instantiation: the plain 16-row schedule in 8-wave blocks (TSDE_MLP_VARIANT / TSDE_MLP_INTERLEAVE do not reach it).
+template <int D, int H, int ACT, bool FULL>
+static hipError_t launch_mlp_kl_full(const MlpKlArgs& p, hipStream_t s) {
+  constexpr int R = 16, NW = 8;
+  const size_t lds_bytes = MlpLds<R>::bytes(D, H) + 2 * D * sizeof(float);
+  static bool configured = false;   // per instantiation
+  if (!configured) {
+    const hipError_t e =
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_trajectory_kernel<D, H, ACT, R, NW, 0, FULL, false, true>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    if (e != hipSuccess) return e;
+    configured = true;
+  }
+  const int64_t rows_per_block = NW * R;
+  const int64_t blocks = (p.B + rows_per_block - 1) / rows_per_block;
+  hipLaunchKernelGGL((mlp_trajectory_kernel<D, H, ACT, R, NW, 0, FULL, false, true>), dim3((unsigned)blocks), dim3(NW * 64),
+                     lds_bytes, s, p);
+  return hipGetLastError();
+}
+
+template <int D, int H>
+static hipError_t launch_mlp_kl_act(const MlpKlArgs& p, int act, hipStream_t s) {
+  const bool full = p.d == D && p.h == H;
+  if (act == TSDE_ACT_TANH)
+    return full ? launch_mlp_kl_full<D, H, TSDE_ACT_TANH, true>(p, s) : launch_mlp_kl_full<D, H, TSDE_ACT_TANH, false>(p, s);
+  if (act == TSDE_ACT_SOFTPLUS)
+    return full ? launch_mlp_kl_full<D, H, TSDE_ACT_SOFTPLUS, true>(p, s)
+                : launch_mlp_kl_full<D, H, TSDE_ACT_SOFTPLUS, false>(p, s);
+  return hipErrorInvalidValue;
+}
+
+template <int D>
+static hipError_t launch_mlp_kl_h(const MlpKlArgs& p, int act, hipStream_t s) {
+  if (p.h <= 32) return launch_mlp_kl_act<D, 32>(p, act, s);
+  if (p.h <= 64) return launch_mlp_kl_act<D, 64>(p, act, s);
+  if (p.h <= 128) return launch_mlp_kl_act<D, 128>(p, act, s);
+  if constexpr (D <= 64) {
+    if (p.h <= 256) return launch_mlp_kl_act<D, 256>(p, act, s);
+  }
+  return hipErrorInvalidValue;
+}
+
+static void fill_mlp_args(MlpArgs& p, void* ys, const void* y0, int64_t rows, int64_t d, int64_t h, const void* W1,
+                          const void* b1, const void* W2, const void* b2, const void* c, const void* e, int diff_kind,
+                          double diff_amp, int method, const tsde_traj_t* tr, NoiseKey key, const uint64_t* key_dev) {
   p.ys = (float*)ys;
   p.y0 = (const float*)y0;
   p.W1 = (const float*)W1;
@@ -648,6 +746,32 @@ hipError_t launch_trajectory_mlp_diag(void* ys, const void* y0, int64_t rows, in
   p.diff_amp = (float)diff_amp;
   p.key = key;
   p.key_dev = key_dev;
+}
+
+hipError_t launch_trajectory_mlp_diag_logqp(void* ys, void* logqp, const void* y0, int64_t rows, int64_t d, int64_t h,
+                                            const void* W1, const void* b1, const void* W2, const void* b2, const void* c,
+                                            const void* e, const void* hr, const void* hs, int diff_kind, double diff_amp,
+                                            int act, int method, const tsde_traj_t* tr, NoiseKey key,
+                                            const uint64_t* key_dev, hipStream_t s) {
+  MlpKlArgs p;
+  fill_mlp_args(p, ys, y0, rows, d, h, W1, b1, W2, b2, c, e, diff_kind, diff_amp, method, tr, key, key_dev);
+  p.hr = (const float*)hr;
+  p.hs = (const float*)hs;
+  p.logqp = (float*)logqp;
+  p.bm_stride = d + 1;
+  if (rows <= 0 || tr->n_steps <= 0) return hipSuccess;
+  if (d <= 32) return launch_mlp_kl_h<32>(p, act, s);
+  if (d <= 64) return launch_mlp_kl_h<64>(p, act, s);
+  if (d <= 128) return launch_mlp_kl_h<128>(p, act, s);
+  return hipErrorInvalidValue;
+}
+
+hipError_t launch_trajectory_mlp_diag(void* ys, const void* y0, int64_t rows, int64_t d, int64_t h, const void* W1,
+                                      const void* b1, const void* W2, const void* b2, const void* c, const void* e,
+                                      int diff_kind, double diff_amp, int act, int method, const tsde_traj_t* tr,
+                                      NoiseKey key, const uint64_t* key_dev, hipStream_t s) {
+  MlpArgs p;
+  fill_mlp_args(p, ys, y0, rows, d, h, W1, b1, W2, b2, c, e, diff_kind, diff_amp, method, tr, key, key_dev);
   if (rows <= 0 || tr->n_steps <= 0) return hipSuccess;
   if (d <= 32) return launch_mlp_h<32>(p, act, s);
   if (d <= 64) return launch_mlp_h<64>(p, act, s);

@@ -190,6 +190,11 @@ hipError_t launch_trajectory_mlp_diag(void* ys, const void* y0, int64_t rows, in
                                       const void* b1, const void* W2, const void* b2, const void* c, const void* e,
                                       int diff_kind, double diff_amp, int act, int method, const tsde_traj_t* tr,
                                       NoiseKey key, const uint64_t* key_dev, hipStream_t s);
+hipError_t launch_trajectory_mlp_diag_logqp(void* ys, void* logqp, const void* y0, int64_t rows, int64_t d, int64_t h,
+                                            const void* W1, const void* b1, const void* W2, const void* b2, const void* c,
+                                            const void* e, const void* hr, const void* hs, int diff_kind, double diff_amp,
+                                            int act, int method, const tsde_traj_t* tr, NoiseKey key,
+                                            const uint64_t* key_dev, hipStream_t s);
 // mlp_general.hip
 hipError_t launch_trajectory_mlp_general(void* ys, const void* y0, int64_t rows, int64_t d, int64_t m, int noise,
                                          const tsde_mlp_t* drift, const tsde_mlp_t* diffusion, int method,
@@ -213,6 +218,13 @@ hipError_t launch_adjoint_mlp_diag(void* y, void* a, void* stash_a, void* stash_
                                    const void* b1, const void* W2, const void* b2, const void* c, const void* e,
                                    int diff_kind, double diff_amp, int act, int ito, const tsde_traj_t* tr, int32_t k_lo,
                                    int32_t k_hi, NoiseKey key, const uint64_t* key_dev, hipStream_t s);
+hipError_t launch_adjoint_mlp_diag_logqp(void* y, void* a, const void* a_l, void* stash_a, void* stash_hid,
+                                         void* stash_delta, void* stash_y, void* row_rate, void* row_shift, void* row_hrate,
+                                         void* row_hshift, int64_t rows, int64_t d, int64_t h, const void* W1,
+                                         const void* b1, const void* W2, const void* b2, const void* c, const void* e,
+                                         const void* hr, const void* hs, int diff_kind, double diff_amp, int act, int ito,
+                                         const tsde_traj_t* tr, int32_t k_lo, int32_t k_hi, NoiseKey key,
+                                         const uint64_t* key_dev, hipStream_t s);
 hipError_t launch_gram_partials(void* partials, void* colsums, const void* A, int64_t lda, const void* Bm, int64_t ldb,
                                 int64_t K, int64_t M, int64_t N, int32_t blocks, hipStream_t s);
 // graph_nodes.hip: memset nodes of a captured, not yet instantiated graph -> fill-kernel nodes with the same edges

@@ -101,6 +101,13 @@ TSDE_D DiffusionValue diffusion_value(bool sigmoid, float amp, float c, float e,
   return v;
 }
 
+// The divisor of misc.stable_division (misc.py:66-68), which the KL column of a logqp solve divides f - h by: g itself, or
+// 1e-7 with g's sign where |g| <= 1e-7 (the reference's `sign`: 0 at 0).
+TSDE_D float stable_divisor(float g) {
+  const float sign = g > 0.0f ? 1.0f : (g < 0.0f ? -1.0f : 0.0f);
+  return fabsf(g) > 1e-7f ? g : 1e-7f * sign;
+}
+
 // ---- drift and diffusion perceptrons: mlp_general.hip, tsde_neural_rheun.h ------------------------------------------------
 
 // One normal of the field, out of line: the element-by-element paths (d % 4 != 0, m not a tile width, an unaligned field) are

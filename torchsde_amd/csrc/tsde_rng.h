@@ -240,6 +240,22 @@ TSDE_D void normal4_pairs(const NoiseKey& key, uint64_t quad, uint32_t cell, uin
   box_muller(r.z, r.w, n[2], n[3]);
 }
 
+// Four CONSECUTIVE normals of the field from any global element index `elem` (not a multiple of 4 in general: the rows of
+// a field whose row stride is no multiple of 4, the (B, d + 1) Brownian motion of a logqp solve): the two Philox quads
+// the four elements straddle, selected by elem & 3. Element for element what normal1 returns. Twice the work of
+// normal4_pairs; an aligned `elem` still draws both quads (the select is per lane, the draw is not).
+template <typename T>
+TSDE_D void normal4_straddle(const NoiseKey& key, uint64_t elem, uint32_t cell, uint64_t node, uint32_t stream, T (&n)[4]) {
+  T lo[4], hi[4];
+  normal4_pairs<T>(key, elem >> 2, cell, node, stream, lo);
+  normal4_pairs<T>(key, (elem >> 2) + 1, cell, node, stream, hi);
+  const uint32_t s = (uint32_t)elem & 3u;
+  n[0] = s == 0 ? lo[0] : s == 1 ? lo[1] : s == 2 ? lo[2] : lo[3];
+  n[1] = s == 0 ? lo[1] : s == 1 ? lo[2] : s == 2 ? lo[3] : hi[0];
+  n[2] = s == 0 ? lo[2] : s == 1 ? lo[3] : s == 2 ? hi[0] : hi[1];
+  n[3] = s == 0 ? lo[3] : s == 1 ? hi[0] : s == 2 ? hi[1] : hi[2];
+}
+
 // One standard normal for a single global element (generic / unaligned paths).
 template <typename T>
 TSDE_D T normal1(const NoiseKey& key, uint64_t elem, uint32_t cell, uint64_t node, uint32_t stream) {

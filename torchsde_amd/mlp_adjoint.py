@@ -10,6 +10,11 @@ per step on the MFMA units -- per chunk of steps, each followed by the two tall-
 (``tsde_gram_partials``) over that chunk's stash. Memory: the outputs plus O(chunk) stash, independent of the step
 count. Same Brownian path and the same arithmetic structure as the stepwise adjoint (adjoint.py), which remains the
 route for every other module, method and grid, and the parity reference for this one (tests/test_gpu_mlp_adjoint.py).
+
+``logqp=True`` (the KL column of the latent-SDE training pattern, base_sde.py:240-306) takes the KL instantiations of the same
+two kernels (``tsde_trajectory_mlp_diag_logqp``, ``tsde_adjoint_mlp_diag_logqp``) when the prior drift is per-channel affine
+in y and does not read t: `plan_logqp`, `_MlpLogqpAdjointFn`. The row sum of the column is an f32 sum in the kernel's own
+order, so this route agrees with the stepwise one to rounding, not bit for bit.
 """
 import numpy as np
 import torch
@@ -48,6 +53,44 @@ def adjoint_mlp_diag(y, a, stashes, row_rate, row_shift, w1, b1, w2, b2, rate, s
         (1 if ito else 0) | (2 if milstein else 0), schedule.struct(), int(k_lo), int(k_hi), bm._key, bm._elem0,
         None if entropy_dev is None else entropy_dev.data_ptr(), dt_code, stream)
     _native.check(code, "tsde_adjoint_mlp_diag")
+
+
+def trajectory_mlp_diag_logqp(ys, logqp, y0, w1, b1, w2, b2, rate, shift, prior_rate, prior_shift, activation, diffusion,
+                              method, schedule, bm):
+    """One launch of ``tsde_trajectory_mlp_diag_logqp``: ys (n_out, rows, d) and the KL column logqp (n_out, rows), the
+    increments from the (rows, d + 1) field of `bm`."""
+    tensors = (ys, logqp, y0, w1, b1, w2, b2, rate, shift, prior_rate, prior_shift)
+    _native.require_device(*tensors)
+    rows, d = y0.shape
+    hidden = b1.numel()
+    if any(t.dtype != torch.float32 or not t.is_contiguous() for t in tensors):
+        raise ValueError("the perceptron-drift kernel takes contiguous float32 tensors")
+    if (w1.shape != (d, hidden) or w2.shape != (hidden, d) or b2.numel() != d or ys.shape != (schedule.n_out, rows, d)
+            or logqp.shape != (schedule.n_out, rows) or any(t.numel() != d for t in (rate, shift, prior_rate, prior_shift))):
+        raise ValueError("shape mismatch: w1 (d, hidden), w2 (hidden, d), ys (n_out, rows, d), logqp (n_out, rows)")
+    lib, dt_code, stream = K._launch_env(y0)
+    code = lib.tsde_trajectory_mlp_diag_logqp(
+        ys.data_ptr(), logqp.data_ptr(), y0.data_ptr(), rows, d, hidden, w1.data_ptr(), b1.data_ptr(), w2.data_ptr(),
+        b2.data_ptr(), rate.data_ptr(), shift.data_ptr(), prior_rate.data_ptr(), prior_shift.data_ptr(), int(diffusion[0]),
+        float(diffusion[1]), int(activation), int(method), *_native.trajectory_tail(schedule, bm, dt_code, stream))
+    _native.check(code, "tsde_trajectory_mlp_diag_logqp")
+
+
+def adjoint_mlp_diag_logqp(y, a, a_l, stashes, row_sums, w1, b1, w2, b2, rate, shift, prior_rate, prior_shift, diffusion,
+                           activation, schedule, k_lo, k_hi, bm, milstein=False):
+    """One launch of ``tsde_adjoint_mlp_diag_logqp`` over steps k_hi-1 ... k_lo (y, a updated in place; a_l, the cotangent of
+    the KL column, read). `row_sums`: (row_rate, row_shift, row_prior_rate, row_prior_shift)."""
+    stash_a, stash_hid, stash_delta, stash_y = stashes
+    rows, d = y.shape
+    lib, dt_code, stream = K._launch_env(y)
+    entropy_dev = bm._entropy_dev
+    code = lib.tsde_adjoint_mlp_diag_logqp(
+        y.data_ptr(), a.data_ptr(), a_l.data_ptr(), stash_a.data_ptr(), stash_hid.data_ptr(), stash_delta.data_ptr(),
+        stash_y.data_ptr(), *(t.data_ptr() for t in row_sums), rows, d, b1.numel(), w1.data_ptr(), b1.data_ptr(),
+        w2.data_ptr(), b2.data_ptr(), rate.data_ptr(), shift.data_ptr(), prior_rate.data_ptr(), prior_shift.data_ptr(),
+        int(diffusion[0]), float(diffusion[1]), int(activation), 1 | (2 if milstein else 0), schedule.struct(), int(k_lo),
+        int(k_hi), bm._key, bm._elem0, None if entropy_dev is None else entropy_dev.data_ptr(), dt_code, stream)
+    _native.check(code, "tsde_adjoint_mlp_diag_logqp")
 
 
 class _MlpAdjointFn(torch.autograd.Function):
@@ -144,11 +187,272 @@ class _MlpAdjointFn(torch.autograd.Function):
         return (None,) * 9 + (a_y if ctx.needs_input_grad[9] else None, *grads)
 
 
+class _MlpLogqpAdjointFn(torch.autograd.Function):
+    """`_MlpAdjointFn` for ``logqp=True``: the state has the KL column l as its last column (contract.check_contract), the
+    prior drift is h = hr * y + hs. Forward: the KL instantiation of the sampling kernel. Backward: that of the adjoint
+    kernel, with a_l -- the cotangent of the column, constant between outputs -- carried through the output loop.
+
+    Inputs after `y0`: the module's six perceptron / diffusion tensors; `hr_t`, `hs_t`, which carry the user's graph from the
+    prior's own parameters (recognise.prior_coefficient_graph) and receive dL/dhr, dL/dhs; the coefficient VALUES the kernels
+    take (detached); then the prior's parameters themselves, which receive a gradient only from a backward pass that builds
+    a graph (``create_graph=True``: adjoint_double differentiates the user's code directly, and hr_t, hs_t get none)."""
+
+    N_PLAIN = 8                # arguments before y0
+
+    @staticmethod
+    def forward(ctx, activation, diffusion, method_code, backward_kind, schedule, backward_schedule, out_steps, bm, y0, w1,
+                b1, w2, b2, rate, shift, hr_t, hs_t, hr, hs, *prior_params):
+        rows, d = y0.shape[0], y0.shape[1] - 1
+        y0d = y0.detach()
+        coefs = [p.detach().reshape(-1).expand(d).contiguous() for p in (rate, shift)]
+        w1_in = w1.detach().t().contiguous()
+        w2_in = w2.detach().t().contiguous()
+        b1c, b2c = b1.detach().contiguous(), b2.detach().contiguous()
+        states = torch.empty((len(out_steps) + 1, rows, d), dtype=y0.dtype, device=y0.device)
+        states[0].copy_(y0d[:, :d])
+        column = torch.empty((len(out_steps), rows), dtype=y0.dtype, device=y0.device)
+        trajectory_mlp_diag_logqp(states[1:], column, states[0], w1_in, b1c, w2_in, b2c, coefs[0], coefs[1], hr, hs,
+                                  activation, diffusion, method_code, schedule, bm)
+        ys = torch.empty((len(out_steps) + 1, rows, d + 1), dtype=y0.dtype, device=y0.device)
+        ys[:, :, :d].copy_(states)
+        ys[0, :, d].copy_(y0d[:, d])
+        torch.add(column, y0d[:, d], out=ys[1:, :, d])
+        ctx.save_for_backward(states, w1_in, b1c, w2_in, b2c, coefs[0], coefs[1], hr, hs, ys)
+        ctx.activation, ctx.diffusion = int(activation), (int(diffusion[0]), float(diffusion[1]))
+        ctx.backward_kind = backward_kind
+        ctx.schedule, ctx.bm, ctx.out_steps = backward_schedule, bm, tuple(out_steps)
+        ctx.param_shapes = (tuple(rate.shape), tuple(shift.shape))
+        ctx.n_prior = len(prior_params)
+        ctx.generic = None
+        return ys
+
+    @staticmethod
+    def backward(ctx, gys):
+        if torch.is_grad_enabled():
+            return _MlpLogqpAdjointFn._backward_with_graph(ctx, gys)
+        states, w1_in, b1c, w2_in, b2c, rate, shift, hr, hs, _ = ctx.saved_tensors
+        rows, d = states.shape[1], states.shape[2]
+        hidden = b1c.numel()
+        dev = states.device
+        g_state = gys[:, :, :d].contiguous()
+        g_column = gys[:, :, d].contiguous()
+        per_step = rows * (2 * d + 2 * hidden) * 4
+        chunk = int(max(1, min(ctx.schedule.n_steps, _MlpAdjointFn.STASH_BYTES // max(per_step, 1))))
+        stashes = (torch.empty((chunk, rows, d), dtype=torch.float32, device=dev),
+                   torch.empty((chunk, rows, hidden), dtype=torch.float32, device=dev),
+                   torch.empty((chunk, rows, hidden), dtype=torch.float32, device=dev),
+                   torch.empty((chunk, rows, d), dtype=torch.float32, device=dev))
+        row_sums = tuple(torch.zeros((rows, d), dtype=torch.float32, device=dev) for _ in range(4))
+        g_w1 = torch.zeros((hidden, d), dtype=torch.float32, device=dev)
+        g_w2 = torch.zeros((d, hidden), dtype=torch.float32, device=dev)
+        g_b1 = torch.zeros(hidden, dtype=torch.float32, device=dev)
+        g_b2 = torch.zeros(d, dtype=torch.float32, device=dev)
+        boundaries = (0,) + ctx.out_steps
+        y = states[-1].clone()
+        a = g_state[-1].clone()
+        a_l = g_column[-1].clone()
+        for i in range(len(boundaries) - 1, 0, -1):
+            for k_hi in range(boundaries[i], boundaries[i - 1], -chunk):
+                k_lo = max(boundaries[i - 1], k_hi - chunk)
+                n = k_hi - k_lo
+                adjoint_mlp_diag_logqp(y, a, a_l, stashes, row_sums, w1_in, b1c, w2_in, b2c, rate, shift, hr, hs,
+                                       ctx.diffusion, ctx.activation, ctx.schedule, k_lo, k_hi, ctx.bm,
+                                       milstein=ctx.backward_kind == "milstein")
+                flat_a = stashes[0][:n].reshape(n * rows, d)
+                flat_hid = stashes[1][:n].reshape(n * rows, hidden)
+                flat_delta = stashes[2][:n].reshape(n * rows, hidden)
+                flat_y = stashes[3][:n].reshape(n * rows, d)
+                for g_w, g_b, lhs, rhs in ((g_w2, g_b2, flat_a, flat_hid), (g_w1, g_b1, flat_delta, flat_y)):
+                    weight, bias = K.gram(lhs, rhs, column_sums=True)
+                    g_w += weight
+                    g_b += bias
+            # adjoint.py:114-116, for the state and for the column alike
+            y.copy_(states[i - 1])
+            a += g_state[i - 1]
+            a_l += g_column[i - 1]
+        diffusion = []
+        for acc, shape in zip(row_sums[:2], ctx.param_shapes):
+            per_channel = acc.sum(dim=0)
+            diffusion.append(per_channel.reshape(shape) if int(np.prod(shape, dtype=np.int64)) == d and len(shape) == 1
+                             else per_channel.sum().reshape(shape))
+        grad_y0 = torch.cat((a, a_l.unsqueeze(1)), dim=1) if ctx.needs_input_grad[_MlpLogqpAdjointFn.N_PLAIN] else None
+        return ((None,) * _MlpLogqpAdjointFn.N_PLAIN
+                + (grad_y0, g_w1, g_b1, g_w2, g_b2, diffusion[0], diffusion[1], row_sums[2].sum(dim=0), row_sums[3].sum(dim=0),
+                   None, None) + (None,) * ctx.n_prior)
+
+    @staticmethod
+    def _backward_with_graph(ctx, gys):
+        from . import adjoint, adjoint_double
+        if ctx.generic is None:
+            raise NotImplementedError("torchsde_amd: no differentiable backward pass was prepared for this call.")
+        sde, ts_host, dt, own = ctx.generic          # own: the six tensors, then the prior's parameters
+        ys = ctx.saved_tensors[-1]
+        params = [p for p in own if p.requires_grad]
+        with _native.on_device_of(ys):
+            plan = adjoint._plan_backward(ts_host, dt, ctx.bm, ys.device)
+            a_y, a_theta = adjoint_double.run(adjoint.AdjointSDE(sde, params), ctx.backward_kind, ctx.bm, plan, ys, gys)
+        a_theta = iter(a_theta)
+        grads = [next(a_theta) if p.requires_grad else None for p in own]
+        return ((None,) * _MlpLogqpAdjointFn.N_PLAIN
+                + (a_y if ctx.needs_input_grad[_MlpLogqpAdjointFn.N_PLAIN] else None, *grads[:6], None, None, None, None,
+                   *grads[6:]))
+
+
+class LogqpRoute:
+    """One ``sdeint_adjoint(..., logqp=True)`` call's plan on the KL kernels (`plan_logqp`): `solve(y0)` launches it,
+    `record(fast, stepwise, y0)` files the verdict of a verifying solve (the interface of neural_rheun_route.Route)."""
+
+    def __init__(self, solver, args, own, prior_params, generic, ledger, key, trusted, reverify):
+        self.solver, self.args, self.own, self.prior_params, self.generic = solver, args, own, prior_params, generic
+        self.ledger, self.key, self.trusted, self.reverify = ledger, key, trusted, reverify
+
+    def solve(self, y0, z_holder=None):
+        from . import recognise
+        inner, t0, d, hr, hs = self.prior
+        hr_t, hs_t = recognise.prior_coefficient_graph(inner.h, t0, d, y0.dtype, y0.device)
+        ys = _MlpLogqpAdjointFn.apply(*self.args, y0, *self.own, hr_t, hs_t, hr, hs, *self.prior_params)
+        if ys.grad_fn is not None:
+            ys.grad_fn.generic = self.generic
+        return ys
+
+    def record(self, fast, stepwise, y0, extra_inputs=()):
+        verdict = self.solver._both_routes_agree(fast, stepwise, y0, "the KL perceptron kernels", network=True,
+                                                 extra_inputs=extra_inputs)
+        self.ledger.file(self.key, verdict, self.reverify)
+        if verdict is True:
+            self.ledger.name_kernel(self.key, "tsde_trajectory_mlp_diag_logqp + tsde_adjoint_mlp_diag_logqp")
+        return verdict
+
+
+def plan_logqp(sde, y0, ts, bm, method, adjoint_method, dt, adaptive, adjoint_adaptive, options, adjoint_options,
+               adjoint_params, extra_solver_state, solver):
+    """The `LogqpRoute` of ``sdeint_adjoint(sde, y0, ts, logqp=True)`` if the call can take the KL kernels, else None (it stays
+    on the stepwise stochastic adjoint). `sde` is ``ForwardSDE(SDELogqp([RenameMethodsSDE(] module [)]))`` and `y0` carries
+    the extra column (contract.check_contract). Conditions: everything `route` asks of the module -- an Ito SDE with diagonal
+    noise, drift ``lin2(act(lin1(y)))``, affine or sigmoid elementwise diffusion, the shape limits --, Euler or Milstein both
+    ways, outputs on step boundaries, a prior drift that is per-channel affine in y and does not read t
+    (recognise.recognise_prior), `adjoint_params` exactly the module's trainable parameters. `solver.recognised_perceptron`
+    cannot verify this call (its forward solve has a (B, d) state against a (B, d + 1) Brownian motion), so trust is earned
+    here as on the reversible-Heun route: the first solve of a (form, batch size, "logqp") on an SDE object runs BOTH routes,
+    returns the stepwise result and files the verdict of `solvers._both_routes_agree` -- values of ys and of the column,
+    gradients for y0 and every parameter. TSDE_VERIFY_EVERY applies; no verifying solve runs under stream capture."""
+    from . import recognise, trust
+    from .sde import ForwardSDE, RenameMethodsSDE, SDELogqp
+    from .settings import NOISE_TYPES
+    if (adaptive or adjoint_adaptive or extra_solver_state is not None or adjoint_method not in _BACKWARD_KINDS
+            or method not in (METHODS.euler, METHODS.milstein)
+            or adjoint_options.get(METHOD_OPTIONS.grad_free, False) or options.get(METHOD_OPTIONS.grad_free, False)
+            or not options.get("trajectory_kernel", True) or not adjoint_options.get("trajectory_kernel", True)
+            or not recognise.ENABLED or solver is None):
+        return None
+    wrapped = getattr(sde, "_base_sde", None)
+    if (type(sde) is not ForwardSDE or type(wrapped) is not SDELogqp or sde.sde_type != SDE_TYPES.ito
+            or sde.noise_type != NOISE_TYPES.diagonal or sde.user_product):
+        return None
+    inner = wrapped._base_sde
+    module = inner._base_sde if type(inner) is RenameMethodsSDE else inner
+    if not isinstance(module, torch.nn.Module) or hasattr(module, "_base_sde") or not hasattr(inner, "h"):
+        return None
+    code = _FORWARD_CODES[(method, SDE_TYPES.ito)]
+    if (not isinstance(bm, BrownianInterval) or bm._rootW is not None or bm._rootH is not None or bm._snap or y0.dim() != 2
+            or not y0.is_cuda or y0.shape[1] < 2 or tuple(bm.shape) != tuple(y0.shape) or y0.dtype != torch.float32
+            or bm.dtype != torch.float32 or ts.dtype != y0.dtype or y0.numel() == 0):
+        return None
+    d = y0.shape[1] - 1
+    ledger = trust.open_book(solver, who=type(solver).__name__ + ":KL perceptron kernels")
+    if ledger is None or ledger.refused():
+        return None
+    state = y0.detach()[:, :d]
+    inner_forward = ForwardSDE(inner)
+    if inner_forward.user_product:
+        return None
+
+    def interpret(rows=None):
+        found = recognise.recognise(inner_forward, ts[0], state, differentiable=True, rows=rows)
+        if not found.perceptron:
+            raise recognise.NotElementwise("the drift is not a two-layer perceptron of y beside an elementwise diffusion")
+        return found, found.perceptron_spec(), recognise.recognise_prior(inner.h, ts[0], state, differentiable=True, rows=rows)
+
+    try:
+        found, spec, (hr, hs) = interpret()
+    except recognise.NotElementwise as e:
+        return ledger.refuse(str(e))
+    own = found.perceptron_parameters()
+    if own is None:
+        return None
+    hidden = own[1].numel()
+    # gradients go to exactly the module's trainable parameters: the six tensors of drift and diffusion, and whatever else
+    # the module holds -- which can only reach the solve through the prior (f and g are the recognised forms over `own`)
+    module_params = list(module.parameters())
+    module_ids = {id(p) for p in module_params}
+    own_ids = {id(p) for p in own}
+    if ({id(p) for p in adjoint_params} != {id(p) for p in module_params if p.requires_grad}
+            or any(p.requires_grad and id(p) not in module_ids for p in own)
+            or hidden % 4 != 0 or y0.shape[0] * (max(d, hidden) + 1) >= 2 ** 30):
+        return None
+    prior_params = [p for p in module_params if id(p) not in own_ids and p.requires_grad]
+
+    # ---- grids: every output on a forward step boundary, every backward step exactly one forward cell ------------------
+    ts_host = timegrid.ts_to_host(ts)
+    grid = timegrid.build(ts_host, dt)
+    if grid.n_steps == 0 or any(not (w0 == 0.0 and w1 == 1.0) for (_, _, w0, w1) in grid.outputs):
+        return None
+    steps = K.solve_steps(grid, bm)
+    if steps is None:
+        return None
+    backward_dt = K.backward_step_sizes(bm, ts_host, dt, steps.cells, steps.out_step)
+    if backward_dt is None:
+        return None
+
+    def shape_of(c):
+        return "number" if isinstance(c, (bool, int, float)) else tuple(c.shape)
+
+    key = ledger.key(found, y0, "logqp", method, adjoint_method, shape_of(hr), shape_of(hs))
+    verdict, reverify = ledger.verdict(key)
+    if verdict is not None and verdict is not True:
+        return None
+    if verdict is None:
+        # the verifying solve: a second interpretation on a probe of another height must find the same forms over the same
+        # tensors, and the calls must leave the object's Python-side state and the random generators alone
+        if torch.cuda.is_current_stream_capturing():
+            return None
+        snapshot = ledger.snapshot(y0.device)
+        if snapshot[0] is None:
+            return None
+        try:
+            again, again_spec, (hr5, hs5) = interpret(rows=5)
+        except recognise.NotElementwise as e:
+            return ledger.refuse(str(e))
+        own5 = again.perceptron_parameters()
+        same = (again.structure() == found.structure() and again_spec[-2:] == spec[-2:] and own5 is not None
+                and all(x is y or (not x.requires_grad and torch.equal(x, y)) for x, y in zip(own5, own))
+                and all(shape_of(x) == shape_of(y) and bool((recognise.prior_vector(x, d, y0.dtype, y0.device)
+                                                             == recognise.prior_vector(y, d, y0.dtype, y0.device)).all())
+                        for x, y in ((hr, hr5), (hs, hs5))))
+        if not same:
+            ledger.file(key, "two interpretations of the same code (probes of 2 and 5 rows) found different forms", reverify)
+            return None
+        side_effect = ledger.side_effect(snapshot, y0.device)
+        if side_effect is not None:
+            return ledger.refuse(side_effect)
+    schedule = steps.schedule(y0.device, y0.dtype)
+    backward_schedule = steps.schedule(y0.device, y0.dtype, dt=backward_dt)
+    args = (spec[-2], tuple(spec[-1]), code, _BACKWARD_KINDS[adjoint_method], schedule, backward_schedule,
+            tuple(int(k) for k in steps.out_step), bm)
+    plan = LogqpRoute(solver, args, own, prior_params, (sde, ts_host, dt, list(own) + prior_params), ledger, key,
+                      verdict is True, reverify)
+    plan.prior = (inner, ts[0], d, recognise.prior_vector(hr, d, y0.dtype, y0.device),
+                  recognise.prior_vector(hs, d, y0.dtype, y0.device))
+    return plan
+
+
 def route(sde, y0, ts, bm, method, adjoint_method, dt, adaptive, adjoint_adaptive, options, adjoint_options,
-          adjoint_params, extra_solver_state, solver=None):
+          adjoint_params, extra_solver_state, solver=None, logqp=False):
     """`ys` with a grad_fn towards y0 and the module's six parameters if this call can take the kernels above, else
-    None (the caller then runs the stepwise stochastic adjoint)."""
+    None (the caller then runs the stepwise stochastic adjoint). ``logqp=True`` is `plan_logqp`'s business."""
     from .sde import ForwardSDE
+    if logqp:
+        return None
     if (adaptive or adjoint_adaptive or extra_solver_state is not None or adjoint_method not in _BACKWARD_KINDS
             or adjoint_options.get(METHOD_OPTIONS.grad_free, False) or options.get(METHOD_OPTIONS.grad_free, False)
             or not options.get("trajectory_kernel", True) or not adjoint_options.get("trajectory_kernel", True)):

@@ -1591,3 +1591,72 @@ def recognise(sde, t, y0, differentiable=False, times=None, rows=None):
     found.users_tensors = interp.seen
     found._alive = interp.keep        # (the ids above stay meaningful for as long as this object lives)
     return found
+
+
+# ---- the prior drift of a logqp solve (mlp_adjoint.py: the KL instantiations of the perceptron kernels) ---------------------------
+def recognise_prior(h, t, y0, differentiable=False, rows=None):
+    """Interpret the prior drift ``h(t, y)`` of a ``logqp=True`` solve alone, on a probe of the width of `y0`, as a per-channel
+    AFFINE function of the state that does not read t: returns ``(hr, hs)`` with ``h = hr * y + hs``, each a Python number or a
+    tensor of one element, of shape (d,) or (1, d) -- the user's own tensor, or one folded from theirs (``-self.theta``,
+    ``self.theta * self.mu``). Anything else raises `NotElementwise` with the reason: another function of the state
+    (``tanh(y)``), a network, a use of t, a stop-gradient when the gradients will stand for autograd (`differentiable`)."""
+    rows = 2 if rows is None else int(rows)
+    if rows == y0.shape[0]:
+        rows += 1
+    d = y0.shape[1]
+    probe = y0.detach()[:1].expand(rows, d).clone() if y0.shape[0] > 0 else torch.zeros(rows, d, dtype=y0.dtype,
+                                                                                       device=y0.device)
+    t_probe = t.detach().clone() if torch.is_tensor(t) else torch.tensor(float(t), dtype=y0.dtype, device=y0.device)
+    if differentiable:
+        probe.requires_grad_(True)
+    interp = _Interpreter(probe, t_probe, rows, d)
+    interp.differentiable = bool(differentiable)
+    try:
+        with (torch.enable_grad() if differentiable else torch.no_grad()), interp:
+            value = h(t_probe, probe)
+    except DependsOnTime:
+        raise NotElementwise("the prior drift depends on t") from None
+    except NotElementwise:
+        raise
+    except Exception as e:
+        raise NotElementwise(f"{type(e).__name__}: {e}") from None
+    form = interp.form_of(value)
+    if not isinstance(form, _Form):
+        raise NotElementwise("the prior drift is not a per-channel function of the state (a network, or no function of it "
+                             "that the interpretation follows)")
+    interp.check_stop_gradient((value,), where="the prior drift")
+    if form.constant():
+        hr, hs = 0.0, _add(form.shift, form.offset)
+    elif form.phi == "identity" and form.scale is None and form.offset is None:
+        hr, hs = form.rate, form.shift
+    else:
+        raise NotElementwise(f"a {form.phi} prior drift: the KL kernels take hr * y + hs only")
+    hr = 1.0 if hr is None else hr
+    hs = 0.0 if hs is None else hs
+    for c in (hr, hs):
+        if isinstance(c, (bool, int, float)):
+            continue
+        if not torch.is_tensor(c) or id(c) in interp.time or not (c.numel() == 1 or tuple(c.shape) in ((d,), (1, d))):
+            raise NotElementwise("a coefficient of the prior drift is not one value per channel")
+        if not c.is_floating_point():
+            raise NotElementwise(f"a coefficient of the prior drift of dtype {c.dtype}")
+    return hr, hs
+
+
+def prior_vector(c, d, dtype, device):
+    """One coefficient of `recognise_prior` as a detached, contiguous (d,) tensor."""
+    if isinstance(c, (bool, int, float)):
+        return _constant_vector(float(c), d, dtype, device)
+    return c.detach().to(device=device, dtype=dtype).reshape(-1).expand(d).contiguous()
+
+
+def prior_coefficient_graph(h, t, d, dtype, device):
+    """``(hr_t, hs_t)``, (d,) tensors with ``h(t, y) = hr_t * y + hs_t`` for an affine h, computed BY the user's code under
+    autograd -- ``hs_t = h(t, 0)``, ``hr_t = h(t, 1) - hs_t`` -- so that they carry the graph back to whatever parameters
+    the coefficients derive from (``theta``, ``mu``), however the code derives them: a gradient handed to these two reaches
+    those parameters by ordinary back-propagation, no symbolic chain rule. Their VALUES carry one rounding more than the
+    coefficients `recognise_prior` returns; the kernels take those."""
+    with torch.enable_grad():
+        hs_t = h(t, torch.zeros(1, d, dtype=dtype, device=device)).reshape(d)
+        hr_t = h(t, torch.ones(1, d, dtype=dtype, device=device)).reshape(d) - hs_t
+    return hr_t, hs_t

@@ -102,6 +102,7 @@ int main() {
   traj.out_w = to_device(out_w);
   traj.n_steps = n_steps;
   traj.n_out = 1;
+  traj.flags = TSDE_TRAJ_POW2_STEPS;          // dt = 2^-8 and sqrt(h) = 2^-4 in every row (0: nothing known about the rows)
   float* coef[4];
   const float values[4] = {mu, 0.0f, sigma, 0.0f};      // drift rate, drift shift, diffusion rate, diffusion shift
   for (int i = 0; i < 4; ++i) coef[i] = to_device(std::vector<float>(d, values[i]));

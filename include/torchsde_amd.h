@@ -81,7 +81,24 @@ typedef struct tsde_seg {
  * Brownian cell `cells[k]`; step k must cover exactly that cell; the last slot may carry t_k, the step's start time,
  * which only tsde_trajectory_mlp_general reads). Output j (the j-th requested time after
  * t0) is written once `out_step[j]` steps are complete, as w0*y_prev + w1*y_curr with the weights of row j
- * of `out_w` ((0,1) = the step lands on the output time). `out_step` is ascending. */
+ * of `out_w` ((0,1) = the step lands on the output time). `out_step` is ascending.
+ *
+ * `flags` (appended; 0 = the behaviour of a struct without it) holds what the caller knows about the rows, which are
+ * device memory the library cannot look at:
+ *   TSDE_TRAJ_POW2_STEPS  every row's dt_k (slot 0) and sqrt(h_k) (slot 4), as stored in `dtype`, are exact powers of two
+ *                         with 2^-52 <= dt_k <= 2^52 and 2^-26 <= sqrt(h_k) <= 2^26, and slot 1 is exactly dt_k/2. Scaling by
+ *                         such a number is exact, so tsde_trajectory_affine_diag (float32, Euler and midpoint, values only,
+ *                         constant coefficients) folds the two scalings of a step into fused multiply-adds:
+ *                           y + f*dt + g*(z*sqrt(h))  ->  fma(g*z, sqrt(h), fma(f, dt, y))      (z: the standard normal)
+ *                         The result is the same float, bit for bit, as long as neither product (f*dt, g*z*sqrt(h)) is
+ *                         subnormal: a nonzero |z| of the generator is far above 2^-100, hence z*sqrt(h) is never
+ *                         subnormal inside the range above; the products with f and g are below 2^-126 only for
+ *                         |a*y| or |c*y| below about 2^-126 / (|z| sqrt(h)), and there the folded form rounds once fewer:
+ *                         a subnormal product carries an error of at most 2^-150 into the sums of the plain form and none
+ *                         here, a few units in the last place of a state that small (2^-149 once it is subnormal). The
+ *                         caller vouches for the bit: a wrong bit changes the rounding of a step and nothing else. Every
+ *                         other entry point ignores it. */
+#define TSDE_TRAJ_POW2_STEPS 1u
 typedef struct tsde_traj {
   const void* step_rows;   /* [n_steps][8], dtype */
   const uint32_t* cells;   /* [n_steps] */
@@ -89,6 +106,7 @@ typedef struct tsde_traj {
   const void* out_w;       /* [n_out][2], dtype */
   int32_t n_steps;
   int32_t n_out;
+  uint32_t flags;          /* TSDE_TRAJ_* bits; a zeroed field is the plain arithmetic */
 } tsde_traj_t;
 
 int tsde_abi_version(void);

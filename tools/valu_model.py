@@ -29,12 +29,18 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-def affine_symbol(method, width=4, timed=False, linear=None):
-    """trajectory_kernel<float, METHOD, W, /*SENS=*/false, TIMED, LINEAR> (METHOD: include/torchsde_amd.h TSDE_TRAJ_*).
+POW2_METHODS = (0, 3)       # TSDE_TRAJ_EULER, TSDE_TRAJ_MIDPOINT: the schemes that have the folded step (csrc/trajectory.hip POW2)
+
+
+def affine_symbol(method, width=4, timed=False, linear=None, pow2=None):
+    """trajectory_kernel<float, METHOD, W, /*SENS=*/false, TIMED, LINEAR, POW2> (METHOD: include/torchsde_amd.h TSDE_TRAJ_*).
     `linear`: the form without shifts, f = rate * y -- what geometric Brownian motion (bench.py's gbm_* workloads) runs and
-    therefore the default for constant coefficients; `linear=False` names the general form, f = rate * y + shift."""
+    therefore the default for constant coefficients; `linear=False` names the general form, f = rate * y + shift.
+    `pow2`: the form for steps whose dt and sqrt(h) are powers of two (TSDE_TRAJ_POW2_STEPS) -- what a dyadic step size
+    runs (bench.py's dt = 2^-10) and therefore the default where it exists: Euler and midpoint with constant coefficients."""
     linear = (not timed) if linear is None else bool(linear)
-    return f"_ZN4tsde17trajectory_kernelIfLi{method}ELi{width}ELb0ELb{int(timed)}ELb{int(linear)}EEEvNS_8TrajArgsIT_EE"
+    pow2 = (not timed and method in POW2_METHODS) if pow2 is None else bool(pow2)
+    return (f"_ZN4tsde17trajectory_kernelIfLi{method}ELi{width}ELb0ELb{int(timed)}ELb{int(linear)}ELb{int(pow2)}EEEvNS_8TrajArgsIT_EE")
 
 
 HEADLINE_SYMBOL = affine_symbol(0)
@@ -173,14 +179,16 @@ def model(symbol=HEADLINE_SYMBOL, rates_path=None, source="trajectory.hip", elem
 
 def all_affine(rates_path=None):
     """The models of the constant-coefficient affine kernels (Euler, Milstein Ito / Stratonovich, midpoint, SRK, Heun,
-    Euler-Heun; one 16-byte group per lane), linear and general form of each, from one compilation."""
+    Euler-Heun; one 16-byte group per lane), linear and general form of each -- and of Euler and midpoint the plain step
+    and the one folded for power-of-two steps -- from one compilation."""
     import bench
     asm = device_asm()
     kernels = {}
     for linear in (True, False):
         for method in range(7):        # TSDE_TRAJ_EULER .. TSDE_TRAJ_EULER_HEUN
-            symbol = affine_symbol(method, linear=linear)
-            kernels[symbol] = model(symbol, rates_path, asm=asm)
+            for pow2 in ((True, False) if method in POW2_METHODS else (False,)):
+                symbol = affine_symbol(method, linear=linear, pow2=pow2)
+                kernels[symbol] = model(symbol, rates_path, asm=asm)
     return {"csrc_sha": bench.csrc_digest(), "kernels": kernels}
 
 

@@ -24,6 +24,7 @@ PRECISION_F32, PRECISION_BF16X3 = 0, 1
 NOISE_DIAGONAL, NOISE_SCALAR, NOISE_GENERAL, NOISE_ADDITIVE = 0, 1, 2, 3
 TRAJ_EULER, TRAJ_MILSTEIN_ITO, TRAJ_MILSTEIN_STRAT, TRAJ_MIDPOINT, TRAJ_SRK, TRAJ_HEUN, TRAJ_EULER_HEUN = 0, 1, 2, 3, 4, 5, 6
 TRAJ_REVERSIBLE_HEUN = 7
+TRAJ_POW2_STEPS = 1      # tsde_traj_t.flags: every row's dt and sqrt(h) are powers of two (include/torchsde_amd.h)
 TRAJ_MILSTEIN_ITO_GF, TRAJ_MILSTEIN_STRAT_GF = 8, 9      # derivative-free Milstein: `tsde_trajectory_mlp_general` only
 FN_CODES = {"identity": 0, "exp": 1, "sigmoid": 2, "tanh": 3, "softplus": 4, "sin": 5, "cos": 6, "poly3": 7}
 
@@ -66,7 +67,7 @@ class Seg(ctypes.Structure):
 class Traj(ctypes.Structure):
     """``tsde_traj_t``."""
     _fields_ = [("step_rows", _c_ptr), ("cells", _c_ptr), ("out_step", _c_ptr), ("out_w", _c_ptr),
-                ("n_steps", ctypes.c_int32), ("n_out", ctypes.c_int32)]
+                ("n_steps", ctypes.c_int32), ("n_out", ctypes.c_int32), ("flags", _c_u32)]
 
 
 class Mlp(ctypes.Structure):

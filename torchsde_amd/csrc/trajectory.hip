@@ -257,6 +257,20 @@ TSDE_D S scheme_step(const S y, const M& m, const N w, const N u, const T dt, co
   }
 }
 
+// The Euler and midpoint steps of `scheme_step` on steps whose dt and sqrt(h) are powers of two (TSDE_TRAJ_POW2_STEPS): `z`
+// is the UNSCALED standard normal, `sw` = sqrt(h) and `half_sw` = sqrt(h)/2 (midpoint only). The same floats, bit for bit, in
+// the domain `drift_diffusion_update_pow2` states. Values only.
+template <typename T, int METHOD, typename M>
+TSDE_D T scheme_step_pow2(const T y, const M& m, const T z, const T dt, const T half_dt, const T sw, const T half_sw) {
+  static_assert(METHOD == kEuler || METHOD == kMidpoint, "the folded step exists for Euler and midpoint");
+  if constexpr (METHOD == kEuler) {
+    return drift_diffusion_update_pow2<T>(y, m.template f<0>(y), m.template g<0>(y), z, dt, sw);
+  } else {
+    const T yp = drift_diffusion_update_pow2<T>(y, m.template f<0>(y), m.template g<0>(y), z, half_dt, half_sw);
+    return drift_diffusion_update_pow2<T>(y, m.template f<1>(yp), m.template g<1>(yp), z, dt, sw);
+  }
+}
+
 // A shift that is zero by construction (the LINEAR form, f = a*x, g = c*x: geometric Brownian motion, any user module
 // recognised as `mu * y`, `sigma * y`): it occupies no register and `x + NoShift{}` is x, no instruction. The stepwise
 // route evaluates such a module with no addition at all; against `x + 0` the only difference is the sign of a zero.
@@ -427,10 +441,12 @@ TSDE_D StepRow<T> step_row(const T* row, const uint32_t* cells, int k) {
 }
 
 // W = z sqrt(h) and, NEED_U (SRK), U = h (W / 2 + z' sqrt(h / 12)) from standard normals z of stream W and z' of stream H,
-// for the single element `elem`.
-template <typename T, bool NEED_U, typename Noise>
+// for the single element `elem`. !SCALED (the POW2 form of the affine kernel, whose step applies sqrt(h) itself): `w` = z.
+template <typename T, bool NEED_U, bool SCALED = true, typename Noise>
 TSDE_D void draw_one(const Noise& noise, const StepRow<T>& r, uint64_t elem, T& w, T& u) {
-  w = noise.template normal1<T>(elem, kStreamW) * r.sw;
+  static_assert(SCALED || !NEED_U, "U is made from the scaled W");
+  const T z = noise.template normal1<T>(elem, kStreamW);
+  w = SCALED ? z * r.sw : z;
   if constexpr (NEED_U) u = r.th * ((T)0.5 * w + noise.template normal1<T>(elem, kStreamH) * r.sh);
 }
 
@@ -439,12 +455,12 @@ TSDE_D void draw_one(const Noise& noise, const StepRow<T>& r, uint64_t elem, T& 
 // kernel, whose registers the shared series costs a wave (profiles/bm_shared_series_resource_usage_notes.txt). Otherwise
 // element by element: one element per lane, or (W = d, a generated row model: specialise.py) a lane that owns a whole ROW
 // of a small coupled system and draws its d increments one by one. `row_noise` (scalar noise): `elem` is the lane's row and
-// all W elements meet its one increment.
-template <typename T, int W, bool NEED_U, bool PAIRS, typename Noise>
+// all W elements meet its one increment. !SCALED: as `draw_one`, the unscaled normals on every path.
+template <typename T, int W, bool NEED_U, bool PAIRS, bool SCALED = true, typename Noise>
 TSDE_D void draw_increment(const Noise& noise, const StepRow<T>& r, uint64_t elem, bool row_noise, T (&w)[W], T (&u)[W]) {
   if (row_noise) {
     T w_row, u_row;
-    draw_one<T, NEED_U>(noise, r, elem, w_row, u_row);
+    draw_one<T, NEED_U, SCALED>(noise, r, elem, w_row, u_row);
 #pragma unroll
     for (int q = 0; q < W; ++q) {
       w[q] = w_row;
@@ -455,7 +471,7 @@ TSDE_D void draw_increment(const Noise& noise, const StepRow<T>& r, uint64_t ele
     if constexpr (PAIRS) noise.normal4_pairs(elem >> 2, kStreamW, z);
     else noise.normal4(elem >> 2, kStreamW, z);
 #pragma unroll
-    for (int q = 0; q < 4; ++q) w[q] = z[q] * r.sw;
+    for (int q = 0; q < 4; ++q) w[q] = SCALED ? z[q] * r.sw : z[q];
     if constexpr (NEED_U) {
       if constexpr (PAIRS) noise.normal4_pairs(elem >> 2, kStreamH, z);
       else noise.normal4(elem >> 2, kStreamH, z);
@@ -464,7 +480,7 @@ TSDE_D void draw_increment(const Noise& noise, const StepRow<T>& r, uint64_t ele
     }
   } else {
 #pragma unroll
-    for (int q = 0; q < W; ++q) draw_one<T, NEED_U>(noise, r, elem + (uint64_t)q, w[q], u[q]);
+    for (int q = 0; q < W; ++q) draw_one<T, NEED_U, SCALED>(noise, r, elem + (uint64_t)q, w[q], u[q]);
   }
 }
 
@@ -498,9 +514,18 @@ TSDE_D void emit_outputs(const Args& p, int64_t i, int k, int& j, int& next_out,
 //        separate instantiation, so the constant-coefficient kernels are untouched.
 // LINEAR: both shifts are zero (`p.b`, `p.e` are null and never read): f = a*y, g = c*y. Chosen by the host, values only,
 //        constant coefficients only -- the sensitivity kernels carry d/db and d/de, which are live at a zero shift too.
-template <typename T, int METHOD, int W, bool SENS, bool TIMED = false, bool LINEAR = false>
+// POW2:  every step's dt and sqrt(h) are powers of two (the schedule's TSDE_TRAJ_POW2_STEPS: the host looked at the rows, the
+//        launcher chooses). The draw hands out the unscaled normals and the step folds both scalings into fused multiply-adds
+//        (`scheme_step_pow2`): 4 multiplies and 2 fmas per element of an Euler step in place of 6 multiplies and 2 adds. Bit
+//        for bit the plain form's floats unless a product f*dt or g*z*sqrt(h) is subnormal -- |a*y| or |c*y| below about
+//        2^-126 / (|z| sqrt(h)) -- where this form rounds once fewer (a few units in the last place of a state that small);
+//        no per-element guard, which would cost more than the fold saves. Euler and midpoint, float32, values only, constant
+//        coefficients; with or without shifts. Milstein, Heun, Euler-Heun and float64 have no folded step yet.
+template <typename T, int METHOD, int W, bool SENS, bool TIMED = false, bool LINEAR = false, bool POW2 = false>
 __global__ void __launch_bounds__(kBlock) trajectory_kernel(const TrajArgs<T> p) {
   static_assert(!LINEAR || (!SENS && !TIMED), "the linear form: values only, constant coefficients");
+  static_assert(!POW2 || (!SENS && !TIMED && (METHOD == kEuler || METHOD == kMidpoint)),
+                "the folded step: Euler and midpoint, values only, constant coefficients");
   constexpr bool kNeedU = METHOD == kSrk;
   constexpr bool kInPlace = !SENS && !TIMED;
   using S = typename std::conditional<SENS, Dual<T>, T>::type;
@@ -550,7 +575,7 @@ __global__ void __launch_bounds__(kBlock) trajectory_kernel(const TrajArgs<T> p)
     }
     const StepNoise noise(key, r.cell);             // (the uniform head of this step's Philox calls: scalar unit)
     Pack<T, W> w, u;
-    draw_increment<T, W, kNeedU, /*PAIRS=*/kNeedU>(noise, r, elem, false, w.v, u.v);   // (SRK: the shared series costs it a wave)
+    draw_increment<T, W, kNeedU, /*PAIRS=*/kNeedU, /*SCALED=*/!POW2>(noise, r, elem, false, w.v, u.v);   // (SRK: the shared series costs it a wave)
     // Values-only kernels with constant coefficients advance the state IN PLACE: a step that ends at or after an output
     // time -- all but a few do not -- first sets the state it starts from aside (the interpolation inside a step needs both
     // ends) in a cold block, and the hot loop has no register copies at its latch. The others (dual numbers, coefficient
@@ -585,8 +610,14 @@ __global__ void __launch_bounds__(kBlock) trajectory_kernel(const TrajArgs<T> p)
           bq = B{b.v[q]};
           eq = E{e.v[q]};
         }
-        y_new[q] = affine_step<T, METHOD, S, A, B, C, E>(y[q], A{a.v[q]}, bq, C{c.v[q]}, eq, w.v[q],
-                                                          kNeedU ? u.v[q] : (T)0, r.dt, r.half_dt, r.rdt, r.sqrt_dt);
+        if constexpr (POW2) {
+          const AffineModel<T, S, A, B, C, E> m{A{a.v[q]}, bq, C{c.v[q]}, eq};
+          y_new[q] = scheme_step_pow2<T, METHOD>(y[q], m, w.v[q], r.dt, r.half_dt, r.sw,
+                                                 METHOD == kMidpoint ? half_of_pow2(r.sw) : r.sw);
+        } else {
+          y_new[q] = affine_step<T, METHOD, S, A, B, C, E>(y[q], A{a.v[q]}, bq, C{c.v[q]}, eq, w.v[q],
+                                                            kNeedU ? u.v[q] : (T)0, r.dt, r.half_dt, r.rdt, r.sqrt_dt);
+        }
       }
     }
     if constexpr (SENS) {
@@ -621,23 +652,33 @@ __global__ void __launch_bounds__(kBlock) trajectory_kernel(const TrajArgs<T> p)
   }
 }
 
-template <typename T, int METHOD, bool SENS, bool TIMED = false, bool LINEAR = false>
+template <typename T, int METHOD, bool SENS, bool TIMED = false, bool LINEAR = false, bool POW2 = false>
 static hipError_t launch_traj_form(const TrajArgs<T>& p, bool vec, hipStream_t s) {
-  if (vec) return launch_lanes(trajectory_kernel<T, METHOD, 4, SENS, TIMED, LINEAR>, p.n >> 2, s, p);
-  return launch_lanes(trajectory_kernel<T, METHOD, 1, SENS, TIMED, LINEAR>, p.n, s, p);
+  if (vec) return launch_lanes(trajectory_kernel<T, METHOD, 4, SENS, TIMED, LINEAR, POW2>, p.n >> 2, s, p);
+  return launch_lanes(trajectory_kernel<T, METHOD, 1, SENS, TIMED, LINEAR, POW2>, p.n, s, p);
+}
+
+// The values-only forms with constant coefficients; `pow2`: the schedule vouches for TSDE_TRAJ_POW2_STEPS. The folded step
+// is built for float32 Euler and midpoint; everything else runs the plain form whatever the flag says.
+template <typename T, int METHOD, bool LINEAR>
+static hipError_t launch_traj_values(const TrajArgs<T>& p, bool vec, bool pow2, hipStream_t s) {
+  if constexpr (std::is_same<T, float>::value && (METHOD == kEuler || METHOD == kMidpoint)) {
+    if (pow2) return launch_traj_form<T, METHOD, false, false, LINEAR, true>(p, vec, s);
+  }
+  return launch_traj_form<T, METHOD, false, false, LINEAR>(p, vec, s);
 }
 
 template <typename T, int METHOD>
-static hipError_t launch_traj_m(const TrajArgs<T>& p, bool vec, hipStream_t s) {
+static hipError_t launch_traj_m(const TrajArgs<T>& p, bool vec, bool pow2, hipStream_t s) {
   if (p.cstride != 0) {            // coefficient tables (values only)
     if (p.sens) return hipErrorNotSupported;
     return launch_traj_form<T, METHOD, false, true>(p, vec, s);
   }
   if (p.b == nullptr && p.e == nullptr) {   // both shifts zero: the linear form (values only)
     if (p.sens) return hipErrorNotSupported;
-    return launch_traj_form<T, METHOD, false, false, true>(p, vec, s);
+    return launch_traj_values<T, METHOD, true>(p, vec, pow2, s);
   }
-  return p.sens ? launch_traj_form<T, METHOD, true>(p, vec, s) : launch_traj_form<T, METHOD, false>(p, vec, s);
+  return p.sens ? launch_traj_form<T, METHOD, true>(p, vec, s) : launch_traj_values<T, METHOD, false>(p, vec, pow2, s);
 }
 
 template <typename T>
@@ -658,7 +699,8 @@ hipError_t launch_trajectory_affine_diag(void* ys, void* sens, const void* y0, i
   const bool vec = may_vec(p, p.a, p.b, p.c, p.e, p.sens) &&
                    (key.elem0 % 4 == 0) &&   // diagonal noise: a lane's 4 elements are one Philox quad
                    (cstride % 4 == 0);       // coefficient tables: every row starts on a 16-byte group
-  return dispatch_method(method, [&](auto m) { return launch_traj_m<T, decltype(m)::value>(p, vec, s); });
+  const bool pow2 = (tr->flags & TSDE_TRAJ_POW2_STEPS) != 0;
+  return dispatch_method(method, [&](auto m) { return launch_traj_m<T, decltype(m)::value>(p, vec, pow2, s); });
 }
 
 template <typename T>

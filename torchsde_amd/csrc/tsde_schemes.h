@@ -22,6 +22,28 @@ TSDE_D S drift_diffusion_update(S y, S f, S g, N w, T cf, T cg) {
   return (y + f * cf) + cg * (g * w);
 }
 
+// The same update when cf and the noise scale `sz` = cg * sqrt(h) are POWERS OF TWO (TSDE_TRAJ_POW2_STEPS, torchsde_amd.h),
+// from the unscaled standard normal z (W = z * sqrt(h)). A product with a power of two is exact, so f*cf is exact and
+// fma(f, cf, y) = rn(y + f*cf); and cg*rn(g*rn(z*sqrt(h))) = rn(g*z)*sz exactly, so the second fma adds the same number
+// and rounds the same sum. Two multiplies fewer per element, the same float bit for bit -- as long as no product
+// (f*cf, z*sqrt(h), g*z*sz) is subnormal: the flag's exponent range keeps z*sqrt(h) normal, and below |f|, |g| of about
+// 2^-126 / scale this form rounds once fewer than the one above: a subnormal product carries an error of at most 2^-150 into
+// the sums there and none here, a few units in the last place of a state that small (tests/test_pow2_step_fold.py). Values
+// only, and written with explicit fused operations: the build has contraction off.
+TSDE_D float fused_mul_add(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+TSDE_D double fused_mul_add(double a, double b, double c) { return __builtin_fma(a, b, c); }
+template <typename T>
+TSDE_D T drift_diffusion_update_pow2(T y, T f, T g, T z, T cf, T sz) {
+  return fused_mul_add(g * z, sz, fused_mul_add(f, cf, y));
+}
+
+// x / 2 for a power of two x well inside the normal range (the flag's range): one step down in the exponent field, integer
+// work -- on a wave-uniform value, scalar work.
+TSDE_D float half_of_pow2(float x) { return __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, x) - 0x00800000u); }
+TSDE_D double half_of_pow2(double x) {
+  return __builtin_bit_cast(double, __builtin_bit_cast(uint64_t, x) - 0x0010000000000000ull);
+}
+
 // v/2 of Milstein: scale * (W^2 - dt) for Ito, scale * W^2 for Stratonovich (milstein.py:54-57 with the 0.5 of :69)
 template <typename T, typename N = T>
 TSDE_D N milstein_v(N w, T dt, T scale, int ito) {

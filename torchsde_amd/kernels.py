@@ -8,6 +8,7 @@ expressed with differentiable torch ops on the re-materialised increment (the st
 """
 import collections
 import ctypes
+import os
 
 import numpy as np
 import torch
@@ -574,6 +575,34 @@ def _on_boundaries(out_w):
     return all(float(w0) == 0.0 and float(w1) == 1.0 for (w0, w1) in out_w)
 
 
+# TSDE_TRAJ_POW2_STEPS (include/torchsde_amd.h): the exponents e of dt = 2^e and of sqrt(h) = 2^e that the bit covers. The
+# folded step needs z * sqrt(h) to be a normal number for every nonzero standard normal z the generator can return; the
+# float32 Box-Muller has radius >= 2^-16 and a nonzero sine or cosine of a float32 turn fraction >= 2^-30, so |z| >= 2^-46,
+# far above the 2^-100 this range is cut for: 2^-100 * 2^-26 = 2^-126, the smallest normal float32 (float64 has more room).
+_POW2_DT_EXPONENTS = (-52, 52)
+_POW2_SQRT_H_EXPONENTS = (-26, 26)
+
+
+def _pow2_in_range(values, exponents):
+    """Every entry a positive power of two 2^e with e in `exponents` (inclusive)?"""
+    mantissa, exponent = np.frexp(values)            # value = mantissa * 2^exponent, mantissa in [0.5, 1): 2^e is (0.5, e + 1)
+    return bool(np.all(mantissa == 0.5) and np.all(exponent - 1 >= exponents[0]) and np.all(exponent - 1 <= exponents[1]))
+
+
+def pow2_steps_enabled():
+    """The switch of tests and A/B runs: TSDE_POW2_STEPS=0 in the environment clears the bit of every schedule made."""
+    return os.environ.get("TSDE_POW2_STEPS", "1") != "0"
+
+
+def pow2_steps(rows):
+    """TSDE_TRAJ_POW2_STEPS of step rows in the state dtype: every dt (slot 0) and sqrt(h) (slot 4) an exact power of two
+    inside the exponent ranges above, and slot 1 exactly dt/2."""
+    if rows.shape[0] == 0 or not pow2_steps_enabled():
+        return False
+    return (_pow2_in_range(rows[:, 0], _POW2_DT_EXPONENTS) and _pow2_in_range(rows[:, 4], _POW2_SQRT_H_EXPONENTS)
+            and bool(np.all(rows[:, 1] == rows[:, 0] * rows.dtype.type(0.5))))
+
+
 class TrajectorySchedule:
     """Device-resident ``tsde_traj_t`` of one solve: step rows, Brownian cells and the output map."""
 
@@ -594,6 +623,8 @@ class TrajectorySchedule:
         s.step_rows, s.cells = self.rows.data_ptr(), self.cells.data_ptr()
         s.out_step, s.out_w = self.out_step.data_ptr(), self.out_w.data_ptr()
         s.n_steps, s.n_out = self.n_steps, self.n_out
+        self.pow2_steps = pow2_steps(rows)           # (of the rows as the kernel reads them: in the state dtype)
+        s.flags = _native.TRAJ_POW2_STEPS if self.pow2_steps else 0
         self._struct = s
 
     def struct(self):
@@ -607,7 +638,8 @@ class TrajectorySchedule:
         training loop) without its four blocking host->device copies; otherwise a new one, remembered (the 64 most
         recent)."""
         key = (np.ascontiguousarray(step_rows).tobytes(), np.ascontiguousarray(cells).tobytes(),
-               tuple(int(k) for k in out_step), tuple((float(a), float(b)) for a, b in out_w), str(device), dtype)
+               tuple(int(k) for k in out_step), tuple((float(a), float(b)) for a, b in out_w), str(device), dtype,
+               pow2_steps_enabled())     # (the bit itself is a function of the rows; the switch that clears it is not)
         hit = cls._recent.get(key)
         if hit is not None:
             cls._recent.move_to_end(key)

@@ -186,7 +186,7 @@ struct SrkDiagOp {
     if constexpr (STAGE == 1) {
       const Pack<T, W> y = load<T, W, NT>(in[0], i), f0 = load<T, W, NT>(in[1], i), g0 = load<T, W, NT>(in[2], i);
       Pack<T, W> w, u, h01, h11, h12;
-      cell_noise<T, W, true>(nz, i, w, u);
+      cell_noise<T, W, true, true>(nz, i, w, u);
 #pragma unroll
       for (int k = 0; k < W; ++k) {
         h01.v[k] = srid2_h0_term<T, 1, 0>(y.v[k], f0.v[k], g0.v[k], u.v[k], dt, rdt);
@@ -200,7 +200,7 @@ struct SrkDiagOp {
       const Pack<T, W> y = load<T, W, NT>(in[0], i), f0 = load<T, W, NT>(in[1], i), g0 = load<T, W, NT>(in[2], i),
                        f1 = load<T, W, NT>(in[3], i), g1 = load<T, W, NT>(in[4], i);
       Pack<T, W> w, u, h02, acc, p13;
-      cell_noise<T, W, true>(nz, i, w, u);
+      cell_noise<T, W, true, true>(nz, i, w, u);
 #pragma unroll
       for (int k = 0; k < W; ++k) {
         T h = srid2_h0_term<T, 2, 0>(y.v[k], f0.v[k], g0.v[k], u.v[k], dt, rdt);
@@ -217,7 +217,7 @@ struct SrkDiagOp {
       const Pack<T, W> p = load<T, W, NT>(in[0], i), a = load<T, W, NT>(in[1], i), f2 = load<T, W, NT>(in[2], i),
                        g2 = load<T, W, NT>(in[3], i);
       Pack<T, W> w, u, h13, acc;
-      cell_noise<T, W, true>(nz, i, w, u);
+      cell_noise<T, W, true, true>(nz, i, w, u);
 #pragma unroll
       for (int k = 0; k < W; ++k) {
         h13.v[k] = srid2_h1_term<T, 3, 2>(p.v[k], f2.v[k], g2.v[k], dt, sqrt_dt);
@@ -231,7 +231,7 @@ struct SrkDiagOp {
       // beta3(3) = 0 (srid2.py:52): the last stage's weight does not depend on U -- (0*U)*rdt is a zero for every
       // finite U -- so U is not generated here (one Philox call and two Box-Muller pairs per 16 bytes less in a kernel
       // that only moves three streams); 0 stands in for it.
-      cell_noise<T, W, false>(nz, i, w, u);
+      cell_noise<T, W, false, true>(nz, i, w, u);
 #pragma unroll
       for (int k = 0; k < W; ++k)
         y1.v[k] = srid2_final_term<T, 3>(a.v[k], zero, g3.v[k], w.v[k], zero, dt, rdt, sqrt_dt);

@@ -22,16 +22,24 @@ struct WH4 {
   T H[4];
 };
 
+// The quad draws of the bridge: with the space-time Levy area (two draws per node) through the select form of the shared
+// series, which keeps query_kernel<float, true> at its scalar spills (profiles/bm_select_resource_usage_notes.txt).
+template <typename T, bool HAVE_H>
+TSDE_D void bridge_normal4(const NoiseKey& key, uint64_t quad, uint32_t cell, uint64_t node, uint32_t stream, T (&n)[4]) {
+  if constexpr (HAVE_H) normal4_selects<T>(key, quad, cell, node, stream, n);
+  else normal4<T>(key, quad, cell, node, stream, n);
+}
+
 // Root draw of a cell of width h:  W ~ sqrt(h) N,  H ~ sqrt(h/12) N   (brownian_interval.py:553-558).
 template <typename T, bool HAVE_H>
 TSDE_D void cell_root(const NoiseKey& key, uint64_t quad, uint32_t cell, double h, WH4<T>& o) {
   T n[4];
-  normal4<T>(key, quad, cell, 0, kStreamW, n);
+  bridge_normal4<T, HAVE_H>(key, quad, cell, 0, kStreamW, n);
   const T sw = (T)sqrt(h);
 #pragma unroll
   for (int j = 0; j < 4; ++j) o.W[j] = n[j] * sw;
   if (HAVE_H) {
-    normal4<T>(key, quad, cell, 0, kStreamH, n);
+    bridge_normal4<T, HAVE_H>(key, quad, cell, 0, kStreamH, n);
     const T sh = (T)sqrt(h / 12.0);
 #pragma unroll
     for (int j = 0; j < 4; ++j) o.H[j] = n[j] * sh;
@@ -117,8 +125,8 @@ template <typename T, bool HAVE_H>
 TSDE_D void bridge_split(const NoiseKey& key, uint64_t quad, uint32_t cell, uint64_t node, const SplitCoef<T, HAVE_H>& k,
                          const WH4<T>& P, WH4<T>& L, WH4<T>& R) {
   T X1[4], X2[4] = {(T)0, (T)0, (T)0, (T)0};
-  normal4<T>(key, quad, cell, node, kStreamW, X1);
-  if constexpr (HAVE_H) normal4<T>(key, quad, cell, node, kStreamH, X2);
+  bridge_normal4<T, HAVE_H>(key, quad, cell, node, kStreamW, X1);
+  if constexpr (HAVE_H) bridge_normal4<T, HAVE_H>(key, quad, cell, node, kStreamH, X2);
   split_apply<T, HAVE_H>(k, X1, X2, P, L, R);
 }
 

@@ -161,8 +161,9 @@ TSDE_D NoiseKey live_key(const CellNoise<T>& nz) {
   return launch_key(nz.key, nz.key_dev);
 }
 
-// W and (optionally) U = h (W/2 + H) for W consecutive elements starting at local index i.
-template <typename T, int W, bool NEED_U>
+// W and (optionally) U = h (W/2 + H) for W consecutive elements starting at local index i. SELECTS: the quad is drawn through
+// `normal4_selects` in place of `normal4` (the SRK step kernels: profiles/bm_select_resource_usage_notes.txt).
+template <typename T, int W, bool NEED_U, bool SELECTS = false>
 TSDE_D void cell_noise(const CellNoise<T>& nz, int64_t i, Pack<T, W>& w, Pack<T, W>& u) {
   if (nz.dW != nullptr) {
     if (nz.bcast_d > 0) {
@@ -183,11 +184,13 @@ TSDE_D void cell_noise(const CellNoise<T>& nz, int64_t i, Pack<T, W>& w, Pack<T,
   const uint64_t e = key.elem0 + (uint64_t)i;
   if constexpr (W == 4) {
     T n[4];
-    normal4<T>(key, e >> 2, nz.cell, 0, kStreamW, n);
+    if constexpr (SELECTS) normal4_selects<T>(key, e >> 2, nz.cell, 0, kStreamW, n);
+    else normal4<T>(key, e >> 2, nz.cell, 0, kStreamW, n);
 #pragma unroll
     for (int j = 0; j < 4; ++j) w.v[j] = n[j] * sw;
     if (NEED_U) {
-      normal4<T>(key, e >> 2, nz.cell, 0, kStreamH, n);
+      if constexpr (SELECTS) normal4_selects<T>(key, e >> 2, nz.cell, 0, kStreamH, n);
+      else normal4<T>(key, e >> 2, nz.cell, 0, kStreamH, n);
 #pragma unroll
       for (int j = 0; j < 4; ++j) u.v[j] = th * ((T)0.5 * w.v[j] + n[j] * sh);
     }

@@ -181,13 +181,35 @@ TSDE_D void box_muller(uint32_t a, uint32_t b, float& n0, float& n1) {
   n1 = r * __builtin_amdgcn_sinf(t);
 }
 
-// Both pairs of one Philox call, the series evaluated once. The series value is kept for 1 pair in 16, so a lane needs
-// it for both of its pairs only 1 time in 256: the lane evaluates it on whichever pair is hot (the first if both are),
-// and the second pair of a both-hot lane is redone in a block that the wave enters only when some lane has one
+// The small-radius series in its two factors: box_muller_series(a) = w * p.
+TSDE_D void box_muller_series_factors(uint32_t a, float& w, float& p) {
+  w = fmaf((float)(~a), 0x1p-32f, 0x1p-33f);
+  p = fmaf(w, 1.0f / 3.0f, 0.4f);
+  p = fmaf(w, p, 0.5f);
+  p = fmaf(w, p, 2.0f / 3.0f);
+  p = fmaf(w, p, 1.0f);
+  p = fmaf(w, p, 2.0f);
+}
+
+// Radii times cos / sin of the two angles: the tail both two-pair forms share.
+TSDE_D void box_muller2_finish(const u32x4& r, float s0, float s1, float (&n)[4]) {
+  const float r0 = __builtin_amdgcn_sqrtf(s0);
+  const float r1 = __builtin_amdgcn_sqrtf(s1);
+  const float t0 = (float)r.y * 0x1p-32f;
+  const float t1 = (float)r.w * 0x1p-32f;
+  n[0] = r0 * __builtin_amdgcn_cosf(t0);
+  n[1] = r0 * __builtin_amdgcn_sinf(t0);
+  n[2] = r1 * __builtin_amdgcn_cosf(t1);
+  n[3] = r1 * __builtin_amdgcn_sinf(t1);
+}
+
+// Both pairs of one Philox call, the series evaluated once, chosen by selects. The series value is kept for 1 pair in 16, so
+// a lane needs it for both of its pairs only 1 time in 256: the lane evaluates it on whichever pair is hot (the first if both
+// are), and the second pair of a both-hot lane is redone in a block that the wave enters only when some lane has one
 // (1 - (255/256)^64 = 22 % of the draws of a full wave). The same floats as box_muller on each pair, bit for bit, by
 // construction: a hot pair gets series(its own word) through the same operations in the same order, a cold pair its
-// log value, and the selects only choose between those.
-TSDE_D void box_muller2(const u32x4& r, float (&n)[4]) {
+// log value, and the selects only choose between those. Three vector compares and three v_cndmask_b32 per draw.
+TSDE_D void box_muller2_selects(const u32x4& r, float (&n)[4]) {
   float s0 = box_muller_log(r.x);
   float s1 = box_muller_log(r.z);
   const bool h0 = r.x >= kSeriesFrom;
@@ -199,14 +221,51 @@ TSDE_D void box_muller2(const u32x4& r, float (&n)[4]) {
     asm volatile("" ::: "memory");   // keeps the block a branch: without it the compiler folds it back into selects
     s1 = (h0 && h1) ? box_muller_series(r.z) : s1;
   }
-  const float r0 = __builtin_amdgcn_sqrtf(s0);
-  const float r1 = __builtin_amdgcn_sqrtf(s1);
-  const float t0 = (float)r.y * 0x1p-32f;
-  const float t1 = (float)r.w * 0x1p-32f;
-  n[0] = r0 * __builtin_amdgcn_cosf(t0);
-  n[1] = r0 * __builtin_amdgcn_sinf(t0);
-  n[2] = r1 * __builtin_amdgcn_cosf(t1);
-  n[3] = r1 * __builtin_amdgcn_sinf(t1);
+  box_muller2_finish(r, s0, s1, n);
+}
+
+// The same, with the results written under the execution mask instead of through selects. The two compares land in scalar
+// registers as lane masks (ballots: a lane that is not active at entry -- the ragged last wave of a launch -- has a zero bit in
+// both). The series runs on the first word where that is hot and on the second elsewhere (one v_cndmask_b32 on the first mask),
+// and its final product w * p is written into s0 by the lanes of h0 and into s1 by the lanes of h1, each with its mask as the
+// execution mask, which is then put back to its value at entry -- never to all ones. That leaves a both-hot lane with the
+// first word's series in both radii; the block the wave enters on h0 & h1 != 0 (a scalar AND of the two masks; as before 22 %
+// of a full wave's draws) evaluates the series of the second word and writes it into s1 under h0 & h1. Two vector compares,
+// one v_cndmask_b32 and two v_mul_f32 where the select form has three, three and one; the cold block 9 vector instructions.
+// Bit for bit box_muller on each pair, as above: the masked writes move the same w * p that the selects moved
+// (tests/test_box_muller_select.py restates the selection, tests/test_gpu_box_muller_ragged.py runs it in ragged waves).
+// Picking the series' word with v_max_u32 (a hot word is larger than any cold one) was built and measured slower: the cold
+// block then has to find which pair holds the smaller word (profiles/bm_select_notes.txt).
+TSDE_D void box_muller2(const u32x4& r, float (&n)[4]) {
+  float s0 = box_muller_log(r.x);
+  float s1 = box_muller_log(r.z);
+  const uint64_t m0 = __builtin_amdgcn_ballot_w64(r.x >= kSeriesFrom);
+  const uint64_t m1 = __builtin_amdgcn_ballot_w64(r.z >= kSeriesFrom);
+  float w, p;
+  box_muller_series_factors(r.x >= kSeriesFrom ? r.x : r.z, w, p);
+  uint64_t entry;
+  asm volatile(
+      "s_mov_b64 %[entry], exec\n\t"
+      "s_mov_b64 exec, %[m0]\n\t"
+      "v_mul_f32_e32 %[s0], %[w], %[p]\n\t"
+      "s_mov_b64 exec, %[m1]\n\t"
+      "v_mul_f32_e32 %[s1], %[w], %[p]\n\t"
+      "s_mov_b64 exec, %[entry]"
+      : [s0] "+v"(s0), [s1] "+v"(s1), [entry] "=&s"(entry)
+      : [w] "v"(w), [p] "v"(p), [m0] "s"(m0), [m1] "s"(m1));
+  const uint64_t both = m0 & m1;
+  if (__builtin_expect(both != 0, 0)) {
+    asm volatile("" ::: "memory");   // keeps the block a branch: without it the compiler folds it back into selects
+    box_muller_series_factors(r.z, w, p);
+    asm volatile(
+        "s_mov_b64 %[entry], exec\n\t"
+        "s_mov_b64 exec, %[both]\n\t"
+        "v_mul_f32_e32 %[s1], %[w], %[p]\n\t"
+        "s_mov_b64 exec, %[entry]"
+        : [s1] "+v"(s1), [entry] "=&s"(entry)
+        : [w] "v"(w), [p] "v"(p), [both] "s"(both));
+  }
+  box_muller2_finish(r, s0, s1, n);
 }
 
 TSDE_D void box_muller(uint32_t a, uint32_t b, double& n0, double& n1) {
@@ -223,11 +282,21 @@ TSDE_D void box_muller2(const u32x4& r, double (&n)[4]) {
   box_muller(r.z, r.w, n[2], n[3]);
 }
 
+TSDE_D void box_muller2_selects(const u32x4& r, double (&n)[4]) { box_muller2(r, n); }
+
 // Four standard normals of one (quad, cell, node, stream).
 template <typename T>
 TSDE_D void normal4(const NoiseKey& key, uint64_t quad, uint32_t cell, uint64_t node, uint32_t stream, T (&n)[4]) {
   const u32x4 r = noise_bits(key, quad, cell, node, stream);
   box_muller2(r, n);
+}
+
+// The same four normals through the select form of the shared series: the entry point of callers that the masked writes of
+// box_muller2 cost scalar spills (the SRK step kernels of steps.hip: profiles/bm_select_resource_usage_notes.txt).
+template <typename T>
+TSDE_D void normal4_selects(const NoiseKey& key, uint64_t quad, uint32_t cell, uint64_t node, uint32_t stream, T (&n)[4]) {
+  const u32x4 r = noise_bits(key, quad, cell, node, stream);
+  box_muller2_selects(r, n);
 }
 
 // The same four normals with the series evaluated on both pairs: the entry point of callers whose register allocation the

@@ -1168,9 +1168,14 @@ struct ProgSensModel {
           case kOpCos: s0 = chain(s0, cos(v), -sin(v)); break;
           case kOpTanh: { const T t = tanh(v); s0 = chain(s0, t, (T)1 - t * t); break; }
           case kOpSigmoid: { const T g = (T)1 / ((T)1 + exp(-v)); s0 = chain(s0, g, g * ((T)1 - g)); break; }
-          case kOpSoftplus:
-            s0 = chain(s0, v > (T)20 ? v : log1p(exp(v)), v > (T)20 ? (T)1 : (T)1 / ((T)1 + exp(-v)));
+          case kOpSoftplus: {
+            // slope z / (z + 1) with z = exp(v), as torch's softplus_backward forms it: for v > 0 the rounding of z cancels,
+            // where 1 / (1 + exp(-v)) rounds 1 + exp(-v) at the spacing of 1 and so costs a whole ulp of a result below 1
+            // (1.3 ulp against 0.5 in [4, 8), profiles/README.md); z is used for v <= 20 only, where it is finite
+            const T z = exp(v);
+            s0 = chain(s0, v > (T)20 ? v : log1p(z), v > (T)20 ? (T)1 : z / (z + (T)1));
             break;
+          }
           case kOpSqrt: { const T r = sqrt(v); s0 = chain(s0, r, (T)0.5 / r); break; }
           case kOpAbs: s0 = chain(s0, fabs(v), v > (T)0 ? (T)1 : (v < (T)0 ? (T)-1 : (T)0)); break;
           case kOpRelu: s0 = chain(s0, v > (T)0 ? v : (T)0, v > (T)0 ? (T)1 : (T)0); break;

@@ -64,7 +64,8 @@ template <typename T> TSDE_D Dual<T> d_sigmoid(const Dual<T>& s) {
 }
 template <typename T> TSDE_D Dual<T> d_softplus(const Dual<T>& s) {
   const T v = s.v;
-  return chain(s, v > (T)20 ? v : log1p(exp(v)), v > (T)20 ? (T)1 : (T)1 / ((T)1 + exp(-v)));
+  const T z = exp(v);
+  return chain(s, v > (T)20 ? v : log1p(z), v > (T)20 ? (T)1 : z / (z + (T)1));
 }
 template <typename T> TSDE_D Dual<T> d_sqrt(const Dual<T>& s) { const T r = sqrt(s.v); return chain(s, r, (T)0.5 / r); }
 template <typename T> TSDE_D Dual<T> d_abs(const Dual<T>& s) {

@@ -14,8 +14,18 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // Activations on the hardware transcendentals (v_exp_f32 / v_log_f32 / v_rcp_f32, ~1 ulp each): the libm forms
 // (tanhf, log1pf(expf)) expand to ~100 instructions with divergent special-case branches, which made the
-// activation -- not the matrix products -- the longest part of a step. Absolute error <= 3e-7, well inside the
-// tolerance at which this kernel is compared with the stepwise path (summation order already differs).
+// activation -- not the matrix products -- the longest part of a step. Error against float64, ABSOLUTE where the result is
+// below 1 and RELATIVE above (relative error near 0 is unbounded for any form that goes through exp), worst over all binades
+// 2^-30 .. 2^7 and the saturation / threshold / overflow points -- with correctly rounded primitives, then as measured on
+// gfx950 (profiles/neural_activation_accuracy.txt; tests/test_gpu_neural_activations.py holds every site to twice the first
+// figure plus 2^-24):
+//   tanh value      1.7e-7  1.8e-7        tanh slope 1 - v^2          3.4e-7  3.2e-7
+//   softplus value  1.5e-7  1.9e-7        softplus slope              7.9e-8  8.4e-8   (1 - rcp(1 + ex); ex * rcp(1 + ex): 7.6e-8)
+//   sigmoid value   7.9e-8  8.3e-8        sigmoid slope s (1 - s)     7.4e-8  7.4e-8
+//   LipSwish value  1.2e-7  1.2e-7        LipSwish slope              8.6e-7  8.6e-7   (x (1 - s) near x = 16.6; torch's: the same)
+// (softplus and LipSwish values are that close to the VALUE: absolutely they are off by up to 1.6e-6 / 1.2e-6 near x = 11 .. 16,
+// where an ulp of the value is 1e-6.) No form returns a NaN or an infinity for a finite argument. All of it is well inside the
+// tolerance at which these kernels are compared with the stepwise path (summation order already differs).
 template <int ACT>
 TSDE_D float activate(float x) {
   constexpr float kLog2e = 1.4426950408889634f, kLn2 = 0.6931471805599453f;

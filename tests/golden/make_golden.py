@@ -22,6 +22,9 @@ The GPU box has no /root/reference; tests read the committed .npz files. Fixture
   closed_form_adjoint_<case>.npz   reference `sdeint_adjoint(adjoint_method="euler")` of the perceptron-drift module, float64,
                       counter-RNG path: ys and all gradients
   logqp_<case>.npz    reference `sdeint(..., logqp=True)` / `sdeint_adjoint(..., logqp=True[, names=])`: ys, log-ratio, gradients
+  adaptive_controller_reference.npz   the reference's `update_step_size` (adaptive_stepping.py:21-39) on scripted triples
+                      (error_estimate, prev_step_size, prev_error_ratio or none = NaN): what tests/adaptive_model.py must
+                      reproduce bit for bit
 """
 import os
 import sys
@@ -912,10 +915,49 @@ def gen_additive():
         print(f"recognised_additive_{name}.npz  |ys|={np.abs(out['ys']).mean():.4f}")
 
 
+# ---------------------------------------------------------------------------------------------------------------------------
+# The step-size controller itself: the reference's `update_step_size` on scripted triples (recorded results only; "none" is
+# NaN). Both branches (error above / not above 1), errors from 1e-7 to 1e6, exactly 1 and its two neighbours in double,
+# previous ratios that push the factor into facmin (0.2 after a rejection, 1.0 after an acceptance) and facmax (1.4), and
+# a band around each clamp where the factor is NOT clamped.
+def controller_triples():
+    one = 1.0
+    errors = [1e-7, 1e-6, 3e-5, 1e-3, 0.02, 0.1, 0.3, 0.5, 0.7, 0.85, 0.9, 0.95, 0.999, float(np.nextafter(one, 0.0)), one,
+              float(np.nextafter(one, 2.0)), 1.001, 1.05, 1.3, 2.0, 3.7, 10.0, 11.5, 50.0, 1e3, 1e6]
+    steps = [0.1, 2.0 ** -6, 1e-5, 0.37]
+    ratios = [None, 0.9, 0.05, 0.3, 1.7, 30.0, 9e6, 1e-6]
+    triples = [(e, s, r) for e in errors for s in steps[:2] for r in ratios]
+    triples += [(e, s, None) for e in errors for s in steps[2:]]
+    rng = np.random.default_rng(20261019)
+    for _ in range(96):
+        e = float(10.0 ** rng.uniform(-7, 6))
+        r = None if rng.uniform() < 0.25 else float(10.0 ** rng.uniform(-6, 7))
+        triples.append((e, float(10.0 ** rng.uniform(-6, 0)), r))
+    return triples
+
+
+def gen_adaptive_controller():
+    from torchsde._core import adaptive_stepping
+    triples = controller_triples()
+    out_step, out_ratio = [], []
+    for e, s, r in triples:
+        step, ratio = adaptive_stepping.update_step_size(error_estimate=e, prev_step_size=s, prev_error_ratio=r)
+        out_step.append(step)
+        out_ratio.append(np.nan if ratio is None else ratio)
+    none = np.nan
+    np.savez(os.path.join(HERE, "adaptive_controller_reference.npz"),
+             error_estimate=np.array([t[0] for t in triples], dtype=np.float64),
+             prev_step_size=np.array([t[1] for t in triples], dtype=np.float64),
+             prev_error_ratio=np.array([none if t[2] is None else t[2] for t in triples], dtype=np.float64),
+             new_step_size=np.array(out_step, dtype=np.float64), new_prev_error_ratio=np.array(out_ratio, dtype=np.float64))
+    clamped = sum(1 for (e, s, r), st in zip(triples, out_step) if st in (s * 0.2, s * 1.0, s * 1.4))
+    print(f"adaptive_controller_reference.npz  {len(triples)} triples, {clamped} on a clamp")
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or ["timegrid", "solver", "adaptive", "adjoint", "bridge", "brownian_seq", "closed_form",
                              "closed_form_affine", "logqp", "closed_form_adjoint", "closed_form_expr", "double_backward",
-                             "adjoint_adaptive", "poly3", "additive"]
+                             "adjoint_adaptive", "poly3", "additive", "adaptive_controller"]
     torch.manual_seed(0)
     for w in which:
         globals()["gen_" + w]()

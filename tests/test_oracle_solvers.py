@@ -28,7 +28,9 @@ def test_oracle_matches_reference(name, tag):
 
 def _adaptive_cases():
     import os
-    return sorted(f[len("adaptive_"):-4] for f in os.listdir(helpers.GOLDEN) if f.startswith("adaptive_"))
+    # (adaptive_controller_reference.npz holds recorded controller results, not a solve: tests/test_adaptive_model.py)
+    return sorted(f[len("adaptive_"):-4] for f in os.listdir(helpers.GOLDEN)
+                  if f.startswith("adaptive_") and f != "adaptive_controller_reference.npz")
 
 
 @pytest.mark.parametrize("tag", ["f32", "f64"])

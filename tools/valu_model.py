@@ -10,7 +10,10 @@ occupies the SIMD's VALU port for its issue cost. This tool
   3. counts the loop's instructions by mnemonic, and
   4. prices the VALU ones with the per-instruction issue cycles measured on the device by tools/microbench_valu.hip
      (profiles/valu_rates.json; an instruction that was not measured costs the guide's 2 cycles per plain wave64 op and
-     is listed under `unmeasured`).
+     is listed under `unmeasured`), and
+  5. lists the hot path's scalar loads and `s_waitcnt`s: for each load, the vector instructions between it and the first
+     wait that covers it (`scalar_waits`; the model prices a wait at nothing, so this is where to look for one that is
+     exposed).
 
     python tools/valu_model.py [--kernel SYMBOL_SUBSTRING] [--out profiles/valu_model_latest.json]
 
@@ -69,10 +72,11 @@ _LABEL = re.compile(r"^(\.LBB\d+_\d+):")
 _INSTR = re.compile(r"^\s+([a-z_0-9]+)\b")
 
 
-def step_loop(lines):
-    """Instruction mnemonics of the depth-1 loop's hot path: from the loop header, falling through every forward
-    conditional branch (the branches to the output code, taken at the few steps that are output times) down to the
-    back edge; plus the latch blocks the assembler placed BEFORE the header, if the back edge goes through them."""
+def walk_step_loop(lines):
+    """The depth-1 loop's hot path as (mnemonic, instruction text) pairs in execution order: from the loop header, falling
+    through every forward conditional branch (the branches to the output code, taken at the few steps that are output
+    times) down to the back edge; plus the latch blocks the assembler placed BEFORE the header, if the back edge goes
+    through them."""
     blocks, order, cur = {}, [], None
     notes = {}
     for ln in lines:
@@ -87,7 +91,7 @@ def step_loop(lines):
             continue
         m = _INSTR.match(ln)
         if m and not ln.lstrip().startswith((";", ".")):
-            blocks[cur].append((m.group(1), ln.split()[-1]))
+            blocks[cur].append((m.group(1), ln.split()[-1], ln.split(";")[0].strip()))
     headers = [b for b in order if "This Loop Header: Depth=1" in notes[b]]
     if len(headers) != 1:
         raise RuntimeError(f"expected one depth-1 loop, found {headers}")
@@ -99,8 +103,8 @@ def step_loop(lines):
         if b != header and not (tag in notes[b] and "Depth=1" in notes[b]):
             break
         walked.append(b)
-        for ins, target in blocks[b]:
-            hot.append(ins)
+        for ins, target, text in blocks[b]:
+            hot.append((ins, text))
             if ins.startswith(("s_cbranch", "s_branch")) and (target == header or target in latch):
                 back = target
                 break
@@ -113,8 +117,50 @@ def step_loop(lines):
         raise RuntimeError("no back edge found below the loop header")
     if back in latch:
         for b in latch[latch.index(back):]:
-            hot += [ins for ins, _ in blocks[b]]
+            hot += [(ins, text) for ins, _, text in blocks[b]]
     return hot, {"header": header, "walked": walked, "back_edge_to": back}
+
+
+def step_loop(lines):
+    """Instruction mnemonics of the hot path (`walk_step_loop`)."""
+    hot, where = walk_step_loop(lines)
+    return [ins for ins, _ in hot], where
+
+
+_LGKM = re.compile(r"lgkmcnt\((\d+)\)")
+
+
+def scalar_load_waits(hot):
+    """The scalar loads and the `s_waitcnt`s of a hot path (`walk_step_loop`'s pairs), read as one turn of a loop.
+
+    Scalar loads return out of order, so the only wait that covers one is `lgkmcnt(0)`: for each load, the first such wait
+    after it -- in this turn, or, if there is none below the load, the first of the NEXT turn (`next_turn`: the value is
+    carried across the back edge) -- and the number of vector instructions the wave can issue in between. A load that is
+    waited for at once (`valu_between` 0) leaves the wave nothing to issue while the scalar cache answers."""
+    waits = [i for i, (ins, text) in enumerate(hot)
+             if ins == "s_waitcnt" and any(int(n) == 0 for n in _LGKM.findall(text))]
+    valu_before = [0]
+    for ins, _ in hot:
+        valu_before.append(valu_before[-1] + ins.startswith("v_"))
+    loads = []
+    for i, (ins, text) in enumerate(hot):
+        if not ins.startswith(("s_load_", "s_buffer_load_")):
+            continue
+        rec = {"load": text, "at": i}
+        later = [w for w in waits if w > i]
+        if later:
+            rec.update(wait_at=later[0], next_turn=False, valu_between=valu_before[later[0]] - valu_before[i])
+        elif waits:
+            rec.update(wait_at=waits[0], next_turn=True,
+                       valu_between=valu_before[-1] - valu_before[i] + valu_before[waits[0]])
+        else:
+            rec.update(wait_at=None, next_turn=None, valu_between=None)
+        loads.append(rec)
+    return {"scalar_loads": loads,
+            "s_waitcnt": [{"at": i, "text": text} for i, (ins, text) in enumerate(hot) if ins == "s_waitcnt"],
+            "s_waitcnt_lgkmcnt0": len(waits),
+            "is": "per scalar load of the hot path: the vector instructions between it and the first s_waitcnt lgkmcnt(0) "
+                  "that covers it (next_turn: that wait is past the back edge); positions count the hot path's instructions"}
 
 
 def _base(mnemonic):
@@ -147,7 +193,8 @@ def model(symbol=HEADLINE_SYMBOL, rates_path=None, source="trajectory.hip", elem
         col = rec.get("column") or ("shader" if rec.get("ticks_are_shader_cycles") else "wall_2p4ghz")
         rates = {k: v[col] for k, v in rec["cycles"].items()}
         rates_meta = {"file": os.path.relpath(rates_path, ROOT), "column": col, "device": rec.get("device")}
-    hot, where = step_loop(kernel_body(asm if asm is not None else device_asm(source), symbol))
+    walked, where = walk_step_loop(kernel_body(asm if asm is not None else device_asm(source), symbol))
+    hot = [ins for ins, _ in walked]
     hist = collections.Counter(_base(i) for i in hot)
     valu = {k: n for k, n in hist.items() if k.startswith("v_")}
     other = {k: n for k, n in hist.items() if not k.startswith("v_")}
@@ -170,6 +217,7 @@ def model(symbol=HEADLINE_SYMBOL, rates_path=None, source="trajectory.hip", elem
         "issue_cycles_per_wave_step": cycles,
         "issue_cycles_per_wave_step_all_plain": plain,
         "unmeasured_priced_at_2_cycles": sorted(unmeasured),
+        "scalar_waits": scalar_load_waits(walked),
         "rates": rates_meta,
         "is": "SIMD cycles the VALU port is occupied per wave and solver step = sum over the loop's vector instructions of "
               "count x measured issue cycles (tools/microbench_valu.hip); scalar, branch and memory instructions issue from "
@@ -205,7 +253,9 @@ def main():
         print(f"{symbol}: {m['valu_instructions_per_wave_step']} VALU instructions, "
               f"{m['issue_cycles_per_wave_step']:.1f} issue cycles per wave-step"
               + (f" (unmeasured, priced at 2 cycles: {m['unmeasured_priced_at_2_cycles']})"
-                 if m["unmeasured_priced_at_2_cycles"] else ""))
+                 if m["unmeasured_priced_at_2_cycles"] else "")
+              + f"; {m['scalar_waits']['s_waitcnt_lgkmcnt0']} s_waitcnt lgkmcnt(0), vector instructions between each scalar "
+                f"load and its wait: {[rec['valu_between'] for rec in m['scalar_waits']['scalar_loads']]}")
 
 
 if __name__ == "__main__":

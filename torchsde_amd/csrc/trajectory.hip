@@ -506,6 +506,33 @@ TSDE_D void emit_outputs(const Args& p, int64_t i, int k, int& j, int& next_out,
   next_out = next_output_step<UNIFORM>(p.out_step, j, p.n_out);
 }
 
+// What the affine kernel's step k takes from the solve's tables: its row, and the uniform head of its Philox calls.
+template <typename T>
+struct StepData {
+  StepRow<T> r;
+  StepNoise noise;
+};
+
+template <typename T>
+TSDE_D StepData<T> step_data(const TrajArgs<T>& p, const NoiseKey& key, int k) {
+  const StepRow<T> r = step_row<true>(p.rows + (int64_t)k * 8, p.cells, k);
+  return {r, StepNoise(key, r.cell)};
+}
+
+// The forms of the affine kernel whose loop is rotated by one step: the scalar loads of step k + 1 (its row and its cell)
+// are issued during step k and carried across the back edge in scalar registers, so that the one `s_waitcnt` left stands at
+// the latch, a whole step after the loads, and the top of a step -- the Philox head, four scalar operations that every
+// vector instruction of the step depends on -- no longer waits for the scalar cache with nothing else to issue. Chosen per
+// form by the compiled loop (no vector register, no vector instruction, no scratch more than the plain loop) and by the
+// device: Euler, both Milsteins, Heun and Euler-Heun, float32, one 16-byte group per lane, constant coefficients. Midpoint
+// measured slower rotated and SRK, whose loop waits for its loads where it uses them either way, the same; the TIMED forms
+// gain vector instructions; W = 1, float64 and SENS were not measured (profiles/step_ahead_notes.txt). Those keep the
+// plain loop.
+template <typename T, int METHOD, int W, bool SENS, bool TIMED>
+constexpr bool step_ahead_form() {
+  return std::is_same<T, float>::value && W == 4 && !SENS && !TIMED && METHOD != kMidpoint && METHOD != kSrk;
+}
+
 // W = 4: a lane owns one 16-byte group (needs d % 4 == 0 so the group stays inside one row).
 // W = 1: a lane owns one element (any d; also used for small problems, where it exposes 4x the lanes).
 // SENS : carry the kSens path-wise sensitivities of every element and write them next to the outputs.
@@ -559,8 +586,15 @@ __global__ void __launch_bounds__(kBlock) trajectory_kernel(const TrajArgs<T> p)
   const uint64_t elem = key.elem0 + (uint64_t)i;
   int j = 0;
   int next_out = next_output_step<true>(p.out_step, 0, p.n_out);
+  constexpr bool kAhead = step_ahead_form<T, METHOD, W, SENS, TIMED>();
+  StepData<T> ahead = step_data(p, key, 0);         // (kAhead only: dead code, and removed, in the other forms)
   for (int k = 0; k < p.n_steps; ++k) {
-    const StepRow<T> r = step_row<true>(p.rows + (int64_t)k * 8, p.cells, k);
+    const StepData<T> now = ahead;                  // (kAhead: what step k - 1 loaded)
+    const StepRow<T> r = kAhead ? now.r : step_row<true>(p.rows + (int64_t)k * 8, p.cells, k);
+    if constexpr (kAhead) {
+      const int kn = k + 1 < p.n_steps ? k + 1 : k;  // (clamped, never branched on: the last step re-reads its own row)
+      ahead = step_data(p, key, kn);
+    }
     constexpr int NS = stage_slots<METHOD>();
     Pack<T, W> ta[NS], tb[NS], tc[NS], te[NS];      // TIMED: the coefficient rows of this step's stage times
     if constexpr (TIMED) {
@@ -573,7 +607,7 @@ __global__ void __launch_bounds__(kBlock) trajectory_kernel(const TrajArgs<T> p)
         te[sl] = load<T, W>(p.e, at);
       }
     }
-    const StepNoise noise(key, r.cell);             // (the uniform head of this step's Philox calls: scalar unit)
+    const StepNoise noise = kAhead ? now.noise : StepNoise(key, r.cell);   // (the uniform head of this step's Philox calls: scalar unit)
     Pack<T, W> w, u;
     draw_increment<T, W, kNeedU, /*PAIRS=*/kNeedU, /*SCALED=*/!POW2>(noise, r, elem, false, w.v, u.v);   // (SRK: the shared series costs it a wave)
     // Values-only kernels with constant coefficients advance the state IN PLACE: a step that ends at or after an output

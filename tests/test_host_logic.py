@@ -1061,3 +1061,35 @@ def test_describe_reads_the_book_key_layout():
         "[Euler] stays stepwise: the drift is not a tracked function of the state",
         "[ReversibleHeun:kernels] stays stepwise: calling f and g advances a random number generator",
     ]
+
+
+# ---- perceptron-drift reverse passes: chunk lengths -----------------------------------------------------------------
+@pytest.mark.parametrize("rows,d,hidden,n_steps,steps_per_chunk", [
+    (1000, 64, 32, 40, 7), (500, 32, 64, 37, 7),       # the budgets tests/test_gpu_mlp_backward.py patches in
+    (16, 128, 128, 12, 5), (37, 20, 36, 12, 5),        # ... tests/test_gpu_mlp_logqp_adjoint.py
+    (40, 124, 120, 7, 3), (24, 36, 68, 3, 1),
+    (32768, 128, 128, 500, None), (3, 4, 4, 2, None),  # the budgets as shipped: 3 GiB
+])
+def test_perceptron_chunk_lengths_follow_the_stash_budgets(monkeypatch, rows, d, hidden, n_steps, steps_per_chunk):
+    """The steps per launch of the three reverse passes over the perceptron-drift kernels (training sweep, stochastic adjoint and
+    its logqp form, which shares the adjoint's budget): stash budget // bytes per step, between 1 and the step count, with
+    d + 2 hidden floats per row and step for the sweep and 2 d + 2 hidden for the adjoint. Chunk boundaries fix the order in
+    which the partial weight gradients are summed, so these numbers are part of what the gradients' bits depend on."""
+    from torchsde_amd import kernels as K
+    from torchsde_amd import mlp_adjoint
+    sweep_row, adjoint_row = d + 2 * hidden, 2 * d + 2 * hidden
+    if steps_per_chunk is not None:
+        monkeypatch.setattr(K._MlpTrajectoryFn, "STASH_BYTES", steps_per_chunk * rows * sweep_row * 4)
+        monkeypatch.setattr(mlp_adjoint._MlpAdjointFn, "STASH_BYTES", steps_per_chunk * rows * adjoint_row * 4)
+    else:
+        assert K._MlpTrajectoryFn.STASH_BYTES == mlp_adjoint._MlpAdjointFn.STASH_BYTES == 3 << 30
+    sweep = int(max(1, min(n_steps, K._MlpTrajectoryFn.STASH_BYTES // max(rows * sweep_row * 4, 1))))
+    adjoint = int(max(1, min(n_steps, mlp_adjoint._MlpAdjointFn.STASH_BYTES // max(rows * adjoint_row * 4, 1))))
+    assert K._MlpTrajectoryFn._chunk(n_steps, rows, d, hidden) == sweep
+    assert mlp_adjoint._MlpAdjointFn._chunk(n_steps, rows, d, hidden) == adjoint
+    assert K.PerceptronGradients.chunk_length(n_steps, rows, sweep_row, K._MlpTrajectoryFn.STASH_BYTES) == sweep
+    assert K.PerceptronGradients.chunk_length(n_steps, rows, adjoint_row, mlp_adjoint._MlpAdjointFn.STASH_BYTES) == adjoint
+    if steps_per_chunk is not None:
+        assert sweep == adjoint == min(steps_per_chunk, n_steps)
+    # one byte short of a step's stash still makes progress
+    assert K.PerceptronGradients.chunk_length(n_steps, rows, sweep_row, rows * sweep_row * 4 - 1) == 1

@@ -342,5 +342,12 @@ def trajectory_tail(schedule, bm, *last):
     return (schedule.struct(), bm._key, bm._elem0, None if entropy_dev is None else entropy_dev.data_ptr()) + last
 
 
+def sweep_tail(schedule, k_lo, k_hi, bm, *last):
+    """`trajectory_tail` for the launches that walk back over the steps k_hi-1 ... k_lo of a schedule (the reverse sweep and
+    the stochastic adjoint of the perceptron-drift kernels)."""
+    tail = trajectory_tail(schedule, bm, *last)
+    return tail[:1] + (int(k_lo), int(k_hi)) + tail[1:]
+
+
 def contiguous(t):
     return t if t.is_contiguous() else t.contiguous()

@@ -2,6 +2,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <initializer_list>
 #include <vector>
 
 #include "tsde_common.h"
@@ -548,27 +549,66 @@ int tsde_trajectory_affine_diag_sens(void* ys, void* sens, const void* y0, int64
                                 diff_rate, diff_shift, 0, method, traj, entropy, elem0, entropy_dev, dtype, stream);
 }
 
+// What the five perceptron-drift entry points check alike (null: nothing is wrong), in the order their callers have always been
+// answered in. `reverse`: the three gradient entries -- hidden a multiple of 4 as well, 32-bit lane offsets over the wider of
+// d and hidden, steps k_hi-1 ... k_lo of the schedule (states from boundary ys_first on) -- against the two sampling entries;
+// `kl`: the Brownian field has a column more than the state. `own_first` / `own_last`: the entry's own complaint (null: none)
+// that is due before the dtype check / behind the activation check.
+static const char* mlp_entry_problem(bool reverse, bool kl, std::initializer_list<const void*> required,
+                                     std::initializer_list<const void*> aligned, const char* own_first, const char* own_last,
+                                     int64_t rows, int64_t d, int64_t hidden, int diff_kind, int activation, int dtype,
+                                     const tsde_traj_t* traj, int32_t k_lo = 0, int32_t k_hi = 0, int32_t ys_first = 0) {
+  const char* null_problem = nullptr;
+  for (const void* q : required)
+    if (!q) null_problem = "null argument";
+  const char* kind_problem =
+      diff_kind != TSDE_DIFF_AFFINE && diff_kind != TSDE_DIFF_SIGMOID ? "unknown diffusion kind" : nullptr;
+  if (!reverse && kind_problem) return kind_problem;
+  if (null_problem) return null_problem;
+  if (own_first) return own_first;
+  if (kind_problem) return kind_problem;
+  if (dtype != TSDE_F32) return "dtype must be TSDE_F32";
+  if (rows < 0) return "need rows >= 0";
+  const bool d_fits = d >= 4 && d <= 128 && d % 4 == 0 && hidden <= 256 && !(hidden > 128 && d > 64);
+  if (!reverse && !(d_fits && hidden >= 1))
+    return "need d a multiple of 4 in [4, 128] and hidden in [1, 128] (up to 256 for d <= 64)";
+  if (reverse && !(d_fits && hidden >= 4 && hidden % 4 == 0))
+    return "need d and hidden multiples of 4, d in [4, 128], hidden in [4, 128] (up to 256 for d <= 64)";
+  const char* align_problem = nullptr;
+  for (const void* q : aligned)
+    if (reinterpret_cast<uintptr_t>(q) & 15u)
+      align_problem = reverse ? "state-shaped buffers must be 16-byte aligned" : "ys and y0 must be 16-byte aligned";
+  if (!reverse && align_problem) return align_problem;
+  const int64_t width = (reverse && hidden > d ? hidden : d) + (kl ? 1 : 0);
+  if (rows * width >= (int64_t(1) << 30)) {
+    if (reverse)
+      return kl ? "need rows * (max(d, hidden) + 1) < 2^30 (32-bit lane offsets)"
+                : "need rows * max(d, hidden) < 2^30 (32-bit lane offsets)";
+    return kl ? "need rows * (d + 1) < 2^30 (32-bit lane offsets)" : "need rows * d < 2^30 (32-bit lane offsets)";
+  }
+  if (align_problem) return align_problem;
+  if (activation != TSDE_ACT_TANH && activation != TSDE_ACT_SOFTPLUS) return "unknown activation";
+  if (own_last) return own_last;
+  if (!reverse) return schedule_problem(traj);
+  if (k_lo < 0 || k_hi < k_lo || k_hi > traj->n_steps) return "need 0 <= k_lo <= k_hi <= n_steps";
+  if (ys_first < 0 || ys_first > k_lo) return "need 0 <= ys_first <= k_lo";
+  if (traj->n_steps > 0 && (!traj->step_rows || !traj->cells)) return "schedule without step rows";
+  return nullptr;
+}
+
 int tsde_trajectory_mlp_diag(void* ys, const void* y0, int64_t rows, int64_t d, int64_t hidden, const void* w1,
                              const void* b1, const void* w2, const void* b2, const void* diff_rate,
                              const void* diff_shift, int diff_kind, double diff_amp, int activation, int method,
                              const tsde_traj_t* traj, uint64_t entropy, uint64_t elem0, const uint64_t* entropy_dev,
                              int dtype, void* stream) {
   const char* where = "tsde_trajectory_mlp_diag";
-  if (diff_kind != TSDE_DIFF_AFFINE && diff_kind != TSDE_DIFF_SIGMOID) return bad_arg(where, "unknown diffusion kind");
-  if (!ys || !y0 || !w1 || !b1 || !w2 || !b2 || !diff_rate || !diff_shift || !traj) return bad_arg(where, "null argument");
-  if (dtype != TSDE_F32) return bad_arg(where, "dtype must be TSDE_F32");
-  if (rows < 0) return bad_arg(where, "need rows >= 0");
-  if (d < 4 || d > 128 || d % 4 != 0 || hidden < 1 || hidden > 256 || (hidden > 128 && d > 64))
-    return bad_arg(where, "need d a multiple of 4 in [4, 128] and hidden in [1, 128] (up to 256 for d <= 64)");
-  if ((reinterpret_cast<uintptr_t>(y0) | reinterpret_cast<uintptr_t>(ys)) & 15u)
-    return bad_arg(where, "ys and y0 must be 16-byte aligned");
-  if (rows * d >= (int64_t(1) << 30)) return bad_arg(where, "need rows * d < 2^30 (32-bit lane offsets)");
-  if (activation != TSDE_ACT_TANH && activation != TSDE_ACT_SOFTPLUS) return bad_arg(where, "unknown activation");
-  if (method != TSDE_TRAJ_EULER && method != TSDE_TRAJ_MILSTEIN_ITO && method != TSDE_TRAJ_MILSTEIN_STRAT &&
-      method != TSDE_TRAJ_MIDPOINT && method != TSDE_TRAJ_SRK)
-    return bad_arg(where, "method must be Euler, Milstein, midpoint or SRK");
-  if (elem0 % 4 != 0) return bad_arg(where, "elem0 must be a multiple of 4");
-  if (const char* bad = schedule_problem(traj)) return bad_arg(where, bad);
+  const bool known_method = method == TSDE_TRAJ_EULER || method == TSDE_TRAJ_MILSTEIN_ITO || method == TSDE_TRAJ_MILSTEIN_STRAT ||
+                            method == TSDE_TRAJ_MIDPOINT || method == TSDE_TRAJ_SRK;
+  const char* own = !known_method ? "method must be Euler, Milstein, midpoint or SRK"
+                    : elem0 % 4 != 0 ? "elem0 must be a multiple of 4" : nullptr;
+  if (const char* bad = mlp_entry_problem(false, false, {ys, y0, w1, b1, w2, b2, diff_rate, diff_shift, traj}, {y0, ys}, nullptr,
+                                          own, rows, d, hidden, diff_kind, activation, dtype, traj))
+    return bad_arg(where, bad);
   const hipStream_t s = (hipStream_t)stream;
   ProfScope p(TSDE_KID_TRAJECTORY, s);
   return fail(tsde::launch_trajectory_mlp_diag(ys, y0, rows, d, hidden, w1, b1, w2, b2, diff_rate, diff_shift,
@@ -582,19 +622,12 @@ int tsde_trajectory_mlp_diag_logqp(void* ys, void* logqp, const void* y0, int64_
                                    double diff_amp, int activation, int method, const tsde_traj_t* traj, uint64_t entropy,
                                    uint64_t elem0, const uint64_t* entropy_dev, int dtype, void* stream) {
   const char* where = "tsde_trajectory_mlp_diag_logqp";
-  if (diff_kind != TSDE_DIFF_AFFINE && diff_kind != TSDE_DIFF_SIGMOID) return bad_arg(where, "unknown diffusion kind");
-  if (!ys || !logqp || !y0 || !w1 || !b1 || !w2 || !b2 || !diff_rate || !diff_shift || !prior_rate || !prior_shift || !traj)
-    return bad_arg(where, "null argument");
-  if (dtype != TSDE_F32) return bad_arg(where, "dtype must be TSDE_F32");
-  if (rows < 0) return bad_arg(where, "need rows >= 0");
-  if (d < 4 || d > 128 || d % 4 != 0 || hidden < 1 || hidden > 256 || (hidden > 128 && d > 64))
-    return bad_arg(where, "need d a multiple of 4 in [4, 128] and hidden in [1, 128] (up to 256 for d <= 64)");
-  if ((reinterpret_cast<uintptr_t>(y0) | reinterpret_cast<uintptr_t>(ys)) & 15u)
-    return bad_arg(where, "ys and y0 must be 16-byte aligned");
-  if (rows * (d + 1) >= (int64_t(1) << 30)) return bad_arg(where, "need rows * (d + 1) < 2^30 (32-bit lane offsets)");
-  if (activation != TSDE_ACT_TANH && activation != TSDE_ACT_SOFTPLUS) return bad_arg(where, "unknown activation");
-  if (method != TSDE_TRAJ_EULER && method != TSDE_TRAJ_MILSTEIN_ITO) return bad_arg(where, "method must be Euler or Ito Milstein");
-  if (const char* bad = schedule_problem(traj)) return bad_arg(where, bad);
+  const char* own =
+      method != TSDE_TRAJ_EULER && method != TSDE_TRAJ_MILSTEIN_ITO ? "method must be Euler or Ito Milstein" : nullptr;
+  if (const char* bad = mlp_entry_problem(false, true, {ys, logqp, y0, w1, b1, w2, b2, diff_rate, diff_shift, prior_rate,
+                                                        prior_shift, traj},
+                                          {y0, ys}, nullptr, own, rows, d, hidden, diff_kind, activation, dtype, traj))
+    return bad_arg(where, bad);
   const hipStream_t s = (hipStream_t)stream;
   ProfScope p(TSDE_KID_TRAJECTORY, s);
   return fail(tsde::launch_trajectory_mlp_diag_logqp(ys, logqp, y0, rows, d, hidden, w1, b1, w2, b2, diff_rate, diff_shift,
@@ -798,23 +831,12 @@ int tsde_adjoint_mlp_diag(void* y, void* a, void* stash_a, void* stash_hid, void
                           int32_t k_hi, uint64_t entropy, uint64_t elem0, const uint64_t* entropy_dev, int dtype,
                           void* stream) {
   const char* where = "tsde_adjoint_mlp_diag";
-  if (!y || !a || !stash_a || !stash_hid || !stash_delta || !stash_y || !row_rate || !row_shift || !w1 || !b1 || !w2 ||
-      !b2 || !diff_rate || !diff_shift || !traj)
-    return bad_arg(where, "null argument");
-  if (diff_kind != TSDE_DIFF_AFFINE && diff_kind != TSDE_DIFF_SIGMOID) return bad_arg(where, "unknown diffusion kind");
-  if (dtype != TSDE_F32) return bad_arg(where, "dtype must be TSDE_F32");
-  if (rows < 0) return bad_arg(where, "need rows >= 0");
-  if (d < 4 || d > 128 || d % 4 != 0 || hidden < 4 || hidden > 256 || hidden % 4 != 0 || (hidden > 128 && d > 64))
-    return bad_arg(where, "need d and hidden multiples of 4, d in [4, 128], hidden in [4, 128] (up to 256 for d <= 64)");
-  if (rows * (d > hidden ? d : hidden) >= (int64_t(1) << 30))
-    return bad_arg(where, "need rows * max(d, hidden) < 2^30 (32-bit lane offsets)");
-  const void* aligned[] = {y, a, stash_a, stash_hid, stash_delta, stash_y, row_rate, row_shift};
-  for (const void* q : aligned)
-    if (reinterpret_cast<uintptr_t>(q) & 15u) return bad_arg(where, "state-shaped buffers must be 16-byte aligned");
-  if (activation != TSDE_ACT_TANH && activation != TSDE_ACT_SOFTPLUS) return bad_arg(where, "unknown activation");
-  if (elem0 % 4 != 0) return bad_arg(where, "elem0 must be a multiple of 4");
-  if (k_lo < 0 || k_hi < k_lo || k_hi > traj->n_steps) return bad_arg(where, "need 0 <= k_lo <= k_hi <= n_steps");
-  if (traj->n_steps > 0 && (!traj->step_rows || !traj->cells)) return bad_arg(where, "schedule without step rows");
+  if (const char* bad = mlp_entry_problem(true, false, {y, a, stash_a, stash_hid, stash_delta, stash_y, row_rate, row_shift, w1,
+                                                        b1, w2, b2, diff_rate, diff_shift, traj},
+                                          {y, a, stash_a, stash_hid, stash_delta, stash_y, row_rate, row_shift}, nullptr,
+                                          elem0 % 4 != 0 ? "elem0 must be a multiple of 4" : nullptr, rows, d, hidden,
+                                          diff_kind, activation, dtype, traj, k_lo, k_hi))
+    return bad_arg(where, bad);
   const hipStream_t s = (hipStream_t)stream;
   ProfScope p(TSDE_KID_MLP_ADJOINT, s);
   return fail(tsde::launch_adjoint_mlp_diag(y, a, stash_a, stash_hid, stash_delta, stash_y, row_rate, row_shift, rows, d,
@@ -832,23 +854,13 @@ int tsde_adjoint_mlp_diag_logqp(void* y, void* a, const void* a_l, void* stash_a
                                 const tsde_traj_t* traj, int32_t k_lo, int32_t k_hi, uint64_t entropy, uint64_t elem0,
                                 const uint64_t* entropy_dev, int dtype, void* stream) {
   const char* where = "tsde_adjoint_mlp_diag_logqp";
-  if (!y || !a || !a_l || !stash_a || !stash_hid || !stash_delta || !stash_y || !row_rate || !row_shift || !row_prior_rate ||
-      !row_prior_shift || !w1 || !b1 || !w2 || !b2 || !diff_rate || !diff_shift || !prior_rate || !prior_shift || !traj)
-    return bad_arg(where, "null argument");
-  if (diff_kind != TSDE_DIFF_AFFINE && diff_kind != TSDE_DIFF_SIGMOID) return bad_arg(where, "unknown diffusion kind");
-  if (dtype != TSDE_F32) return bad_arg(where, "dtype must be TSDE_F32");
-  if (rows < 0) return bad_arg(where, "need rows >= 0");
-  if (d < 4 || d > 128 || d % 4 != 0 || hidden < 4 || hidden > 256 || hidden % 4 != 0 || (hidden > 128 && d > 64))
-    return bad_arg(where, "need d and hidden multiples of 4, d in [4, 128], hidden in [4, 128] (up to 256 for d <= 64)");
-  if (rows * ((d > hidden ? d : hidden) + 1) >= (int64_t(1) << 30))
-    return bad_arg(where, "need rows * (max(d, hidden) + 1) < 2^30 (32-bit lane offsets)");
-  const void* aligned[] = {y, a, stash_a, stash_hid, stash_delta, stash_y, row_rate, row_shift, row_prior_rate, row_prior_shift};
-  for (const void* q : aligned)
-    if (reinterpret_cast<uintptr_t>(q) & 15u) return bad_arg(where, "state-shaped buffers must be 16-byte aligned");
-  if (activation != TSDE_ACT_TANH && activation != TSDE_ACT_SOFTPLUS) return bad_arg(where, "unknown activation");
-  if (!(ito & 1)) return bad_arg(where, "the KL column is carried for Ito SDEs only");
-  if (k_lo < 0 || k_hi < k_lo || k_hi > traj->n_steps) return bad_arg(where, "need 0 <= k_lo <= k_hi <= n_steps");
-  if (traj->n_steps > 0 && (!traj->step_rows || !traj->cells)) return bad_arg(where, "schedule without step rows");
+  if (const char* bad = mlp_entry_problem(
+          true, true, {y, a, a_l, stash_a, stash_hid, stash_delta, stash_y, row_rate, row_shift, row_prior_rate, row_prior_shift,
+                       w1, b1, w2, b2, diff_rate, diff_shift, prior_rate, prior_shift, traj},
+          {y, a, stash_a, stash_hid, stash_delta, stash_y, row_rate, row_shift, row_prior_rate, row_prior_shift}, nullptr,
+          !(ito & 1) ? "the KL column is carried for Ito SDEs only" : nullptr, rows, d, hidden, diff_kind, activation, dtype,
+          traj, k_lo, k_hi))
+    return bad_arg(where, bad);
   const hipStream_t s = (hipStream_t)stream;
   ProfScope p(TSDE_KID_MLP_ADJOINT, s);
   return fail(tsde::launch_adjoint_mlp_diag_logqp(y, a, a_l, stash_a, stash_hid, stash_delta, stash_y, row_rate, row_shift,
@@ -867,27 +879,17 @@ int tsde_trajectory_mlp_diag_backward(void* lam, void* stash_lam, void* stash_hi
                                       uint64_t entropy, uint64_t elem0, const uint64_t* entropy_dev, int dtype,
                                       void* stream) {
   const char* where = "tsde_trajectory_mlp_diag_backward";
-  if (!lam || !stash_lam || !stash_hid || !stash_delta || !row_rate || !row_shift || !ys_all || !w1 || !b1 || !w2 ||
-      !diff_rate || !diff_shift || !traj)
-    return bad_arg(where, "null argument");
-  if (method != TSDE_TRAJ_EULER && method != TSDE_TRAJ_MILSTEIN_ITO && method != TSDE_TRAJ_MILSTEIN_STRAT)
-    return bad_arg(where, "method must be Euler or Milstein");
-  if (diff_kind != TSDE_DIFF_AFFINE && !(diff_kind == TSDE_DIFF_SIGMOID && method == TSDE_TRAJ_EULER))
-    return bad_arg(where, "diffusion kind must be affine, or sigmoid with Euler");
-  if (dtype != TSDE_F32) return bad_arg(where, "dtype must be TSDE_F32");
-  if (rows < 0) return bad_arg(where, "need rows >= 0");
-  if (d < 4 || d > 128 || d % 4 != 0 || hidden < 4 || hidden > 256 || hidden % 4 != 0 || (hidden > 128 && d > 64))
-    return bad_arg(where, "need d and hidden multiples of 4, d in [4, 128], hidden in [4, 128] (up to 256 for d <= 64)");
-  if (rows * (d > hidden ? d : hidden) >= (int64_t(1) << 30))
-    return bad_arg(where, "need rows * max(d, hidden) < 2^30 (32-bit lane offsets)");
-  const void* aligned[] = {lam, stash_lam, stash_hid, stash_delta, row_rate, row_shift, ys_all, grad_ys};
-  for (const void* q : aligned)
-    if (reinterpret_cast<uintptr_t>(q) & 15u) return bad_arg(where, "state-shaped buffers must be 16-byte aligned");
-  if (activation != TSDE_ACT_TANH && activation != TSDE_ACT_SOFTPLUS) return bad_arg(where, "unknown activation");
-  if (elem0 % 4 != 0) return bad_arg(where, "elem0 must be a multiple of 4");
-  if (k_lo < 0 || k_hi < k_lo || k_hi > traj->n_steps) return bad_arg(where, "need 0 <= k_lo <= k_hi <= n_steps");
-  if (ys_first < 0 || ys_first > k_lo) return bad_arg(where, "need 0 <= ys_first <= k_lo");
-  if (traj->n_steps > 0 && (!traj->step_rows || !traj->cells)) return bad_arg(where, "schedule without step rows");
+  const char* own =
+      method != TSDE_TRAJ_EULER && method != TSDE_TRAJ_MILSTEIN_ITO && method != TSDE_TRAJ_MILSTEIN_STRAT
+          ? "method must be Euler or Milstein"
+      : diff_kind != TSDE_DIFF_AFFINE && !(diff_kind == TSDE_DIFF_SIGMOID && method == TSDE_TRAJ_EULER)
+          ? "diffusion kind must be affine, or sigmoid with Euler" : nullptr;
+  if (const char* bad = mlp_entry_problem(true, false, {lam, stash_lam, stash_hid, stash_delta, row_rate, row_shift, ys_all, w1,
+                                                        b1, w2, diff_rate, diff_shift, traj},
+                                          {lam, stash_lam, stash_hid, stash_delta, row_rate, row_shift, ys_all, grad_ys}, own,
+                                          elem0 % 4 != 0 ? "elem0 must be a multiple of 4" : nullptr, rows, d, hidden,
+                                          diff_kind, activation, dtype, traj, k_lo, k_hi, ys_first))
+    return bad_arg(where, bad);
   if (grad_last >= 0 && (!grad_ys || !grad_step)) return bad_arg(where, "grad_last >= 0 without cotangents");
   const hipStream_t s = (hipStream_t)stream;
   ProfScope p(TSDE_KID_MLP_BACKWARD, s);

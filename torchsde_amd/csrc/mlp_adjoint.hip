@@ -96,31 +96,34 @@ TSDE_D float row_total(float v) {
   return v;
 }
 
+// The kernel's LDS behind b2 / c / e (MlpLds): kAdjSums x D sums per wave -- rate, shift; KL: the prior's (hr, hs) after
+// them -- and, KL, hr and hs themselves.
+template <bool KL>
+constexpr int kAdjSums = KL ? 4 : 2;
+template <int D, int NW, bool KL>
+constexpr int kAdjExtraFloats = NW * kAdjSums<KL> * D + (KL ? 2 * D : 0);
+
 template <int D, int H, int ACT, int NW, bool FULL, bool MILSTEIN, bool KL = false>
 __global__ void __launch_bounds__(NW * 64)
     mlp_adjoint_kernel(const std::conditional_t<KL, MlpAdjKlArgs, MlpAdjArgs> p) {
-  constexpr int R = 16, kSums = KL ? 4 : 2;
+  constexpr int R = 16, kSums = kAdjSums<KL>;
   using TL = Tile<R>;
   constexpr int TD = D / R, TH = H / R, kThreads = NW * 64;
-  constexpr int S1 = H + MlpLds<R>::kPad, S2 = D + MlpLds<R>::kPad;
+  using L = MlpLds<R>;
+  constexpr int S1 = H + L::kPad, S2 = D + L::kPad;
   extern __shared__ float lds[];
-  float* W1s = lds;                 // D rows of S1: W1s[channel][hidden]
-  float* W2s = W1s + D * S1;        // H rows of S2: W2s[hidden][channel]
-  float* b1s = W2s + H * S2;        // H
-  float* b2s = b1s + H;             // D
-  float* cs = b2s + D;              // D
-  float* es = cs + D;               // D
-  float* sums = es + D;             // NW x 2 x D: per wave, the diffusion-parameter sums (rate, shift) of its 16 rows
-  //                                   (KL: NW x 4 x D, the prior's (hr, hs) after them, then hr and hs themselves)
+  float* W1s = lds;                         // D rows of S1: W1s[channel][hidden]
+  float* W2s = lds + L::w2(D, H);           // H rows of S2: W2s[hidden][channel]
+  float* b1s = lds + L::b1(D, H);           // H
+  float* b2s = lds + L::vec(D, H, 0);       // D
+  float* cs = lds + L::vec(D, H, 1);        // D
+  float* es = lds + L::vec(D, H, 2);        // D
+  float* sums = lds + L::vec(D, H, 3);      // NW x 2 x D: per wave, the diffusion-parameter sums (rate, shift) of its 16 rows
+  //                                           (KL: NW x 4 x D, the prior's (hr, hs) after them, then hr and hs themselves)
   [[maybe_unused]] float* hrs = sums + NW * kSums * D;      // D
   [[maybe_unused]] float* hss = hrs + D;                    // D
   const int dT = p.d, hT = p.h;
-  for (int i = threadIdx.x; i < D * H; i += kThreads) {
-    const int k1 = i / H, m1 = i % H, k2 = i / D, m2 = i % D;
-    W1s[k1 * S1 + m1] = (k1 < dT && m1 < hT) ? p.W1[k1 * hT + m1] : 0.0f;
-    W2s[k2 * S2 + m2] = (k2 < hT && m2 < dT) ? p.W2[k2 * dT + m2] : 0.0f;
-  }
-  for (int i = threadIdx.x; i < H; i += kThreads) b1s[i] = i < hT ? p.b1[i] : 0.0f;
+  stage_perceptron<D, H, R, kThreads>(lds, p.W1, p.W2, p.b1, dT, hT);
   for (int i = threadIdx.x; i < D; i += kThreads) {
     b2s[i] = i < dT ? p.b2[i] : 0.0f;
     cs[i] = i < dT ? p.c[i] : 0.0f;
@@ -413,129 +416,41 @@ __global__ void __launch_bounds__(NW * 64)
   }
 }
 
-template <int D, int H, int ACT, int NW, bool FULL, bool MILSTEIN>
-static hipError_t launch_adj_scheme(const MlpAdjArgs& p, hipStream_t s) {
-  constexpr int R = 16;
-  const size_t lds_bytes =
-      (size_t)(D * (H + MlpLds<R>::kPad) + H * (D + MlpLds<R>::kPad) + H + 3 * D + NW * 2 * D) * sizeof(float);
-  static bool configured = false;   // per instantiation
-  if (!configured) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_adjoint_kernel<D, H, ACT, NW, FULL, MILSTEIN>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return e;
-    configured = true;
-  }
-  const int64_t rows_per_block = NW * R;
-  const int64_t blocks = (p.B + rows_per_block - 1) / rows_per_block;
-  hipLaunchKernelGGL((mlp_adjoint_kernel<D, H, ACT, NW, FULL, MILSTEIN>), dim3((unsigned)blocks), dim3(NW * 64), lds_bytes,
-                     s, p);
-  return hipGetLastError();
-}
-
-template <int D, int H, int ACT, int NW, bool FULL>
-static hipError_t launch_adj_variant(const MlpAdjArgs& p, hipStream_t s) {
-  return (p.ito & 2) ? launch_adj_scheme<D, H, ACT, NW, FULL, true>(p, s)
-                     : launch_adj_scheme<D, H, ACT, NW, FULL, false>(p, s);
-}
-
 // y, a, the f accumulators and act'(z) are 3 x D/4 + H/4 live registers per lane (128 at d = hidden = 128). The large
 // shapes exist as 8-wave blocks (two waves per SIMD, 256 registers: at most 10 spilled dwords) and as 4-wave blocks (one
 // wave per SIMD, up to 512 registers: no spills); TSDE_ADJ_WAVES=4 picks the latter (default: 8).
-template <int D, int H, int ACT>
-static hipError_t launch_adj_shape(const MlpAdjArgs& p, hipStream_t s) {
-  const bool full = p.d == D && p.h == H;
-  if constexpr (D >= 128 || H >= 256) {
-    static const int waves = [] {
-      const char* e = getenv("TSDE_ADJ_WAVES");
-      return e ? atoi(e) : 0;
-    }();
-    const bool eight = waves != 4;
-    if (eight) return full ? launch_adj_variant<D, H, ACT, 8, true>(p, s) : launch_adj_variant<D, H, ACT, 8, false>(p, s);
-    return full ? launch_adj_variant<D, H, ACT, 4, true>(p, s) : launch_adj_variant<D, H, ACT, 4, false>(p, s);
-  } else {
-    return full ? launch_adj_variant<D, H, ACT, 8, true>(p, s) : launch_adj_variant<D, H, ACT, 8, false>(p, s);
-  }
-}
-
-template <int D, int H>
-static hipError_t launch_adj_act(const MlpAdjArgs& p, int act, hipStream_t s) {
-  if (act == TSDE_ACT_TANH) return launch_adj_shape<D, H, TSDE_ACT_TANH>(p, s);
-  if (act == TSDE_ACT_SOFTPLUS) return launch_adj_shape<D, H, TSDE_ACT_SOFTPLUS>(p, s);
-  return hipErrorInvalidValue;
-}
-
-template <int D>
-static hipError_t launch_adj_h(const MlpAdjArgs& p, int act, hipStream_t s) {
-  if (p.h <= 32) return launch_adj_act<D, 32>(p, act, s);
-  if (p.h <= 64) return launch_adj_act<D, 64>(p, act, s);
-  if (p.h <= 128) return launch_adj_act<D, 128>(p, act, s);
-  if constexpr (D <= 64) {                 // both weight arrays must fit the LDS of a CU: d * hidden <= 16384
-    if (p.h <= 256) return launch_adj_act<D, 256>(p, act, s);
-  }
-  return hipErrorInvalidValue;
-}
-
+//
 // The KL instantiation. Five state-sized register arrays are live across the u product (y, a, f, act'(z), a + w): at
 // d = hidden = 128 the 8-wave block spills 31-34 dwords (the aligned instantiation: 10), the 4-wave block none -- and the 8-wave
 // block is still the faster one (32768 x 128 x 500 forward + backward: 58.0 ms against 61.4 ms,
 // profiles/logqp_adjoint_ab.txt), so every shape runs as 8-wave blocks and TSDE_ADJ_WAVES does not reach this instantiation.
-template <int D, int H, int ACT, int NW, bool FULL, bool MILSTEIN>
-static hipError_t launch_adj_kl_scheme(const MlpAdjKlArgs& p, hipStream_t s) {
-  constexpr int R = 16;
-  const size_t lds_bytes =
-      (size_t)(D * (H + MlpLds<R>::kPad) + H * (D + MlpLds<R>::kPad) + H + 3 * D + NW * 4 * D + 2 * D) * sizeof(float);
-  static bool configured = false;   // per instantiation
-  if (!configured) {
-    const hipError_t e =
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_adjoint_kernel<D, H, ACT, NW, FULL, MILSTEIN, true>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return e;
-    configured = true;
+template <bool KL>
+struct MlpAdjointPolicy {
+  using Args = std::conditional_t<KL, MlpAdjKlArgs, MlpAdjArgs>;
+  template <int D, int H, int ACT, int NW, bool FULL>
+  static hipError_t waves(const Args& p, hipStream_t s) {
+    const size_t lds_bytes = MlpLds<16>::bytes(D, H, 3, kAdjExtraFloats<D, NW, KL>);
+    return (p.ito & 2) ? launch_rows_per_wave<mlp_adjoint_kernel<D, H, ACT, NW, FULL, true, KL>, NW, 16>(p, lds_bytes, s)
+                       : launch_rows_per_wave<mlp_adjoint_kernel<D, H, ACT, NW, FULL, false, KL>, NW, 16>(p, lds_bytes, s);
   }
-  const int64_t rows_per_block = NW * R;
-  const int64_t blocks = (p.B + rows_per_block - 1) / rows_per_block;
-  hipLaunchKernelGGL((mlp_adjoint_kernel<D, H, ACT, NW, FULL, MILSTEIN, true>), dim3((unsigned)blocks), dim3(NW * 64),
-                     lds_bytes, s, p);
-  return hipGetLastError();
-}
-
-template <int D, int H, int ACT, int NW>
-static hipError_t launch_adj_kl_waves(const MlpAdjKlArgs& p, hipStream_t s) {
-  const bool full = p.d == D && p.h == H, milstein = (p.ito & 2) != 0;
-  if (full)
-    return milstein ? launch_adj_kl_scheme<D, H, ACT, NW, true, true>(p, s)
-                    : launch_adj_kl_scheme<D, H, ACT, NW, true, false>(p, s);
-  return milstein ? launch_adj_kl_scheme<D, H, ACT, NW, false, true>(p, s)
-                  : launch_adj_kl_scheme<D, H, ACT, NW, false, false>(p, s);
-}
-
-template <int D, int H, int ACT>
-static hipError_t launch_adj_kl_shape(const MlpAdjKlArgs& p, hipStream_t s) {
-  return launch_adj_kl_waves<D, H, ACT, 8>(p, s);
-}
-
-template <int D, int H>
-static hipError_t launch_adj_kl_act(const MlpAdjKlArgs& p, int act, hipStream_t s) {
-  if (act == TSDE_ACT_TANH) return launch_adj_kl_shape<D, H, TSDE_ACT_TANH>(p, s);
-  if (act == TSDE_ACT_SOFTPLUS) return launch_adj_kl_shape<D, H, TSDE_ACT_SOFTPLUS>(p, s);
-  return hipErrorInvalidValue;
-}
-
-template <int D>
-static hipError_t launch_adj_kl_h(const MlpAdjKlArgs& p, int act, hipStream_t s) {
-  if (p.h <= 32) return launch_adj_kl_act<D, 32>(p, act, s);
-  if (p.h <= 64) return launch_adj_kl_act<D, 64>(p, act, s);
-  if (p.h <= 128) return launch_adj_kl_act<D, 128>(p, act, s);
-  if constexpr (D <= 64) {
-    if (p.h <= 256) return launch_adj_kl_act<D, 256>(p, act, s);
+  template <int D, int H, int ACT, bool FULL>
+  static hipError_t launch(const Args& p, hipStream_t s) {
+    if constexpr (!KL && (D >= 128 || H >= 256)) {
+      static const int waves_env = [] {
+        const char* e = getenv("TSDE_ADJ_WAVES");
+        return e ? atoi(e) : 0;
+      }();
+      if (waves_env == 4) return waves<D, H, ACT, 4, FULL>(p, s);
+    }
+    return waves<D, H, ACT, 8, FULL>(p, s);
   }
-  return hipErrorInvalidValue;
-}
+};
 
 static void fill_adj_args(MlpAdjArgs& p, void* y, void* a, void* stash_a, void* stash_hid, void* stash_delta, void* stash_y,
                           void* row_rate, void* row_shift, int64_t rows, int64_t d, int64_t h, const void* W1, const void* b1,
                           const void* W2, const void* b2, const void* c, const void* e, int diff_kind, double diff_amp,
                           int ito, const tsde_traj_t* tr, int32_t k_lo, int32_t k_hi, NoiseKey key, const uint64_t* key_dev) {
+  fill_mlp_core(p, rows, d, h, W1, b1, W2, c, e, diff_kind, diff_amp, tr, key, key_dev);
   p.y = (float*)y;
   p.a = (float*)a;
   p.stash_a = (float*)stash_a;
@@ -544,24 +459,10 @@ static void fill_adj_args(MlpAdjArgs& p, void* y, void* a, void* stash_a, void* 
   p.stash_y = (float*)stash_y;
   p.row_rate = (float*)row_rate;
   p.row_shift = (float*)row_shift;
-  p.W1 = (const float*)W1;
-  p.b1 = (const float*)b1;
-  p.W2 = (const float*)W2;
   p.b2 = (const float*)b2;
-  p.c = (const float*)c;
-  p.e = (const float*)e;
-  p.diff_kind = diff_kind;
-  p.diff_amp = (float)diff_amp;
   p.ito = ito;
-  p.rows = (const float*)tr->step_rows;
-  p.cells = tr->cells;
-  p.B = rows;
-  p.d = (int32_t)d;
-  p.h = (int32_t)h;
   p.k_lo = k_lo;
   p.k_hi = k_hi;
-  p.key = key;
-  p.key_dev = key_dev;
 }
 
 hipError_t launch_adjoint_mlp_diag_logqp(void* y, void* a, const void* a_l, void* stash_a, void* stash_hid,
@@ -581,10 +482,7 @@ hipError_t launch_adjoint_mlp_diag_logqp(void* y, void* a, const void* a_l, void
   p.row_hshift = (float*)row_hshift;
   p.bm_stride = d + 1;
   if (rows <= 0 || k_hi <= k_lo) return hipSuccess;
-  if (d <= 32) return launch_adj_kl_h<32>(p, act, s);
-  if (d <= 64) return launch_adj_kl_h<64>(p, act, s);
-  if (d <= 128) return launch_adj_kl_h<128>(p, act, s);
-  return hipErrorInvalidValue;
+  return mlp_ladder<MlpAdjointPolicy<true>>(p, act, s);
 }
 
 hipError_t launch_adjoint_mlp_diag(void* y, void* a, void* stash_a, void* stash_hid, void* stash_delta, void* stash_y,
@@ -596,11 +494,7 @@ hipError_t launch_adjoint_mlp_diag(void* y, void* a, void* stash_a, void* stash_
   fill_adj_args(p, y, a, stash_a, stash_hid, stash_delta, stash_y, row_rate, row_shift, rows, d, h, W1, b1, W2, b2, c, e,
                 diff_kind, diff_amp, ito, tr, k_lo, k_hi, key, key_dev);
   if (rows <= 0 || k_hi <= k_lo) return hipSuccess;
-  hipError_t r = hipErrorInvalidValue;
-  if (d <= 32) r = launch_adj_h<32>(p, act, s);
-  else if (d <= 64) r = launch_adj_h<64>(p, act, s);
-  else if (d <= 128) r = launch_adj_h<128>(p, act, s);
-  return r;
+  return mlp_ladder<MlpAdjointPolicy<false>>(p, act, s);
 }
 
 }  // namespace tsde

@@ -66,20 +66,16 @@ __global__ void __launch_bounds__(NW * 64) mlp_backward_kernel(const MlpBackArgs
   constexpr int R = 16;
   using TL = Tile<R>;
   constexpr int TD = D / R, TH = H / R, kThreads = NW * 64;
-  constexpr int S1 = H + MlpLds<R>::kPad, S2 = D + MlpLds<R>::kPad;
+  using L = MlpLds<R>;
+  constexpr int S1 = H + L::kPad, S2 = D + L::kPad;
   extern __shared__ float lds[];
-  float* W1s = lds;                 // D rows of S1: W1s[channel][hidden]
-  float* W2s = W1s + D * S1;        // H rows of S2: W2s[hidden][channel]
-  float* b1s = W2s + H * S2;        // H
-  float* cs = b1s + H;              // D
-  float* es = cs + D;               // D
+  float* W1s = lds;                         // D rows of S1: W1s[channel][hidden]
+  float* W2s = lds + L::w2(D, H);           // H rows of S2: W2s[hidden][channel]
+  float* b1s = lds + L::b1(D, H);           // H
+  float* cs = lds + L::vec(D, H, 0);        // D
+  float* es = lds + L::vec(D, H, 1);        // D
   const int dT = p.d, hT = p.h;
-  for (int i = threadIdx.x; i < D * H; i += kThreads) {
-    const int k1 = i / H, m1 = i % H, k2 = i / D, m2 = i % D;
-    W1s[k1 * S1 + m1] = (k1 < dT && m1 < hT) ? p.W1[k1 * hT + m1] : 0.0f;
-    W2s[k2 * S2 + m2] = (k2 < hT && m2 < dT) ? p.W2[k2 * dT + m2] : 0.0f;
-  }
-  for (int i = threadIdx.x; i < H; i += kThreads) b1s[i] = i < hT ? p.b1[i] : 0.0f;
+  stage_perceptron<D, H, R, kThreads>(lds, p.W1, p.W2, p.b1, dT, hT);
   for (int i = threadIdx.x; i < D; i += kThreads) {
     cs[i] = i < dT ? p.c[i] : 0.0f;
     es[i] = i < dT ? p.e[i] : 0.0f;
@@ -156,13 +152,7 @@ __global__ void __launch_bounds__(NW * 64) mlp_backward_kernel(const MlpBackArgs
       }
       // the A operands arrive as 2 TD two-address reads (ds_read2_b32: rows r, r+1 of W1s), each feeding two MFMAs: keep
       // four of them in flight ahead of the MFMAs instead of hipcc's read -> wait -> two MFMAs
-      __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
-#pragma unroll
-      for (int i = 0; i < 2 * TD; ++i) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-        if (i < 2 * TD - 4) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);
+      reads_ahead<2 * TD, 2>();
       f32x4 value;
       const f32x4 bias = lds_quad(b1s, R * th + 4 * part);
 #pragma unroll
@@ -260,49 +250,15 @@ __global__ void __launch_bounds__(NW * 64) mlp_backward_kernel(const MlpBackArgs
   }
 }
 
-template <int D, int H, int ACT, int NW, bool FULL>
-static hipError_t launch_back_variant(const MlpBackArgs& p, hipStream_t s) {
-  constexpr int R = 16;
-  const size_t lds_bytes = (size_t)(D * (H + MlpLds<R>::kPad) + H * (D + MlpLds<R>::kPad) + H + 2 * D) * sizeof(float);
-  static bool configured = false;   // per instantiation
-  if (!configured) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_backward_kernel<D, H, ACT, NW, FULL>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return e;
-    configured = true;
-  }
-  const int64_t rows_per_block = NW * R;
-  const int64_t blocks = (p.B + rows_per_block - 1) / rows_per_block;
-  hipLaunchKernelGGL((mlp_backward_kernel<D, H, ACT, NW, FULL>), dim3((unsigned)blocks), dim3(NW * 64), lds_bytes, s, p);
-  return hipGetLastError();
-}
-
 // 8-wave blocks (two waves per SIMD, 256 registers each) everywhere except the padded 128-channel case, whose bounds
 // tests push the sweep past 256 registers: 4-wave blocks there (one wave per SIMD, 512 registers) instead of spilling.
-template <int D, int H, int ACT>
-static hipError_t launch_back_shape(const MlpBackArgs& p, hipStream_t s) {
-  if (p.d == D && p.h == H) return launch_back_variant<D, H, ACT, 8, true>(p, s);
-  if constexpr (D == 128) return launch_back_variant<D, H, ACT, 4, false>(p, s);
-  else return launch_back_variant<D, H, ACT, 8, false>(p, s);
-}
-
-template <int D, int H>
-static hipError_t launch_back_act(const MlpBackArgs& p, int act, hipStream_t s) {
-  if (act == TSDE_ACT_TANH) return launch_back_shape<D, H, TSDE_ACT_TANH>(p, s);
-  if (act == TSDE_ACT_SOFTPLUS) return launch_back_shape<D, H, TSDE_ACT_SOFTPLUS>(p, s);
-  return hipErrorInvalidValue;
-}
-
-template <int D>
-static hipError_t launch_back_h(const MlpBackArgs& p, int act, hipStream_t s) {
-  if (p.h <= 32) return launch_back_act<D, 32>(p, act, s);
-  if (p.h <= 64) return launch_back_act<D, 64>(p, act, s);
-  if (p.h <= 128) return launch_back_act<D, 128>(p, act, s);
-  if constexpr (D <= 64) {                 // both weight arrays must fit the LDS of a CU: d * hidden <= 16384
-    if (p.h <= 256) return launch_back_act<D, 256>(p, act, s);
+struct MlpBackwardPolicy {
+  template <int D, int H, int ACT, bool FULL>
+  static hipError_t launch(const MlpBackArgs& p, hipStream_t s) {
+    constexpr int NW = (!FULL && D == 128) ? 4 : 8;
+    return launch_rows_per_wave<mlp_backward_kernel<D, H, ACT, NW, FULL>, NW, 16>(p, MlpLds<16>::bytes(D, H, 2), s);
   }
-  return hipErrorInvalidValue;
-}
+};
 
 hipError_t launch_trajectory_mlp_diag_backward(void* lam, void* stash_lam, void* stash_hid, void* stash_delta,
                                                void* row_rate, void* row_shift, const void* ys_all,
@@ -313,6 +269,7 @@ hipError_t launch_trajectory_mlp_diag_backward(void* lam, void* stash_lam, void*
                                                int32_t k_lo, int32_t k_hi, NoiseKey key, const uint64_t* key_dev,
                                                hipStream_t s) {
   MlpBackArgs p;
+  fill_mlp_core(p, rows, d, h, W1, b1, W2, c, e, diff_kind, diff_amp, tr, key, key_dev);
   p.lam = (float*)lam;
   p.stash_lam = (float*)stash_lam;
   p.stash_hid = (float*)stash_hid;
@@ -324,28 +281,11 @@ hipError_t launch_trajectory_mlp_diag_backward(void* lam, void* stash_lam, void*
   p.grad_ys = (const float*)grad_ys;
   p.grad_step = grad_step;
   p.grad_last = grad_last;
-  p.W1 = (const float*)W1;
-  p.b1 = (const float*)b1;
-  p.W2 = (const float*)W2;
-  p.c = (const float*)c;
-  p.e = (const float*)e;
   p.method = method;
-  p.diff_kind = diff_kind;
-  p.diff_amp = (float)diff_amp;
-  p.rows = (const float*)tr->step_rows;
-  p.cells = tr->cells;
-  p.B = rows;
-  p.d = (int32_t)d;
-  p.h = (int32_t)h;
   p.k_lo = k_lo;
   p.k_hi = k_hi;
-  p.key = key;
-  p.key_dev = key_dev;
   if (rows <= 0 || k_hi <= k_lo) return hipSuccess;
-  if (d <= 32) return launch_back_h<32>(p, act, s);
-  if (d <= 64) return launch_back_h<64>(p, act, s);
-  if (d <= 128) return launch_back_h<128>(p, act, s);
-  return hipErrorInvalidValue;
+  return mlp_ladder<MlpBackwardPolicy>(p, act, s);
 }
 
 // ---- C = A^T B (and the column sums of A) over a tall K --------------------------------------------------------------

@@ -82,16 +82,17 @@ __global__ void __launch_bounds__(NW * 64)
   // LDS row strides. The parts of a wave read weight rows 4 apart; with a stride that is a multiple of 32 floats all
   // of them hit the same banks. Padding the stride to 4 (mod 8) floats spreads the four quarters of a 16-row wave
   // over both halves of the 32 banks (2 lanes per bank: the minimum for 64 lanes).
-  constexpr int S1 = H + MlpLds<R>::kPad, S2 = D + MlpLds<R>::kPad;
+  using L = MlpLds<R>;
+  constexpr int S1 = H + L::kPad, S2 = D + L::kPad;
   extern __shared__ float lds[];
-  float* W1s = lds;                 // D rows of S1
-  float* W2s = W1s + D * S1;        // H rows of S2
-  float* b1s = W2s + H * S2;        // H
-  float* b2s = b1s + H;             // D
-  float* cs = b2s + D;              // D
-  float* es = cs + D;               // D
-  [[maybe_unused]] float* hrs = es + D;      // D  (KL) prior drift h = hr * y + hs
-  [[maybe_unused]] float* hss = hrs + D;     // D  (KL)
+  float* W1s = lds;                         // D rows of S1
+  float* W2s = lds + L::w2(D, H);           // H rows of S2
+  float* b1s = lds + L::b1(D, H);           // H
+  float* b2s = lds + L::vec(D, H, 0);       // D
+  float* cs = lds + L::vec(D, H, 1);        // D
+  float* es = lds + L::vec(D, H, 2);        // D
+  [[maybe_unused]] float* hrs = lds + L::vec(D, H, 3);      // D  (KL) prior drift h = hr * y + hs
+  [[maybe_unused]] float* hss = lds + L::vec(D, H, 4);      // D  (KL)
   // weights into LDS, zero-padded from (d, h) to the tile sizes (D, H): padded hidden units feed zero rows of W2 and
   // padded state channels have zero drift, zero diffusion and no noise, so they stay exactly 0
   const int dT = p.d, hT = p.h;
@@ -205,15 +206,6 @@ __global__ void __launch_bounds__(NW * 64)
     //  them: without them the unrolled body needs > 512 registers and spills)
     // 16-row waves: the A operands of a tile arrive as `pairs` two-address reads (ds_read2_b32: weight rows r, r+1), each
     // feeding two MFMAs; four of them are kept in flight ahead of the MFMAs (hipcc alone: read -> wait -> two MFMAs)
-    auto reads_ahead = [](int pairs) {
-      __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
-#pragma unroll
-      for (int i = 0; i < 32; ++i) {
-        if (i < pairs) __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-        if (i < pairs - 4) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    };
     acc_t hid[TH];
     auto hidden_layer = [&](const acc_t* x) {
       // (an opaque zero in every weight address: a multi-stage scheme evaluates the drift several times per step, and
@@ -233,7 +225,7 @@ __global__ void __launch_bounds__(NW * 64)
           }
           if (R != 16 && (t + 1) * kRegs % 16 == 0) __builtin_amdgcn_sched_barrier(0);
         }
-        if constexpr (R == 16) reads_ahead(2 * TD);
+        if constexpr (R == 16) reads_ahead<2 * TD, 2>();
 #pragma unroll
         for (int q = 0; q < TL::kQuads; ++q) {
           const f32x4 bias = lds_quad(b1s, R * th + TL::quad_base(q, part));
@@ -257,7 +249,7 @@ __global__ void __launch_bounds__(NW * 64)
         }
         if (R != 16 && (th + 1) * kRegs % 16 == 0) __builtin_amdgcn_sched_barrier(0);
       }
-      if constexpr (R == 16) reads_ahead(2 * TH);
+      if constexpr (R == 16) reads_ahead<2 * TH, 2>();
       return acc;
     };
 
@@ -591,161 +583,80 @@ __global__ void __launch_bounds__(NW * 64)
   }
 }
 
-template <int D, int H, int ACT, int R, int NW, int SCHEME, bool FULL, bool IL = false>
-static hipError_t launch_mlp_full(const MlpArgs& p, hipStream_t s) {
-  const size_t lds_bytes = MlpLds<R>::bytes(D, H);
-  static bool configured = false;   // per instantiation
-  if (!configured) {
-    const hipError_t e =
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_trajectory_kernel<D, H, ACT, R, NW, SCHEME, FULL, IL>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return e;
-    configured = true;
-  }
-  const int64_t rows_per_block = NW * R;
-  const int64_t blocks = (p.B + rows_per_block - 1) / rows_per_block;
-  hipLaunchKernelGGL((mlp_trajectory_kernel<D, H, ACT, R, NW, SCHEME, FULL, IL>), dim3((unsigned)blocks), dim3(NW * 64),
-                     lds_bytes, s, p);
-  return hipGetLastError();
-}
-
-template <int D, int H, int ACT, int R, int NW, int SCHEME>
-static hipError_t launch_mlp_variant(const MlpArgs& p, hipStream_t s) {
-  // (the multi-stage schemes keep the bounds tests even for unpadded shapes: without them hipcc's schedule of the wider
-  //  basic blocks needs MORE registers -- 390 spilled dwords instead of 62 for the midpoint scheme at d = hidden = 128)
-  if constexpr (SCHEME == 0) {
-    if (p.d == D && p.h == H) {
-      if constexpr (R == 16) {
-        static const bool interleave = [] {
-          const char* e = getenv("TSDE_MLP_INTERLEAVE");
-          return e == nullptr || atoi(e) != 0;
-        }();
-        if (interleave) return launch_mlp_full<D, H, ACT, R, NW, SCHEME, true, true>(p, s);
-      }
-      return launch_mlp_full<D, H, ACT, R, NW, SCHEME, true>(p, s);
-    }
-  }
-  return launch_mlp_full<D, H, ACT, R, NW, SCHEME, false>(p, s);
-}
-
 // Variant choice (tools/bench_mlp_trajectory.py, MI355X): 16-row waves in 8-wave blocks everywhere. The weights of a
 // d = hidden = 128 net fill the LDS of a CU, so all waves of a CU share one block; 16-row waves then put two waves
 // on every SIMD (one's RNG / activation / update overlaps the other's MFMAs) at the same 128 rows per CU: 10.9 ms
 // vs 12.1 ms for 32-row waves at B 32768 x 500 steps, 6.6 vs 6.9 ms at d = hidden = 64. TSDE_MLP_VARIANT=32
 // selects the 32x32x2 form (kept for the tests: both layouts must agree).
-template <int D, int H, int ACT>
-static hipError_t launch_mlp_dh(const MlpArgs& p, hipStream_t s) {
-  static const int forced = [] {
-    const char* e = getenv("TSDE_MLP_VARIANT");
-    return e ? atoi(e) : 0;
-  }();
-  if (p.method == TSDE_TRAJ_MIDPOINT) {
-    if (forced == 32) return launch_mlp_variant<D, H, ACT, 32, 4, 1>(p, s);
-    return launch_mlp_variant<D, H, ACT, 16, 8, 1>(p, s);
-  }
-  if (p.method == TSDE_TRAJ_SRK) {
-    // five state-sized arrays live across the drift evaluations. d = hidden = 128, 32768 x 500 steps: 8-wave blocks (two
-    // waves per SIMD, 70 spilled dwords) 43.0 ms, 4-wave blocks (one wave per SIMD, no spills) 49.0 ms
-    if constexpr (D >= 128) {
-      static const int waves = [] {
-        const char* e = getenv("TSDE_MLP_SRK_WAVES");
-        return e ? atoi(e) : 0;
-      }();
-      if (waves == 4) return launch_mlp_variant<D, H, ACT, 16, 4, 2>(p, s);
-      return launch_mlp_variant<D, H, ACT, 16, 8, 2>(p, s);
+struct MlpSamplingPolicy {
+  template <int D, int H, int ACT, int R, int NW, int SCHEME, bool FULL>
+  static hipError_t variant(const MlpArgs& p, hipStream_t s) {
+    const size_t lds_bytes = MlpLds<R>::bytes(D, H);
+    // (the multi-stage schemes keep the bounds tests even for unpadded shapes: without them hipcc's schedule of the wider
+    //  basic blocks needs MORE registers -- 390 spilled dwords instead of 62 for the midpoint scheme at d = hidden = 128)
+    if constexpr (SCHEME == 0 && FULL) {
+      if constexpr (R == 16) {
+        static const bool interleave = [] {
+          const char* e = getenv("TSDE_MLP_INTERLEAVE");
+          return e == nullptr || atoi(e) != 0;
+        }();
+        if (interleave)
+          return launch_rows_per_wave<mlp_trajectory_kernel<D, H, ACT, R, NW, SCHEME, true, true>, NW, R>(p, lds_bytes, s);
+      }
+      return launch_rows_per_wave<mlp_trajectory_kernel<D, H, ACT, R, NW, SCHEME, true>, NW, R>(p, lds_bytes, s);
     } else {
-      return launch_mlp_variant<D, H, ACT, 16, 8, 2>(p, s);
+      return launch_rows_per_wave<mlp_trajectory_kernel<D, H, ACT, R, NW, SCHEME, false>, NW, R>(p, lds_bytes, s);
     }
   }
-  if (forced == 32) return launch_mlp_variant<D, H, ACT, 32, 4, 0>(p, s);
-  return launch_mlp_variant<D, H, ACT, 16, 8, 0>(p, s);
-}
-
-template <int D, int H>
-static hipError_t launch_mlp_act(const MlpArgs& p, int act, hipStream_t s) {
-  if (act == TSDE_ACT_TANH) return launch_mlp_dh<D, H, TSDE_ACT_TANH>(p, s);
-  if (act == TSDE_ACT_SOFTPLUS) return launch_mlp_dh<D, H, TSDE_ACT_SOFTPLUS>(p, s);
-  return hipErrorInvalidValue;
-}
-
-template <int D>
-static hipError_t launch_mlp_h(const MlpArgs& p, int act, hipStream_t s) {
-  if (p.h <= 32) return launch_mlp_act<D, 32>(p, act, s);
-  if (p.h <= 64) return launch_mlp_act<D, 64>(p, act, s);
-  if (p.h <= 128) return launch_mlp_act<D, 128>(p, act, s);
-  if constexpr (D <= 64) {                 // both weight arrays must fit the LDS of a CU: d * hidden <= 16384
-    if (p.h <= 256) return launch_mlp_act<D, 256>(p, act, s);
+  template <int D, int H, int ACT, bool FULL>
+  static hipError_t launch(const MlpArgs& p, hipStream_t s) {
+    static const int forced = [] {
+      const char* e = getenv("TSDE_MLP_VARIANT");
+      return e ? atoi(e) : 0;
+    }();
+    if (p.method == TSDE_TRAJ_MIDPOINT) {
+      if (forced == 32) return variant<D, H, ACT, 32, 4, 1, FULL>(p, s);
+      return variant<D, H, ACT, 16, 8, 1, FULL>(p, s);
+    }
+    if (p.method == TSDE_TRAJ_SRK) {
+      // five state-sized arrays live across the drift evaluations. d = hidden = 128, 32768 x 500 steps: 8-wave blocks (two
+      // waves per SIMD, 70 spilled dwords) 43.0 ms, 4-wave blocks (one wave per SIMD, no spills) 49.0 ms
+      if constexpr (D >= 128) {
+        static const int waves = [] {
+          const char* e = getenv("TSDE_MLP_SRK_WAVES");
+          return e ? atoi(e) : 0;
+        }();
+        if (waves == 4) return variant<D, H, ACT, 16, 4, 2, FULL>(p, s);
+      }
+      return variant<D, H, ACT, 16, 8, 2, FULL>(p, s);
+    }
+    if (forced == 32) return variant<D, H, ACT, 32, 4, 0, FULL>(p, s);
+    return variant<D, H, ACT, 16, 8, 0, FULL>(p, s);
   }
-  return hipErrorInvalidValue;
-}
+};
 
-// The KL instantiation: the plain 16-row schedule in 8-wave blocks (TSDE_MLP_VARIANT / TSDE_MLP_INTERLEAVE do not reach it).
-template <int D, int H, int ACT, bool FULL>
-static hipError_t launch_mlp_kl_full(const MlpKlArgs& p, hipStream_t s) {
-  constexpr int R = 16, NW = 8;
-  const size_t lds_bytes = MlpLds<R>::bytes(D, H) + 2 * D * sizeof(float);
-  static bool configured = false;   // per instantiation
-  if (!configured) {
-    const hipError_t e =
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_trajectory_kernel<D, H, ACT, R, NW, 0, FULL, false, true>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return e;
-    configured = true;
+// The KL instantiation: the plain 16-row schedule in 8-wave blocks (TSDE_MLP_VARIANT / TSDE_MLP_INTERLEAVE do not reach it),
+// hr and hs behind b2 / c / e in LDS.
+struct MlpSamplingKlPolicy {
+  template <int D, int H, int ACT, bool FULL>
+  static hipError_t launch(const MlpKlArgs& p, hipStream_t s) {
+    return launch_rows_per_wave<mlp_trajectory_kernel<D, H, ACT, 16, 8, 0, FULL, false, true>, 8, 16>(
+        p, MlpLds<16>::bytes(D, H, 5), s);
   }
-  const int64_t rows_per_block = NW * R;
-  const int64_t blocks = (p.B + rows_per_block - 1) / rows_per_block;
-  hipLaunchKernelGGL((mlp_trajectory_kernel<D, H, ACT, R, NW, 0, FULL, false, true>), dim3((unsigned)blocks), dim3(NW * 64),
-                     lds_bytes, s, p);
-  return hipGetLastError();
-}
-
-template <int D, int H>
-static hipError_t launch_mlp_kl_act(const MlpKlArgs& p, int act, hipStream_t s) {
-  const bool full = p.d == D && p.h == H;
-  if (act == TSDE_ACT_TANH)
-    return full ? launch_mlp_kl_full<D, H, TSDE_ACT_TANH, true>(p, s) : launch_mlp_kl_full<D, H, TSDE_ACT_TANH, false>(p, s);
-  if (act == TSDE_ACT_SOFTPLUS)
-    return full ? launch_mlp_kl_full<D, H, TSDE_ACT_SOFTPLUS, true>(p, s)
-                : launch_mlp_kl_full<D, H, TSDE_ACT_SOFTPLUS, false>(p, s);
-  return hipErrorInvalidValue;
-}
-
-template <int D>
-static hipError_t launch_mlp_kl_h(const MlpKlArgs& p, int act, hipStream_t s) {
-  if (p.h <= 32) return launch_mlp_kl_act<D, 32>(p, act, s);
-  if (p.h <= 64) return launch_mlp_kl_act<D, 64>(p, act, s);
-  if (p.h <= 128) return launch_mlp_kl_act<D, 128>(p, act, s);
-  if constexpr (D <= 64) {
-    if (p.h <= 256) return launch_mlp_kl_act<D, 256>(p, act, s);
-  }
-  return hipErrorInvalidValue;
-}
+};
 
 static void fill_mlp_args(MlpArgs& p, void* ys, const void* y0, int64_t rows, int64_t d, int64_t h, const void* W1,
                           const void* b1, const void* W2, const void* b2, const void* c, const void* e, int diff_kind,
                           double diff_amp, int method, const tsde_traj_t* tr, NoiseKey key, const uint64_t* key_dev) {
+  fill_mlp_core(p, rows, d, h, W1, b1, W2, c, e, diff_kind, diff_amp, tr, key, key_dev);
   p.ys = (float*)ys;
   p.y0 = (const float*)y0;
-  p.W1 = (const float*)W1;
-  p.b1 = (const float*)b1;
-  p.W2 = (const float*)W2;
   p.b2 = (const float*)b2;
-  p.c = (const float*)c;
-  p.e = (const float*)e;
-  p.rows = (const float*)tr->step_rows;
-  p.cells = tr->cells;
   p.out_step = tr->out_step;
   p.out_w = (const float*)tr->out_w;
-  p.B = rows;
-  p.d = (int32_t)d;
-  p.h = (int32_t)h;
   p.n_steps = tr->n_steps;
   p.n_out = tr->n_out;
   p.method = method;
-  p.diff_kind = diff_kind;
-  p.diff_amp = (float)diff_amp;
-  p.key = key;
-  p.key_dev = key_dev;
 }
 
 hipError_t launch_trajectory_mlp_diag_logqp(void* ys, void* logqp, const void* y0, int64_t rows, int64_t d, int64_t h,
@@ -760,10 +671,7 @@ hipError_t launch_trajectory_mlp_diag_logqp(void* ys, void* logqp, const void* y
   p.logqp = (float*)logqp;
   p.bm_stride = d + 1;
   if (rows <= 0 || tr->n_steps <= 0) return hipSuccess;
-  if (d <= 32) return launch_mlp_kl_h<32>(p, act, s);
-  if (d <= 64) return launch_mlp_kl_h<64>(p, act, s);
-  if (d <= 128) return launch_mlp_kl_h<128>(p, act, s);
-  return hipErrorInvalidValue;
+  return mlp_ladder<MlpSamplingKlPolicy>(p, act, s);
 }
 
 hipError_t launch_trajectory_mlp_diag(void* ys, const void* y0, int64_t rows, int64_t d, int64_t h, const void* W1,
@@ -773,10 +681,7 @@ hipError_t launch_trajectory_mlp_diag(void* ys, const void* y0, int64_t rows, in
   MlpArgs p;
   fill_mlp_args(p, ys, y0, rows, d, h, W1, b1, W2, b2, c, e, diff_kind, diff_amp, method, tr, key, key_dev);
   if (rows <= 0 || tr->n_steps <= 0) return hipSuccess;
-  if (d <= 32) return launch_mlp_h<32>(p, act, s);
-  if (d <= 64) return launch_mlp_h<64>(p, act, s);
-  if (d <= 128) return launch_mlp_h<128>(p, act, s);
-  return hipErrorInvalidValue;
+  return mlp_ladder<MlpSamplingPolicy>(p, act, s);
 }
 
 }  // namespace tsde

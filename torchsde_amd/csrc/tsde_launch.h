@@ -58,6 +58,81 @@ hipError_t launch_weights_resident(const Args& p, int outp, size_t lds_bytes, hi
   return hipGetLastError();
 }
 
+// ---- the perceptron-drift kernels (mlp_trajectory.hip, mlp_backward.hip, mlp_adjoint.hip) ----------------------------------
+
+// What the argument structs of all of them hold under the same names -- the weights, b1, the diffusion's c, e, kind and
+// amplitude, the schedule's rows and cells, B, d, h and the noise key -- filled from the C-level arguments. (Not a common base
+// struct: a base moves these fields to the front of the kernel arguments, and that order is part of what the scalar register
+// allocation of the kernels depends on -- profiles/perceptron_frame_resource_usage_notes.txt.)
+template <typename Args>
+void fill_mlp_core(Args& p, int64_t rows, int64_t d, int64_t h, const void* W1, const void* b1, const void* W2, const void* c,
+                   const void* e, int diff_kind, double diff_amp, const tsde_traj_t* tr, NoiseKey key,
+                   const uint64_t* key_dev) {
+  p.W1 = (const float*)W1;
+  p.b1 = (const float*)b1;
+  p.W2 = (const float*)W2;
+  p.c = (const float*)c;
+  p.e = (const float*)e;
+  p.diff_kind = diff_kind;
+  p.diff_amp = (float)diff_amp;
+  p.rows = (const float*)tr->step_rows;
+  p.cells = tr->cells;
+  p.B = rows;
+  p.d = (int32_t)d;
+  p.h = (int32_t)h;
+  p.key = key;
+  p.key_dev = key_dev;
+}
+
+// Launch of such a kernel, `Kernel(p)`: a block of NW waves, each owning R batch rows for the whole launch, all sharing one copy
+// of the weights in `lds_bytes` of dynamic LDS, which the kernel is allowed once per instantiation.
+template <auto Kernel, int NW, int R, typename Args>
+hipError_t launch_rows_per_wave(const Args& p, size_t lds_bytes, hipStream_t s) {
+  static bool configured = false;
+  if (!configured) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             (int)lds_bytes);
+    if (e != hipSuccess) return e;
+    configured = true;
+  }
+  const int64_t rows_per_block = NW * R;
+  const int64_t blocks = (p.B + rows_per_block - 1) / rows_per_block;
+  hipLaunchKernelGGL(Kernel, dim3((unsigned)blocks), dim3(NW * 64), lds_bytes, s, p);
+  return hipGetLastError();
+}
+
+// The tile sizes of a launch: the smallest D in {32, 64, 128} and H in {32, 64, 128, 256} that hold (p.d, p.h) -- H = 256 for
+// D <= 64 only: both weight arrays must fit the LDS of a CU, d * hidden <= 16384 -- the activation, and FULL where nothing is
+// padded. Which kernel, how many waves and how much LDS that means is `Policy::launch<D, H, ACT, FULL>(p, s)`.
+template <typename Policy, int D, int H, typename Args>
+hipError_t mlp_ladder_act(const Args& p, int act, hipStream_t s) {
+  const bool full = p.d == D && p.h == H;
+  if (act == TSDE_ACT_TANH)
+    return full ? Policy::template launch<D, H, TSDE_ACT_TANH, true>(p, s)
+                : Policy::template launch<D, H, TSDE_ACT_TANH, false>(p, s);
+  if (act == TSDE_ACT_SOFTPLUS)
+    return full ? Policy::template launch<D, H, TSDE_ACT_SOFTPLUS, true>(p, s)
+                : Policy::template launch<D, H, TSDE_ACT_SOFTPLUS, false>(p, s);
+  return hipErrorInvalidValue;
+}
+template <typename Policy, int D, typename Args>
+hipError_t mlp_ladder_h(const Args& p, int act, hipStream_t s) {
+  if (p.h <= 32) return mlp_ladder_act<Policy, D, 32>(p, act, s);
+  if (p.h <= 64) return mlp_ladder_act<Policy, D, 64>(p, act, s);
+  if (p.h <= 128) return mlp_ladder_act<Policy, D, 128>(p, act, s);
+  if constexpr (D <= 64) {
+    if (p.h <= 256) return mlp_ladder_act<Policy, D, 256>(p, act, s);
+  }
+  return hipErrorInvalidValue;
+}
+template <typename Policy, typename Args>
+hipError_t mlp_ladder(const Args& p, int act, hipStream_t s) {
+  if (p.d <= 32) return mlp_ladder_h<Policy, 32>(p, act, s);
+  if (p.d <= 64) return mlp_ladder_h<Policy, 64>(p, act, s);
+  if (p.d <= 128) return mlp_ladder_h<Policy, 128>(p, act, s);
+  return hipErrorInvalidValue;
+}
+
 struct QueryArgs {
   const double* edges;  // device pointer, n_cells + 1 doubles
   int64_t ca, cb;

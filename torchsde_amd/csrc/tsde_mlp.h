@@ -207,10 +207,38 @@ struct PairLayout {
 };
 TSDE_D int pair_slot(int o) { return 32 * (o >> 5) + 2 * (o & 15) + ((o >> 4) & 1); }
 
+// ---- perceptron drift: mlp_trajectory.hip, mlp_backward.hip, mlp_adjoint.hip ------------------------------------------------
+
+// The LDS of a block, in floats from its start: W1s (D rows of H + kPad), W2s (H rows of D + kPad), b1s (H), then `vectors`
+// per-channel arrays of D (b2 / c / e, ...), then `extra` floats of the kernel's own (the adjoint's per-wave sums). The kernels
+// carve their pointers with w2 / b1 / vec and the launchers ask `bytes` for the same (vectors, extra): one formula.
 template <int R>
 struct MlpLds {
   static constexpr int kPad = (R == 16) ? 4 : 0;
-  static constexpr size_t bytes(int d, int h) { return (size_t)(d * (h + kPad) + h * (d + kPad) + h + 3 * d) * sizeof(float); }
+  static constexpr int w2(int d, int h) { return d * (h + kPad); }
+  static constexpr int b1(int d, int h) { return w2(d, h) + h * (d + kPad); }
+  static constexpr int vec(int d, int h, int i) { return b1(d, h) + h + i * d; }
+  static constexpr size_t bytes(int d, int h, int vectors = 3, int extra = 0) {
+    return (size_t)(vec(d, h, vectors) + extra) * sizeof(float);
+  }
 };
+
+// Staging of the net into LDS by the two gradient kernels (called by all THREADS threads of a block, before its barrier):
+// W1s[channel][hidden unit], W2s[hidden unit][channel] and b1s, zero-padded from (dT, hT) to the tile sizes (D, H) -- padded
+// hidden units see zero weights both ways, padded state channels are never read back. As stage_two_nets: the order of these
+// loops is part of what the register allocation of the step bodies depends on. The per-channel vectors stay with each kernel,
+// and so does the whole staging of the sampling kernel, whose explicitly scheduled form stores the transposes.
+template <int D, int H, int R, int THREADS>
+TSDE_D void stage_perceptron(float* lds, const float* W1, const float* W2, const float* b1, int dT, int hT) {
+  using L = MlpLds<R>;
+  constexpr int S1 = H + L::kPad, S2 = D + L::kPad;
+  float *W1s = lds, *W2s = lds + L::w2(D, H), *b1s = lds + L::b1(D, H);
+  for (int i = threadIdx.x; i < D * H; i += THREADS) {
+    const int k1 = i / H, m1 = i % H, k2 = i / D, m2 = i % D;
+    W1s[k1 * S1 + m1] = (k1 < dT && m1 < hT) ? W1[k1 * hT + m1] : 0.0f;
+    W2s[k2 * S2 + m2] = (k2 < hT && m2 < dT) ? W2[k2 * dT + m2] : 0.0f;
+  }
+  for (int i = threadIdx.x; i < H; i += THREADS) b1s[i] = i < hT ? b1[i] : 0.0f;
+}
 
 }  // namespace tsde

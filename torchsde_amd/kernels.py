@@ -1228,6 +1228,61 @@ def gram(a, b, blocks=512, column_sums=False):
     return (out, sums) if column_sums else out
 
 
+class PerceptronGradients:
+    """What the passes over the perceptron-drift kernels share on the host (`_MlpTrajectoryFn`, and mlp_adjoint's
+    `_MlpAdjointFn`, `_MlpLogqpAdjointFn`): the tensors as the kernels read them, the per-chunk stash, and the four weight- and
+    bias-gradient sums, to which every chunk adds its two `gram` products."""
+
+    @staticmethod
+    def prepare(d, w1, b1, w2, b2, rate, shift):
+        """(w1_in, b1, w2_in, b2, rate, shift) detached and contiguous: the weights input-major -- (d, hidden) and (hidden, d),
+        as the kernels read them -- and the diffusion's rate and shift expanded to d channels."""
+        coefs = [p.detach().reshape(-1).expand(d).contiguous() for p in (rate, shift)]
+        return (w1.detach().t().contiguous(), b1.detach().contiguous(), w2.detach().t().contiguous(),
+                b2.detach().contiguous(), coefs[0], coefs[1])
+
+    @staticmethod
+    def chunk_length(n_steps, rows, floats_per_row, budget):
+        """Steps per launch of a reverse pass that stashes `floats_per_row` floats per row and step (d + 2 hidden for the
+        training sweep, 2 d + 2 hidden for the adjoint) within `budget` bytes. Chunk boundaries fix the order in which the
+        partial weight gradients are summed: the gradients' bits depend on this number."""
+        per_step = rows * floats_per_row * 4
+        return int(max(1, min(n_steps, budget // max(per_step, 1))))
+
+    def __init__(self, rows, d, hidden, device):
+        self.rows = rows
+        self.g_w1 = torch.zeros((hidden, d), dtype=torch.float32, device=device)
+        self.g_w2 = torch.zeros((d, hidden), dtype=torch.float32, device=device)
+        self.g_b1 = torch.zeros(hidden, dtype=torch.float32, device=device)
+        self.g_b2 = torch.zeros(d, dtype=torch.float32, device=device)
+
+    def stashes(self, chunk, widths):
+        """One (chunk, rows, width) array per entry of `widths`."""
+        return tuple(torch.empty((chunk, self.rows, w), dtype=torch.float32, device=self.g_w1.device) for w in widths)
+
+    def accumulate(self, n, cotangent, hid, delta, y):
+        """A chunk of n steps joins the sums: dL/dW2, dL/db2 from (dt * cotangent)^T hid, then dL/dW1, dL/db1 from delta^T y
+        (each argument: at least n steps of (rows, width))."""
+        def flat(t):
+            return t[:n].reshape(n * self.rows, t.shape[2])
+        for g_w, g_b, a, b in ((self.g_w2, self.g_b2, cotangent, hid), (self.g_w1, self.g_b1, delta, y)):
+            weight, bias = gram(flat(a), flat(b), column_sums=True)
+            g_w += weight
+            g_b += bias
+
+    @staticmethod
+    def diffusion_gradients(row_sums, param_shapes):
+        """dL/d(rate), dL/d(shift) in the parameters' own shapes from the per-row sums (rows, d): per channel, or summed over
+        the channels for a parameter that all of them share."""
+        d = row_sums[0].shape[1]
+        grads = []
+        for acc, shape in zip(row_sums, param_shapes):
+            per_channel = acc.sum(dim=0)
+            grads.append(per_channel.reshape(shape) if int(np.prod(shape, dtype=np.int64)) == d and len(shape) == 1
+                         else per_channel.sum().reshape(shape))
+        return grads
+
+
 _boundary_tables = collections.OrderedDict()
 
 
@@ -1261,18 +1316,14 @@ class _MlpTrajectoryFn(torch.autograd.Function):
 
     @staticmethod
     def _chunk(n_steps, rows, d, hidden):
-        per_step = rows * (d + 2 * hidden) * 4
-        return int(max(1, min(n_steps, _MlpTrajectoryFn.STASH_BYTES // max(per_step, 1))))
+        return PerceptronGradients.chunk_length(n_steps, rows, d + 2 * hidden, _MlpTrajectoryFn.STASH_BYTES)
 
     @staticmethod
     def forward(ctx, activation, diffusion, method, schedule_all, out_steps, bm, y0, w1, b1, w2, b2, rate, shift):
         rows, d = y0.shape
         hidden, n_steps = b1.numel(), schedule_all.n_steps
         y0c = _native.contiguous(y0.detach())
-        coefs = [p.detach().reshape(-1).expand(d).contiguous() for p in (rate, shift)]
-        w1_in = w1.detach().t().contiguous()                # (d, hidden): input-major, as the kernels read it
-        w2_in = w2.detach().t().contiguous()                # (hidden, d)
-        b1c, b2c = b1.detach().contiguous(), b2.detach().contiguous()
+        net = PerceptronGradients.prepare(d, w1, b1, w2, b2, rate, shift)
         budget = _MlpTrajectoryFn.STATE_BYTES
         if budget is None:
             budget = torch.cuda.mem_get_info(y0.device)[0] // 2
@@ -1288,10 +1339,9 @@ class _MlpTrajectoryFn(torch.autograd.Function):
                                                  [(0.0, 1.0)] * len(marks), y0.device, y0.dtype)
         states = torch.empty((schedule.n_out + 1, rows, d), dtype=y0.dtype, device=y0.device)
         states[0].copy_(y0c)
-        trajectory_mlp_diag(states[1:], y0c, w1_in, b1c, w2_in, b2c, coefs[0], coefs[1], activation, diffusion, method,
-                            schedule, bm)
+        trajectory_mlp_diag(states[1:], y0c, *net, activation, diffusion, method, schedule, bm)
         ctx.grad_step = _boundary_table(out_steps, y0.device)
-        ctx.save_for_backward(states, w1_in, b1c, w2_in, b2c, coefs[0], coefs[1])
+        ctx.save_for_backward(states, *net)
         ctx.method, ctx.activation, ctx.hidden = int(method), int(activation), hidden
         ctx.diffusion = (int(diffusion[0]), float(diffusion[1]))
         ctx.schedule, ctx.bm, ctx.out_steps, ctx.kept_at = schedule_all, bm, out_steps, kept_at
@@ -1311,18 +1361,12 @@ class _MlpTrajectoryFn(torch.autograd.Function):
         gys = _native.contiguous(gys)
         boundaries = np.asarray([0] + list(ctx.out_steps), dtype=np.int32)
         chunk = _MlpTrajectoryFn._chunk(n_steps, rows, d, hidden)
-        stash_lam = torch.empty((chunk, rows, d), dtype=torch.float32, device=dev)
-        stash_hid = torch.empty((chunk, rows, hidden), dtype=torch.float32, device=dev)
-        stash_delta = torch.empty((chunk, rows, hidden), dtype=torch.float32, device=dev)
+        sums = PerceptronGradients(rows, d, hidden, dev)
+        stash_lam, stash_hid, stash_delta = sums.stashes(chunk, (d, hidden, hidden))
         rerun = None if kept_at is None else torch.empty((chunk + 1, rows, d), dtype=torch.float32, device=dev)
         lam = torch.zeros((rows, d), dtype=torch.float32, device=dev)
         row_rate, row_shift = torch.zeros_like(lam), torch.zeros_like(lam)
-        g_w1 = torch.zeros((hidden, d), dtype=torch.float32, device=dev)
-        g_w2 = torch.zeros((d, hidden), dtype=torch.float32, device=dev)
-        g_b1 = torch.zeros(hidden, dtype=torch.float32, device=dev)
-        g_b2 = torch.zeros(d, dtype=torch.float32, device=dev)
         lib, dt_code, stream = _launch_env(states)
-        entropy_dev = bm._entropy_dev
         for k_hi in range(n_steps, 0, -chunk):
             k_lo = max(0, k_hi - chunk)
             n = k_hi - k_lo
@@ -1338,24 +1382,13 @@ class _MlpTrajectoryFn(torch.autograd.Function):
                 lam.data_ptr(), stash_lam.data_ptr(), stash_hid.data_ptr(), stash_delta.data_ptr(), row_rate.data_ptr(),
                 row_shift.data_ptr(), ys.data_ptr(), ys_first, gys.data_ptr(), ctx.grad_step.data_ptr(), grad_last,
                 rows, d, hidden, w1_in.data_ptr(), b1c.data_ptr(), w2_in.data_ptr(), rate.data_ptr(), shift.data_ptr(),
-                ctx.diffusion[0], ctx.diffusion[1], ctx.activation, ctx.method, schedule.struct(), k_lo, k_hi, bm._key,
-                bm._elem0, None if entropy_dev is None else entropy_dev.data_ptr(), dt_code, stream)
+                ctx.diffusion[0], ctx.diffusion[1], ctx.activation, ctx.method,
+                *_native.sweep_tail(schedule, k_lo, k_hi, bm, dt_code, stream))
             _native.check(code, "tsde_trajectory_mlp_diag_backward")
-            flat_lam = stash_lam[:n].reshape(n * rows, d)
-            flat_hid = stash_hid[:n].reshape(n * rows, hidden)
-            flat_delta = stash_delta[:n].reshape(n * rows, hidden)
-            flat_y = ys[k_lo - ys_first:k_hi - ys_first].reshape(n * rows, d)
-            for g_w, g_b, a, b in ((g_w2, g_b2, flat_lam, flat_hid), (g_w1, g_b1, flat_delta, flat_y)):
-                weight, bias = gram(a, b, column_sums=True)
-                g_w += weight
-                g_b += bias
+            sums.accumulate(n, stash_lam, stash_hid, stash_delta, ys[k_lo - ys_first:k_hi - ys_first])
         grad_y0 = lam + gys[0] if ctx.needs_input_grad[6] else None
-        diffusion = []
-        for acc, shape in zip((row_rate, row_shift), ctx.param_shapes):
-            per_channel = acc.sum(dim=0)
-            diffusion.append(per_channel.reshape(shape) if int(np.prod(shape, dtype=np.int64)) == d and len(shape) == 1
-                             else per_channel.sum().reshape(shape))
-        return (None, None, None, None, None, None, grad_y0, g_w1, g_b1, g_w2, g_b2, diffusion[0], diffusion[1])
+        diffusion = PerceptronGradients.diffusion_gradients((row_rate, row_shift), ctx.param_shapes)
+        return (None, None, None, None, None, None, grad_y0, sums.g_w1, sums.g_b1, sums.g_w2, sums.g_b2, *diffusion)
 
 
 def trajectory_mlp_diag_differentiable(y0, module_params, activation, diffusion, method, schedule_all, out_steps, bm):

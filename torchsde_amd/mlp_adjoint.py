@@ -16,7 +16,6 @@ two kernels (``tsde_trajectory_mlp_diag_logqp``, ``tsde_adjoint_mlp_diag_logqp``
 in y and does not read t: `plan_logqp`, `_MlpLogqpAdjointFn`. The row sum of the column is an f32 sum in the kernel's own
 order, so this route agrees with the stepwise one to rounding, not bit for bit.
 """
-import numpy as np
 import torch
 
 from . import _native
@@ -45,13 +44,11 @@ def adjoint_mlp_diag(y, a, stashes, row_rate, row_shift, w1, b1, w2, b2, rate, s
     stash_a, stash_hid, stash_delta, stash_y = stashes
     rows, d = y.shape
     lib, dt_code, stream = K._launch_env(y)
-    entropy_dev = bm._entropy_dev
     code = lib.tsde_adjoint_mlp_diag(
         y.data_ptr(), a.data_ptr(), stash_a.data_ptr(), stash_hid.data_ptr(), stash_delta.data_ptr(), stash_y.data_ptr(),
         row_rate.data_ptr(), row_shift.data_ptr(), rows, d, b1.numel(), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(),
         b2.data_ptr(), rate.data_ptr(), shift.data_ptr(), int(diffusion[0]), float(diffusion[1]), int(activation),
-        (1 if ito else 0) | (2 if milstein else 0), schedule.struct(), int(k_lo), int(k_hi), bm._key, bm._elem0,
-        None if entropy_dev is None else entropy_dev.data_ptr(), dt_code, stream)
+        (1 if ito else 0) | (2 if milstein else 0), *_native.sweep_tail(schedule, k_lo, k_hi, bm, dt_code, stream))
     _native.check(code, "tsde_adjoint_mlp_diag")
 
 
@@ -83,13 +80,12 @@ def adjoint_mlp_diag_logqp(y, a, a_l, stashes, row_sums, w1, b1, w2, b2, rate, s
     stash_a, stash_hid, stash_delta, stash_y = stashes
     rows, d = y.shape
     lib, dt_code, stream = K._launch_env(y)
-    entropy_dev = bm._entropy_dev
     code = lib.tsde_adjoint_mlp_diag_logqp(
         y.data_ptr(), a.data_ptr(), a_l.data_ptr(), stash_a.data_ptr(), stash_hid.data_ptr(), stash_delta.data_ptr(),
         stash_y.data_ptr(), *(t.data_ptr() for t in row_sums), rows, d, b1.numel(), w1.data_ptr(), b1.data_ptr(),
         w2.data_ptr(), b2.data_ptr(), rate.data_ptr(), shift.data_ptr(), prior_rate.data_ptr(), prior_shift.data_ptr(),
-        int(diffusion[0]), float(diffusion[1]), int(activation), 1 | (2 if milstein else 0), schedule.struct(), int(k_lo),
-        int(k_hi), bm._key, bm._elem0, None if entropy_dev is None else entropy_dev.data_ptr(), dt_code, stream)
+        int(diffusion[0]), float(diffusion[1]), int(activation), 1 | (2 if milstein else 0),
+        *_native.sweep_tail(schedule, k_lo, k_hi, bm, dt_code, stream))
     _native.check(code, "tsde_adjoint_mlp_diag_logqp")
 
 
@@ -100,19 +96,19 @@ class _MlpAdjointFn(torch.autograd.Function):
     STASH_BYTES = 3 << 30      # per-chunk stash of the backward sweep (four (steps, rows, width) float32 arrays)
 
     @staticmethod
+    def _chunk(n_steps, rows, d, hidden):
+        return K.PerceptronGradients.chunk_length(n_steps, rows, 2 * d + 2 * hidden, _MlpAdjointFn.STASH_BYTES)
+
+    @staticmethod
     def forward(ctx, activation, diffusion, method_code, ito, backward_kind, schedule, backward_schedule, out_steps, bm,
                 y0, w1, b1, w2, b2, rate, shift):
         rows, d = y0.shape
         y0c = _native.contiguous(y0.detach())
-        coefs = [p.detach().reshape(-1).expand(d).contiguous() for p in (rate, shift)]
-        w1_in = w1.detach().t().contiguous()                # (d, hidden): input-major, as the kernels read it
-        w2_in = w2.detach().t().contiguous()                # (hidden, d)
-        b1c, b2c = b1.detach().contiguous(), b2.detach().contiguous()
+        net = K.PerceptronGradients.prepare(d, w1, b1, w2, b2, rate, shift)
         ys = torch.empty((len(out_steps) + 1, rows, d), dtype=y0.dtype, device=y0.device)
         ys[0].copy_(y0c)
-        K.trajectory_mlp_diag(ys[1:], y0c, w1_in, b1c, w2_in, b2c, coefs[0], coefs[1], activation, diffusion, method_code,
-                              schedule, bm)
-        ctx.save_for_backward(ys, w1_in, b1c, w2_in, b2c, coefs[0], coefs[1])
+        K.trajectory_mlp_diag(ys[1:], y0c, *net, activation, diffusion, method_code, schedule, bm)
+        ctx.save_for_backward(ys, *net)
         ctx.activation, ctx.diffusion, ctx.ito = int(activation), (int(diffusion[0]), float(diffusion[1])), bool(ito)
         ctx.backward_kind = backward_kind
         ctx.schedule, ctx.bm, ctx.out_steps = backward_schedule, bm, tuple(out_steps)
@@ -129,47 +125,27 @@ class _MlpAdjointFn(torch.autograd.Function):
         hidden = b1c.numel()
         dev = ys.device
         gys = _native.contiguous(gys)
-        per_step = rows * (2 * d + 2 * hidden) * 4
-        chunk = int(max(1, min(ctx.schedule.n_steps, _MlpAdjointFn.STASH_BYTES // max(per_step, 1))))
-        stashes = (torch.empty((chunk, rows, d), dtype=torch.float32, device=dev),
-                   torch.empty((chunk, rows, hidden), dtype=torch.float32, device=dev),
-                   torch.empty((chunk, rows, hidden), dtype=torch.float32, device=dev),
-                   torch.empty((chunk, rows, d), dtype=torch.float32, device=dev))
+        chunk = _MlpAdjointFn._chunk(ctx.schedule.n_steps, rows, d, hidden)
+        sums = K.PerceptronGradients(rows, d, hidden, dev)
+        stashes = sums.stashes(chunk, (d, hidden, hidden, d))
         row_rate = torch.zeros((rows, d), dtype=torch.float32, device=dev)
         row_shift = torch.zeros_like(row_rate)
-        g_w1 = torch.zeros((hidden, d), dtype=torch.float32, device=dev)
-        g_w2 = torch.zeros((d, hidden), dtype=torch.float32, device=dev)
-        g_b1 = torch.zeros(hidden, dtype=torch.float32, device=dev)
-        g_b2 = torch.zeros(d, dtype=torch.float32, device=dev)
         boundaries = (0,) + ctx.out_steps                   # step boundary of output i
         y = ys[-1].clone()
         a = gys[-1].clone()
         for i in range(len(boundaries) - 1, 0, -1):
             for k_hi in range(boundaries[i], boundaries[i - 1], -chunk):
                 k_lo = max(boundaries[i - 1], k_hi - chunk)
-                n = k_hi - k_lo
                 adjoint_mlp_diag(y, a, stashes, row_rate, row_shift, w1_in, b1c, w2_in, b2c, rate, shift, ctx.diffusion,
                                  ctx.activation, ctx.ito, ctx.schedule, k_lo, k_hi, ctx.bm,
                                  milstein=ctx.backward_kind == "milstein")
-                flat_a = stashes[0][:n].reshape(n * rows, d)
-                flat_hid = stashes[1][:n].reshape(n * rows, hidden)
-                flat_delta = stashes[2][:n].reshape(n * rows, hidden)
-                flat_y = stashes[3][:n].reshape(n * rows, d)
-                for g_w, g_b, lhs, rhs in ((g_w2, g_b2, flat_a, flat_hid), (g_w1, g_b1, flat_delta, flat_y)):
-                    weight, bias = K.gram(lhs, rhs, column_sums=True)
-                    g_w += weight
-                    g_b += bias
+                sums.accumulate(k_hi - k_lo, *stashes)
             # adjoint.py:114-116: the forward state is known again at an output time; its cotangent joins a_y
             y.copy_(ys[i - 1])
             a += gys[i - 1]
-        diffusion = []
-        for acc, shape in zip((row_rate, row_shift), ctx.param_shapes):
-            per_channel = acc.sum(dim=0)
-            diffusion.append(per_channel.reshape(shape) if int(np.prod(shape, dtype=np.int64)) == d and len(shape) == 1
-                             else per_channel.sum().reshape(shape))
+        diffusion = K.PerceptronGradients.diffusion_gradients((row_rate, row_shift), ctx.param_shapes)
         grad_y0 = a if ctx.needs_input_grad[9] else None
-        return (None,) * 9 + (grad_y0, g_w1, g_b1, g_w2, g_b2, diffusion[0], diffusion[1])
-
+        return (None,) * 9 + (grad_y0, sums.g_w1, sums.g_b1, sums.g_w2, sums.g_b2, *diffusion)
 
     @staticmethod
     def _backward_with_graph(ctx, gys):
@@ -204,20 +180,17 @@ class _MlpLogqpAdjointFn(torch.autograd.Function):
                 b1, w2, b2, rate, shift, hr_t, hs_t, hr, hs, *prior_params):
         rows, d = y0.shape[0], y0.shape[1] - 1
         y0d = y0.detach()
-        coefs = [p.detach().reshape(-1).expand(d).contiguous() for p in (rate, shift)]
-        w1_in = w1.detach().t().contiguous()
-        w2_in = w2.detach().t().contiguous()
-        b1c, b2c = b1.detach().contiguous(), b2.detach().contiguous()
+        net = K.PerceptronGradients.prepare(d, w1, b1, w2, b2, rate, shift)
         states = torch.empty((len(out_steps) + 1, rows, d), dtype=y0.dtype, device=y0.device)
         states[0].copy_(y0d[:, :d])
         column = torch.empty((len(out_steps), rows), dtype=y0.dtype, device=y0.device)
-        trajectory_mlp_diag_logqp(states[1:], column, states[0], w1_in, b1c, w2_in, b2c, coefs[0], coefs[1], hr, hs,
-                                  activation, diffusion, method_code, schedule, bm)
+        trajectory_mlp_diag_logqp(states[1:], column, states[0], *net, hr, hs, activation, diffusion, method_code, schedule,
+                                  bm)
         ys = torch.empty((len(out_steps) + 1, rows, d + 1), dtype=y0.dtype, device=y0.device)
         ys[:, :, :d].copy_(states)
         ys[0, :, d].copy_(y0d[:, d])
         torch.add(column, y0d[:, d], out=ys[1:, :, d])
-        ctx.save_for_backward(states, w1_in, b1c, w2_in, b2c, coefs[0], coefs[1], hr, hs, ys)
+        ctx.save_for_backward(states, *net, hr, hs, ys)
         ctx.activation, ctx.diffusion = int(activation), (int(diffusion[0]), float(diffusion[1]))
         ctx.backward_kind = backward_kind
         ctx.schedule, ctx.bm, ctx.out_steps = backward_schedule, bm, tuple(out_steps)
@@ -236,17 +209,10 @@ class _MlpLogqpAdjointFn(torch.autograd.Function):
         dev = states.device
         g_state = gys[:, :, :d].contiguous()
         g_column = gys[:, :, d].contiguous()
-        per_step = rows * (2 * d + 2 * hidden) * 4
-        chunk = int(max(1, min(ctx.schedule.n_steps, _MlpAdjointFn.STASH_BYTES // max(per_step, 1))))
-        stashes = (torch.empty((chunk, rows, d), dtype=torch.float32, device=dev),
-                   torch.empty((chunk, rows, hidden), dtype=torch.float32, device=dev),
-                   torch.empty((chunk, rows, hidden), dtype=torch.float32, device=dev),
-                   torch.empty((chunk, rows, d), dtype=torch.float32, device=dev))
+        chunk = _MlpAdjointFn._chunk(ctx.schedule.n_steps, rows, d, hidden)
+        sums = K.PerceptronGradients(rows, d, hidden, dev)
+        stashes = sums.stashes(chunk, (d, hidden, hidden, d))
         row_sums = tuple(torch.zeros((rows, d), dtype=torch.float32, device=dev) for _ in range(4))
-        g_w1 = torch.zeros((hidden, d), dtype=torch.float32, device=dev)
-        g_w2 = torch.zeros((d, hidden), dtype=torch.float32, device=dev)
-        g_b1 = torch.zeros(hidden, dtype=torch.float32, device=dev)
-        g_b2 = torch.zeros(d, dtype=torch.float32, device=dev)
         boundaries = (0,) + ctx.out_steps
         y = states[-1].clone()
         a = g_state[-1].clone()
@@ -254,31 +220,19 @@ class _MlpLogqpAdjointFn(torch.autograd.Function):
         for i in range(len(boundaries) - 1, 0, -1):
             for k_hi in range(boundaries[i], boundaries[i - 1], -chunk):
                 k_lo = max(boundaries[i - 1], k_hi - chunk)
-                n = k_hi - k_lo
                 adjoint_mlp_diag_logqp(y, a, a_l, stashes, row_sums, w1_in, b1c, w2_in, b2c, rate, shift, hr, hs,
                                        ctx.diffusion, ctx.activation, ctx.schedule, k_lo, k_hi, ctx.bm,
                                        milstein=ctx.backward_kind == "milstein")
-                flat_a = stashes[0][:n].reshape(n * rows, d)
-                flat_hid = stashes[1][:n].reshape(n * rows, hidden)
-                flat_delta = stashes[2][:n].reshape(n * rows, hidden)
-                flat_y = stashes[3][:n].reshape(n * rows, d)
-                for g_w, g_b, lhs, rhs in ((g_w2, g_b2, flat_a, flat_hid), (g_w1, g_b1, flat_delta, flat_y)):
-                    weight, bias = K.gram(lhs, rhs, column_sums=True)
-                    g_w += weight
-                    g_b += bias
+                sums.accumulate(k_hi - k_lo, *stashes)
             # adjoint.py:114-116, for the state and for the column alike
             y.copy_(states[i - 1])
             a += g_state[i - 1]
             a_l += g_column[i - 1]
-        diffusion = []
-        for acc, shape in zip(row_sums[:2], ctx.param_shapes):
-            per_channel = acc.sum(dim=0)
-            diffusion.append(per_channel.reshape(shape) if int(np.prod(shape, dtype=np.int64)) == d and len(shape) == 1
-                             else per_channel.sum().reshape(shape))
+        diffusion = K.PerceptronGradients.diffusion_gradients(row_sums[:2], ctx.param_shapes)
         grad_y0 = torch.cat((a, a_l.unsqueeze(1)), dim=1) if ctx.needs_input_grad[_MlpLogqpAdjointFn.N_PLAIN] else None
         return ((None,) * _MlpLogqpAdjointFn.N_PLAIN
-                + (grad_y0, g_w1, g_b1, g_w2, g_b2, diffusion[0], diffusion[1], row_sums[2].sum(dim=0), row_sums[3].sum(dim=0),
-                   None, None) + (None,) * ctx.n_prior)
+                + (grad_y0, sums.g_w1, sums.g_b1, sums.g_w2, sums.g_b2, *diffusion, row_sums[2].sum(dim=0),
+                   row_sums[3].sum(dim=0), None, None) + (None,) * ctx.n_prior)
 
     @staticmethod
     def _backward_with_graph(ctx, gys):

@@ -261,65 +261,65 @@ struct MergeHalvesOp {
   }
 };
 
-template <typename T>
-hipError_t launch_adaptive_begin(double* ctl, void* scal, double out_t, const double* out_times, int n_out,
+static StageFracs stage_fracs_of(const double* fracs, int n_fracs) {
+  StageFracs sf;
+  sf.n = n_fracs;
+  for (int j = 0; j < kMaxStages - 1; ++j) sf.frac[j] = j < n_fracs ? fracs[j] : 0.0;
+  return sf;
+}
+
+hipError_t launch_adaptive_begin(int dtype, double* ctl, void* scal, double out_t, const double* out_times, int n_out,
                                  const double* fracs, int n_fracs, hipStream_t s) {
-  StageFracs sf;
-  sf.n = n_fracs;
-  for (int j = 0; j < kMaxStages - 1; ++j) sf.frac[j] = j < n_fracs ? fracs[j] : 0.0;
-  hipLaunchKernelGGL(adaptive_begin_kernel<T>, dim3(1), dim3(64), 0, s, ctl, (T*)scal, out_t, out_times, n_out, sf);
-  return hipGetLastError();
+  const StageFracs sf = stage_fracs_of(fracs, n_fracs);
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(adaptive_begin_kernel<T>, dim3(1), dim3(64), 0, s, ctl, (T*)scal, out_t, out_times, n_out, sf);
+    return hipGetLastError();
+  });
 }
 
-template <typename T>
-hipError_t launch_adaptive_control(double* ctl, void* scal, const double* error, const double* out_times,
+hipError_t launch_adaptive_control(int dtype, double* ctl, void* scal, const double* error, const double* out_times,
                                    double* accept_log, int log_capacity, const double* fracs, int n_fracs, hipStream_t s) {
-  StageFracs sf;
-  sf.n = n_fracs;
-  for (int j = 0; j < kMaxStages - 1; ++j) sf.frac[j] = j < n_fracs ? fracs[j] : 0.0;
-  hipLaunchKernelGGL(adaptive_control_kernel<T>, dim3(1), dim3(64), 0, s, ctl, (T*)scal, error, out_times, accept_log,
-                     log_capacity, sf);
-  return hipGetLastError();
+  const StageFracs sf = stage_fracs_of(fracs, n_fracs);
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(adaptive_control_kernel<T>, dim3(1), dim3(64), 0, s, ctl, (T*)scal, error, out_times, accept_log,
+                       log_capacity, sf);
+    return hipGetLastError();
+  });
 }
 
-template <typename T>
-hipError_t launch_adaptive_emit(const void* ys_slot, const void* prev_y, const void* curr_y, int64_t n, const double* ctl,
-                                const double* out_times, hipStream_t s) {
-  EmitOp<T> op{(T* const*)ys_slot, (const T*)prev_y, (const T*)curr_y, ctl, out_times, n};
+hipError_t launch_adaptive_emit(int dtype, const void* ys_slot, const void* prev_y, const void* curr_y, int64_t n,
+                                const double* ctl, const double* out_times, hipStream_t s) {
   // (the rows of ys are n elements apart: 16-byte groups need n % 4 == 0; the host allocates ys 16-byte aligned)
-  const bool vec = (n % 4 == 0) && aligned16(prev_y) && aligned16(curr_y);
-  return launch_elementwise(op, n, vec, s, sizeof(T));
+  const bool vec = vec_ok(n, prev_y, curr_y);
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    EmitOp<T> op{(T* const*)ys_slot, (const T*)prev_y, (const T*)curr_y, ctl, out_times, n};
+    return launch_elementwise(op, n, vec, s, sizeof(T));
+  });
 }
 
-template <typename T>
-hipError_t launch_adaptive_commit(void* prev_y, void* curr_y, const void* y_next, int64_t n, const void* scal,
+hipError_t launch_adaptive_commit(int dtype, void* prev_y, void* curr_y, const void* y_next, int64_t n, const void* scal,
                                   hipStream_t s) {
-  CommitOp<T> op{(T*)prev_y, (T*)curr_y, (const T*)y_next, (const T*)scal + kAccept};
-  const bool vec = (n % 4 == 0) && aligned16(prev_y) && aligned16(curr_y) && aligned16(y_next);
-  return launch_elementwise(op, n, vec, s, sizeof(T));
+  const bool vec = vec_ok(n, prev_y, curr_y, y_next);
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    CommitOp<T> op{(T*)prev_y, (T*)curr_y, (const T*)y_next, (const T*)scal + kAccept};
+    return launch_elementwise(op, n, vec, s, sizeof(T));
+  });
 }
 
-template <typename T>
-hipError_t launch_merge_halves(void* W, void* U, const void* Wa, const void* Ha, const void* Wb, const void* Hb,
+hipError_t launch_merge_halves(int dtype, void* W, void* U, const void* Wa, const void* Ha, const void* Wb, const void* Hb,
                                int64_t n, const double* ctl, double ha, double hb, hipStream_t s) {
-  MergeHalvesOp<T> op{(T*)W, (T*)U, (const T*)Wa, (const T*)Ha, (const T*)Wb, (const T*)Hb, ctl ? ctl + kHa : nullptr,
-                      ha,    hb};
-  const bool vec = (n % 4 == 0) && aligned16(W) && (!U || aligned16(U)) && aligned16(Wa) && aligned16(Wb) &&
-                   (!U || (aligned16(Ha) && aligned16(Hb)));
-  return launch_elementwise(op, n, vec, s, sizeof(T));
+  // (Ha and Hb are read only where U is written)
+  const bool vec = vec_ok(n, W, U, Wa, Wb, U ? Ha : nullptr, U ? Hb : nullptr);
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    MergeHalvesOp<T> op{(T*)W, (T*)U, (const T*)Wa, (const T*)Ha, (const T*)Wb, (const T*)Hb, ctl ? ctl + kHa : nullptr,
+                        ha,    hb};
+    return launch_elementwise(op, n, vec, s, sizeof(T));
+  });
 }
-
-#define TSDE_ADAPTIVE_INSTANTIATE(T)                                                                              \
-  template hipError_t launch_adaptive_begin<T>(double*, void*, double, const double*, int, const double*, int,    \
-                                               hipStream_t);                                                      \
-  template hipError_t launch_adaptive_control<T>(double*, void*, const double*, const double*, double*, int,      \
-                                                 const double*, int, hipStream_t);                                \
-  template hipError_t launch_adaptive_emit<T>(const void*, const void*, const void*, int64_t, const double*,      \
-                                              const double*, hipStream_t);                                        \
-  template hipError_t launch_adaptive_commit<T>(void*, void*, const void*, int64_t, const void*, hipStream_t);    \
-  template hipError_t launch_merge_halves<T>(void*, void*, const void*, const void*, const void*, const void*,    \
-                                             int64_t, const double*, double, double, hipStream_t);
-TSDE_ADAPTIVE_INSTANTIATE(float)
-TSDE_ADAPTIVE_INSTANTIATE(double)
 
 }  // namespace tsde

@@ -159,34 +159,32 @@ __global__ void __launch_bounds__(kBlock) query_kernel(T* __restrict__ W, T* __r
   }
 }
 
-template <typename T>
-hipError_t launch_normals(void* out, int64_t n, NoiseKey key, uint32_t cell, uint64_t node, uint32_t stream_id,
+hipError_t launch_normals(int dtype, void* out, int64_t n, NoiseKey key, uint32_t cell, uint64_t node, uint32_t stream_id,
                           hipStream_t s) {
-  if (n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(normals_kernel<T>, dim3(grid_for((n + 3) / 4 + 1)), dim3(kBlock), 0, s, (T*)out, n, key, cell,
-                     node, stream_id);
-  return hipGetLastError();
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(normals_kernel<T>, dim3(grid_for((n + 3) / 4 + 1)), dim3(kBlock), 0, s, (T*)out, n, key, cell,
+                       node, stream_id);
+    return hipGetLastError();
+  });
 }
 
-template <typename T>
-hipError_t launch_query(void* W, void* U, void* H, int64_t n, NoiseKey key, const QueryArgs& qa, bool have_h,
+hipError_t launch_query(int dtype, void* W, void* U, void* H, int64_t n, NoiseKey key, const QueryArgs& qa, bool have_h,
                         hipStream_t s) {
-  if (n <= 0) return hipSuccess;
-  const bool vec = (key.elem0 % 4 == 0) && (n % 4 == 0) && aligned16(W) && (!U || aligned16(U)) &&
-                   (!H || aligned16(H));
-  const dim3 grid(grid_for((n + 3) / 4 + 1));
-  if (have_h) {
-    TSDE_LAUNCH((query_kernel<T, true>), grid, dim3(kBlock), 0, s, (T*)W, (T*)U, (T*)H, n, key, qa, vec ? 1 : 0);
-  } else {
-    TSDE_LAUNCH((query_kernel<T, false>), grid, dim3(kBlock), 0, s, (T*)W, (T*)nullptr, (T*)nullptr, n, key, qa,
-                vec ? 1 : 0);
-  }
-  return hipGetLastError();
+  const bool vec = (key.elem0 % 4 == 0) && vec_ok(n, W, U, H);
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    if (n <= 0) return hipSuccess;
+    const dim3 grid(grid_for((n + 3) / 4 + 1));
+    if (have_h) {
+      TSDE_LAUNCH((query_kernel<T, true>), grid, dim3(kBlock), 0, s, (T*)W, (T*)U, (T*)H, n, key, qa, vec ? 1 : 0);
+    } else {
+      TSDE_LAUNCH((query_kernel<T, false>), grid, dim3(kBlock), 0, s, (T*)W, (T*)nullptr, (T*)nullptr, n, key, qa,
+                  vec ? 1 : 0);
+    }
+    return hipGetLastError();
+  });
 }
-
-template hipError_t launch_normals<float>(void*, int64_t, NoiseKey, uint32_t, uint64_t, uint32_t, hipStream_t);
-template hipError_t launch_normals<double>(void*, int64_t, NoiseKey, uint32_t, uint64_t, uint32_t, hipStream_t);
-template hipError_t launch_query<float>(void*, void*, void*, int64_t, NoiseKey, const QueryArgs&, bool, hipStream_t);
-template hipError_t launch_query<double>(void*, void*, void*, int64_t, NoiseKey, const QueryArgs&, bool, hipStream_t);
 
 }  // namespace tsde

@@ -30,6 +30,15 @@ const char* schedule_problem(const tsde_traj_t* traj) {
   return nullptr;
 }
 
+// What tsde_step_general_w and tsde_step_shared check alike (`g`: the diffusion, per row or shared).
+const char* weighted_step_problem(const void* y1, const void* y0, const void* f, const void* g, int weight_mode,
+                                  const tsde_noise_t* noise) {
+  if (!y1 || !y0 || !f || !g || !noise) return "null argument";
+  if (weight_mode < 0 || weight_mode > 2) return "weight_mode must be 0, 1 or 2";
+  if (weight_mode != 0 && noise->dW && !noise->dU) return "weights need dU";
+  return nullptr;
+}
+
 tsde::NoiseKey make_key(uint64_t entropy, uint64_t elem0) {
   tsde::NoiseKey k;
   k.k0 = (uint32_t)entropy;
@@ -77,11 +86,11 @@ struct ProfScope {
   }
 };
 
-#define TSDE_DISPATCH(dtype, where, expr_f32, expr_f64)         \
-  do {                                                          \
-    if ((dtype) == TSDE_F32) return fail((expr_f32), where);    \
-    if ((dtype) == TSDE_F64) return fail((expr_f64), where);    \
-    return bad_arg(where, "dtype must be TSDE_F32 or TSDE_F64"); \
+// The last statement of an entry point with a state dtype: `expr` is the call of its launcher, which takes the dtype first.
+#define TSDE_DISPATCH(dtype, where, expr)                                                                          \
+  do {                                                                                                             \
+    if ((dtype) != TSDE_F32 && (dtype) != TSDE_F64) return bad_arg(where, "dtype must be TSDE_F32 or TSDE_F64");   \
+    return fail((expr), where);                                                                                    \
   } while (0)
 
 }  // namespace
@@ -112,8 +121,7 @@ int tsde_brownian_normals(void* out, int64_t n, uint64_t entropy, uint64_t elem0
                           uint32_t stream_id, int dtype, void* stream) {
   const hipStream_t s = (hipStream_t)stream;
   const tsde::NoiseKey key = make_key(entropy, elem0);
-  TSDE_DISPATCH(dtype, "tsde_brownian_normals", tsde::launch_normals<float>(out, n, key, cell, node, stream_id, s),
-                tsde::launch_normals<double>(out, n, key, cell, node, stream_id, s));
+  TSDE_DISPATCH(dtype, "tsde_brownian_normals", tsde::launch_normals(dtype, out, n, key, cell, node, stream_id, s));
 }
 
 int tsde_brownian_query(void* W, void* U, void* H, int64_t n, uint64_t entropy, uint64_t elem0, const double* edges,
@@ -141,8 +149,7 @@ int tsde_brownian_query(void* W, void* U, void* H, int64_t n, uint64_t entropy, 
   qa.cfg.max_depth = max_depth;
   qa.cfg.snap = snap;
   ProfScope p(TSDE_KID_BROWNIAN_QUERY, s, true);
-  TSDE_DISPATCH(dtype, "tsde_brownian_query", tsde::launch_query<float>(W, U, H, n, key, qa, have_h != 0, s),
-                tsde::launch_query<double>(W, U, H, n, key, qa, have_h != 0, s));
+  TSDE_DISPATCH(dtype, "tsde_brownian_query", tsde::launch_query(dtype, W, U, H, n, key, qa, have_h != 0, s));
 }
 
 int tsde_brownian_query_dev(void* W, void* U, void* H, int64_t n, uint64_t entropy, uint64_t elem0, const double* edges,
@@ -165,16 +172,14 @@ int tsde_brownian_query_dev(void* W, void* U, void* H, int64_t n, uint64_t entro
   qa.cfg.max_depth = max_depth;
   qa.cfg.snap = 0;
   ProfScope p(TSDE_KID_BROWNIAN_QUERY, s, true);
-  TSDE_DISPATCH(dtype, "tsde_brownian_query_dev", tsde::launch_query<float>(W, U, H, n, key, qa, have_h != 0, s),
-                tsde::launch_query<double>(W, U, H, n, key, qa, have_h != 0, s));
+  TSDE_DISPATCH(dtype, "tsde_brownian_query_dev", tsde::launch_query(dtype, W, U, H, n, key, qa, have_h != 0, s));
 }
 
 int tsde_cell_increment(void* W_out, void* U_out, int64_t n, const tsde_noise_t* noise, int dtype, void* stream) {
   if (!W_out || !noise) return bad_arg("tsde_cell_increment", "null argument");
   if (noise->dW) return bad_arg("tsde_cell_increment", "noise must describe a generated cell (dW == NULL)");
   const hipStream_t s = (hipStream_t)stream;
-  TSDE_DISPATCH(dtype, "tsde_cell_increment", tsde::launch_cell_increment<float>(W_out, U_out, n, noise, s),
-                tsde::launch_cell_increment<double>(W_out, U_out, n, noise, s));
+  TSDE_DISPATCH(dtype, "tsde_cell_increment", tsde::launch_cell_increment(dtype, W_out, U_out, n, noise, s));
 }
 
 int tsde_step_diag(void* y1, const void* y0, const void* f, const void* g, int64_t n, double cf, double cg,
@@ -182,16 +187,14 @@ int tsde_step_diag(void* y1, const void* y0, const void* f, const void* g, int64
   if (!y1 || !y0 || !f || !g || !noise) return bad_arg("tsde_step_diag", "null argument");
   const hipStream_t s = (hipStream_t)stream;
   ProfScope p(TSDE_KID_STEP_DIAG, s, true);
-  TSDE_DISPATCH(dtype, "tsde_step_diag", tsde::launch_step_diag<float>(y1, y0, f, g, n, cf, cg, noise, s),
-                tsde::launch_step_diag<double>(y1, y0, f, g, n, cf, cg, noise, s));
+  TSDE_DISPATCH(dtype, "tsde_step_diag", tsde::launch_step_diag(dtype, y1, y0, f, g, n, cf, cg, noise, s));
 }
 
 int tsde_step_prod(void* y1, const void* y0, const void* f, const void* gp, int64_t n, double cf, double cg, int dtype,
                    void* stream) {
   if (!y1 || !y0 || !f || !gp) return bad_arg("tsde_step_prod", "null argument");
   const hipStream_t s = (hipStream_t)stream;
-  TSDE_DISPATCH(dtype, "tsde_step_prod", tsde::launch_step_prod<float>(y1, y0, f, gp, n, cf, cg, s),
-                tsde::launch_step_prod<double>(y1, y0, f, gp, n, cf, cg, s));
+  TSDE_DISPATCH(dtype, "tsde_step_prod", tsde::launch_step_prod(dtype, y1, y0, f, gp, n, cf, cg, s));
 }
 
 int tsde_step_general(void* y1, const void* y0, const void* f, const void* g, int64_t B, int64_t d, int64_t m,
@@ -202,46 +205,35 @@ int tsde_step_general(void* y1, const void* y0, const void* f, const void* g, in
 int tsde_step_general_w(void* y1, const void* y0, const void* f, const void* g, int64_t B, int64_t d, int64_t m,
                         double ca, double cf, double cg, int weight_mode, double cw, double cu, double rdt,
                         const tsde_noise_t* noise, int dtype, void* stream) {
-  if (!y1 || !y0 || !f || !g || !noise) return bad_arg("tsde_step_general", "null argument");
-  if (weight_mode < 0 || weight_mode > 2) return bad_arg("tsde_step_general", "weight_mode must be 0, 1 or 2");
-  if (weight_mode != 0 && noise->dW && !noise->dU) return bad_arg("tsde_step_general", "weights need dU");
+  if (const char* bad = weighted_step_problem(y1, y0, f, g, weight_mode, noise)) return bad_arg("tsde_step_general", bad);
   const hipStream_t s = (hipStream_t)stream;
   ProfScope p(TSDE_KID_STEP_GENERAL, s, true);
   TSDE_DISPATCH(dtype, "tsde_step_general",
-                tsde::launch_step_general<float>(y1, y0, f, g, B, d, m, ca, cf, cg, weight_mode, cw, cu, rdt, noise, s),
-                tsde::launch_step_general<double>(y1, y0, f, g, B, d, m, ca, cf, cg, weight_mode, cw, cu, rdt, noise,
-                                                  s));
+                tsde::launch_step_general(dtype, y1, y0, f, g, B, d, m, ca, cf, cg, weight_mode, cw, cu, rdt, noise, s));
 }
 
 int tsde_step_shared(void* y1, const void* y0, const void* f, const void* S, int64_t B, int64_t d, int64_t m, double ca,
                      double cf, double cg, int weight_mode, double cw, double cu, double rdt, const tsde_noise_t* noise,
                      int dtype, void* stream) {
-  if (!y1 || !y0 || !f || !S || !noise) return bad_arg("tsde_step_shared", "null argument");
-  if (weight_mode < 0 || weight_mode > 2) return bad_arg("tsde_step_shared", "weight_mode must be 0, 1 or 2");
-  if (weight_mode != 0 && noise->dW && !noise->dU) return bad_arg("tsde_step_shared", "weights need dU");
+  if (const char* bad = weighted_step_problem(y1, y0, f, S, weight_mode, noise)) return bad_arg("tsde_step_shared", bad);
   const hipStream_t s = (hipStream_t)stream;
   ProfScope p(TSDE_KID_STEP_SHARED, s, true);
   TSDE_DISPATCH(dtype, "tsde_step_shared",
-                tsde::launch_step_shared<float>(y1, y0, f, S, B, d, m, ca, cf, cg, weight_mode, cw, cu, rdt, noise, s),
-                tsde::launch_step_shared<double>(y1, y0, f, S, B, d, m, ca, cf, cg, weight_mode, cw, cu, rdt, noise, s));
+                tsde::launch_step_shared(dtype, y1, y0, f, S, B, d, m, ca, cf, cg, weight_mode, cw, cu, rdt, noise, s));
 }
 
 int tsde_milstein_v(void* v_out, void* W_out, int64_t n, double dt, int ito, double scale, const tsde_noise_t* noise,
                     int dtype, void* stream) {
   if (!v_out || !noise) return bad_arg("tsde_milstein_v", "null argument");
   const hipStream_t s = (hipStream_t)stream;
-  TSDE_DISPATCH(dtype, "tsde_milstein_v",
-                tsde::launch_milstein_v<float>(v_out, W_out, nullptr, n, dt, ito, scale, noise, s),
-                tsde::launch_milstein_v<double>(v_out, W_out, nullptr, n, dt, ito, scale, noise, s));
+  TSDE_DISPATCH(dtype, "tsde_milstein_v", tsde::launch_milstein_v(dtype, v_out, W_out, nullptr, n, dt, ito, scale, noise, s));
 }
 
 int tsde_milstein_weight(void* out, const void* g, int64_t n, double dt, int ito, double scale,
                          const tsde_noise_t* noise, int dtype, void* stream) {
   if (!out || !g || !noise) return bad_arg("tsde_milstein_weight", "null argument");
   const hipStream_t s = (hipStream_t)stream;
-  TSDE_DISPATCH(dtype, "tsde_milstein_weight",
-                tsde::launch_milstein_v<float>(out, nullptr, g, n, dt, ito, scale, noise, s),
-                tsde::launch_milstein_v<double>(out, nullptr, g, n, dt, ito, scale, noise, s));
+  TSDE_DISPATCH(dtype, "tsde_milstein_weight", tsde::launch_milstein_v(dtype, out, nullptr, g, n, dt, ito, scale, noise, s));
 }
 
 int tsde_milstein_diag(void* y1, const void* y0, const void* f, const void* g, const void* gdg, int64_t n, double dt,
@@ -249,17 +241,14 @@ int tsde_milstein_diag(void* y1, const void* y0, const void* f, const void* g, c
   if (!y1 || !y0 || !f || !g || !gdg || !noise) return bad_arg("tsde_milstein_diag", "null argument");
   const hipStream_t s = (hipStream_t)stream;
   ProfScope p(TSDE_KID_MILSTEIN_DIAG, s, true);
-  TSDE_DISPATCH(dtype, "tsde_milstein_diag", tsde::launch_milstein_diag<float>(y1, y0, f, g, gdg, n, dt, noise, s),
-                tsde::launch_milstein_diag<double>(y1, y0, f, g, gdg, n, dt, noise, s));
+  TSDE_DISPATCH(dtype, "tsde_milstein_diag", tsde::launch_milstein_diag(dtype, y1, y0, f, g, gdg, n, dt, noise, s));
 }
 
 int tsde_milstein_gf_prime(void* yp, const void* y0, const void* f, const void* g, int64_t n, double dt,
                            double sqrt_dt, int ito, int dtype, void* stream) {
   if (!yp || !y0 || !f || !g) return bad_arg("tsde_milstein_gf_prime", "null argument");
   const hipStream_t s = (hipStream_t)stream;
-  TSDE_DISPATCH(dtype, "tsde_milstein_gf_prime",
-                tsde::launch_milstein_gf_prime<float>(yp, y0, f, g, n, dt, sqrt_dt, ito, s),
-                tsde::launch_milstein_gf_prime<double>(yp, y0, f, g, n, dt, sqrt_dt, ito, s));
+  TSDE_DISPATCH(dtype, "tsde_milstein_gf_prime", tsde::launch_milstein_gf_prime(dtype, yp, y0, f, g, n, dt, sqrt_dt, ito, s));
 }
 
 int tsde_milstein_gf_diag(void* y1, const void* y0, const void* f, const void* g, const void* gprime, int64_t n,
@@ -268,24 +257,20 @@ int tsde_milstein_gf_diag(void* y1, const void* y0, const void* f, const void* g
   const hipStream_t s = (hipStream_t)stream;
   ProfScope p(TSDE_KID_MILSTEIN_DIAG, s, true);
   TSDE_DISPATCH(dtype, "tsde_milstein_gf_diag",
-                tsde::launch_milstein_gf_diag<float>(y1, y0, f, g, gprime, n, dt, sqrt_dt, ito, noise, s),
-                tsde::launch_milstein_gf_diag<double>(y1, y0, f, g, gprime, n, dt, sqrt_dt, ito, noise, s));
+                tsde::launch_milstein_gf_diag(dtype, y1, y0, f, g, gprime, n, dt, sqrt_dt, ito, noise, s));
 }
 
 int tsde_srk_diag_stage(int stage, void* const out[3], const void* const in[5], int64_t n, double dt, double rdt,
                         double sqrt_dt, const tsde_noise_t* noise, int dtype, void* stream) {
   if (!out || !in || !noise) return bad_arg("tsde_srk_diag_stage", "null argument");
   if (stage < 1 || stage > 4) return bad_arg("tsde_srk_diag_stage", "stage must be 1..4");
-  static const int n_in[5] = {0, 3, 5, 4, 2}, n_out[5] = {0, 3, 3, 2, 1};
-  for (int j = 0; j < n_in[stage]; ++j)
+  for (int j = 0; j < tsde::kSrkIn[stage]; ++j)
     if (!in[j]) return bad_arg("tsde_srk_diag_stage", "missing input pointer (stage 1: 3, 2: 5, 3: 4, 4: 2 inputs)");
-  for (int j = 0; j < n_out[stage]; ++j)
+  for (int j = 0; j < tsde::kSrkOut[stage]; ++j)
     if (!out[j]) return bad_arg("tsde_srk_diag_stage", "missing output pointer (stage 1: 3, 2: 3, 3: 2, 4: 1 outputs)");
   const hipStream_t s = (hipStream_t)stream;
   ProfScope p(TSDE_KID_SRK_STAGE, s, true);
-  TSDE_DISPATCH(dtype, "tsde_srk_diag_stage",
-                tsde::launch_srk_stage<float>(stage, out, in, n, dt, rdt, sqrt_dt, noise, s),
-                tsde::launch_srk_stage<double>(stage, out, in, n, dt, rdt, sqrt_dt, noise, s));
+  TSDE_DISPATCH(dtype, "tsde_srk_diag_stage", tsde::launch_srk_stage(dtype, stage, out, in, n, dt, rdt, sqrt_dt, noise, s));
 }
 
 int tsde_milstein_gf_general_support(void* yk, const void* y0, const void* f, const void* g, int64_t B, int64_t d,
@@ -293,8 +278,7 @@ int tsde_milstein_gf_general_support(void* yk, const void* y0, const void* f, co
   if (!yk || !y0 || !f || !g) return bad_arg("tsde_milstein_gf_general_support", "null argument");
   const hipStream_t s = (hipStream_t)stream;
   TSDE_DISPATCH(dtype, "tsde_milstein_gf_general_support",
-                tsde::launch_milstein_gf_general_support<float>(yk, y0, f, g, B, d, m, dt, sqrt_dt, ito, s),
-                tsde::launch_milstein_gf_general_support<double>(yk, y0, f, g, B, d, m, dt, sqrt_dt, ito, s));
+                tsde::launch_milstein_gf_general_support(dtype, yk, y0, f, g, B, d, m, dt, sqrt_dt, ito, s));
 }
 
 int tsde_milstein_gf_general_correction(void* corr, const void* g, const void* gk, const void* I, int64_t B, int64_t d,
@@ -303,8 +287,7 @@ int tsde_milstein_gf_general_correction(void* corr, const void* g, const void* g
   const hipStream_t s = (hipStream_t)stream;
   ProfScope p(TSDE_KID_MILSTEIN_GF_GENERAL, s, true);
   TSDE_DISPATCH(dtype, "tsde_milstein_gf_general_correction",
-                tsde::launch_milstein_gf_general_correction<float>(corr, g, gk, I, B, d, m, sqrt_dt, s),
-                tsde::launch_milstein_gf_general_correction<double>(corr, g, gk, I, B, d, m, sqrt_dt, s));
+                tsde::launch_milstein_gf_general_correction(dtype, corr, g, gk, I, B, d, m, sqrt_dt, s));
 }
 
 int tsde_heun_final(void* y1, const void* y0, const void* f, const void* fp, const void* g, const void* gp, int64_t n,
@@ -314,16 +297,14 @@ int tsde_heun_final(void* y1, const void* y0, const void* f, const void* fp, con
   if (mode == 0 && !fp) return bad_arg("tsde_heun_final", "heun needs the second drift evaluation");
   if (!prod && !noise) return bad_arg("tsde_heun_final", "noise required unless prod");
   const hipStream_t s = (hipStream_t)stream;
-  TSDE_DISPATCH(dtype, "tsde_heun_final", tsde::launch_heun_final<float>(y1, y0, f, fp, g, gp, n, dt, mode, prod, noise, s),
-                tsde::launch_heun_final<double>(y1, y0, f, fp, g, gp, n, dt, mode, prod, noise, s));
+  TSDE_DISPATCH(dtype, "tsde_heun_final", tsde::launch_heun_final(dtype, y1, y0, f, fp, g, gp, n, dt, mode, prod, noise, s));
 }
 
 int tsde_iterated_integrals(void* I, const void* W, const void* A, int64_t B, int64_t m, double dt, int ito, int dtype,
                             void* stream) {
   if (!I || !W) return bad_arg("tsde_iterated_integrals", "null argument");
   const hipStream_t s = (hipStream_t)stream;
-  TSDE_DISPATCH(dtype, "tsde_iterated_integrals", tsde::launch_iterated_integrals<float>(I, W, A, B, m, dt, ito, s),
-                tsde::launch_iterated_integrals<double>(I, W, A, B, m, dt, ito, s));
+  TSDE_DISPATCH(dtype, "tsde_iterated_integrals", tsde::launch_iterated_integrals(dtype, I, W, A, B, m, dt, ito, s));
 }
 
 int tsde_levy_area(void* A, const void* W, const void* H, int64_t B, int64_t m, double h, int foster, uint64_t entropy,
@@ -332,8 +313,7 @@ int tsde_levy_area(void* A, const void* W, const void* H, int64_t B, int64_t m, 
   const hipStream_t s = (hipStream_t)stream;
   const tsde::NoiseKey key = make_key(entropy, elem0);
   TSDE_DISPATCH(dtype, "tsde_levy_area",
-                tsde::launch_levy_area<float>(A, W, H, B, m, h, foster, key, entropy_dev, cell, node, s),
-                tsde::launch_levy_area<double>(A, W, H, B, m, h, foster, key, entropy_dev, cell, node, s));
+                tsde::launch_levy_area(dtype, A, W, H, B, m, h, foster, key, entropy_dev, cell, node, s));
 }
 
 int tsde_levy_iterated_integrals(void* I, const void* W, const void* H, int64_t B, int64_t m, double h, int foster,
@@ -343,8 +323,7 @@ int tsde_levy_iterated_integrals(void* I, const void* W, const void* H, int64_t 
   const hipStream_t s = (hipStream_t)stream;
   const tsde::NoiseKey key = make_key(entropy, elem0);
   TSDE_DISPATCH(dtype, "tsde_levy_iterated_integrals",
-                tsde::launch_levy_area<float>(I, W, H, B, m, h, foster, key, entropy_dev, cell, node, s, 1, dt, ito),
-                tsde::launch_levy_area<double>(I, W, H, B, m, h, foster, key, entropy_dev, cell, node, s, 1, dt, ito));
+                tsde::launch_levy_area(dtype, I, W, H, B, m, h, foster, key, entropy_dev, cell, node, s, 1, dt, ito));
 }
 
 int tsde_rheun_z_diag(void* z1, const void* y0, const void* z0, const void* f0, const void* g0, int64_t n, double dt,
@@ -352,8 +331,7 @@ int tsde_rheun_z_diag(void* z1, const void* y0, const void* z0, const void* f0, 
   if (!z1 || !y0 || !z0 || !f0 || !g0 || !noise) return bad_arg("tsde_rheun_z_diag", "null argument");
   const hipStream_t s = (hipStream_t)stream;
   ProfScope p(TSDE_KID_RHEUN, s);
-  TSDE_DISPATCH(dtype, "tsde_rheun_z_diag", tsde::launch_rheun_z<float>(z1, y0, z0, f0, g0, n, dt, sign, noise, s),
-                tsde::launch_rheun_z<double>(z1, y0, z0, f0, g0, n, dt, sign, noise, s));
+  TSDE_DISPATCH(dtype, "tsde_rheun_z_diag", tsde::launch_rheun_z(dtype, z1, y0, z0, f0, g0, n, dt, sign, noise, s));
 }
 
 int tsde_rheun_y_diag(void* y1, const void* y0, const void* f0, const void* f1, const void* g0, const void* g1,
@@ -361,16 +339,13 @@ int tsde_rheun_y_diag(void* y1, const void* y0, const void* f0, const void* f1, 
   if (!y1 || !y0 || !f0 || !f1 || !g0 || !g1 || !noise) return bad_arg("tsde_rheun_y_diag", "null argument");
   const hipStream_t s = (hipStream_t)stream;
   ProfScope p(TSDE_KID_RHEUN, s);
-  TSDE_DISPATCH(dtype, "tsde_rheun_y_diag",
-                tsde::launch_rheun_y<float>(y1, y0, f0, f1, g0, g1, n, half_dt, sign, noise, s),
-                tsde::launch_rheun_y<double>(y1, y0, f0, f1, g0, g1, n, half_dt, sign, noise, s));
+  TSDE_DISPATCH(dtype, "tsde_rheun_y_diag", tsde::launch_rheun_y(dtype, y1, y0, f0, f1, g0, g1, n, half_dt, sign, noise, s));
 }
 
 int tsde_lincomb2(void* out, const void* x, const void* y, int64_t n, double a, double b, int dtype, void* stream) {
   if (!out || !x || !y) return bad_arg("tsde_lincomb2", "null argument");
   const hipStream_t s = (hipStream_t)stream;
-  TSDE_DISPATCH(dtype, "tsde_lincomb2", tsde::launch_lincomb2<float>(out, x, y, n, a, b, s),
-                tsde::launch_lincomb2<double>(out, x, y, n, a, b, s));
+  TSDE_DISPATCH(dtype, "tsde_lincomb2", tsde::launch_lincomb2(dtype, out, x, y, n, a, b, s));
 }
 
 int tsde_rheun_adj_a_diag(void* af0_out, void* ag0_out, const void* ay, const void* af0, const void* ag0, int64_t n,
@@ -378,8 +353,7 @@ int tsde_rheun_adj_a_diag(void* af0_out, void* ag0_out, const void* ay, const vo
   if (!af0_out || !ag0_out || !ay || !af0 || !ag0 || !noise) return bad_arg("tsde_rheun_adj_a_diag", "null argument");
   const hipStream_t s = (hipStream_t)stream;
   TSDE_DISPATCH(dtype, "tsde_rheun_adj_a_diag",
-                tsde::launch_rheun_adj_a<float>(af0_out, ag0_out, ay, af0, ag0, n, half_dt, noise, s),
-                tsde::launch_rheun_adj_a<double>(af0_out, ag0_out, ay, af0, ag0, n, half_dt, noise, s));
+                tsde::launch_rheun_adj_a(dtype, af0_out, ag0_out, ay, af0, ag0, n, half_dt, noise, s));
 }
 
 int tsde_rheun_adj_b_diag(void* ay1, void* az1, void* af1, void* ag1, const void* ay, const void* az0,
@@ -389,28 +363,25 @@ int tsde_rheun_adj_b_diag(void* ay1, void* az1, void* af1, void* ag1, const void
     return bad_arg("tsde_rheun_adj_b_diag", "null argument");
   const hipStream_t s = (hipStream_t)stream;
   TSDE_DISPATCH(dtype, "tsde_rheun_adj_b_diag",
-                tsde::launch_rheun_adj_b<float>(ay1, az1, af1, ag1, ay, az0, vjp_z, n, dt, half_dt, noise, s),
-                tsde::launch_rheun_adj_b<double>(ay1, az1, af1, ag1, ay, az0, vjp_z, n, dt, half_dt, noise, s));
+                tsde::launch_rheun_adj_b(dtype, ay1, az1, af1, ag1, ay, az0, vjp_z, n, dt, half_dt, noise, s));
 }
 
 int tsde_aug_update(const tsde_seg_t* segs, int nseg, double cF, double cG, int dtype, void* stream) {
   if (!segs || nseg < 0) return bad_arg("tsde_aug_update", "bad segment list");
-  if (dtype != TSDE_F32 && dtype != TSDE_F64) return bad_arg("tsde_aug_update", "dtype");
+  if (dtype != TSDE_F32 && dtype != TSDE_F64) return bad_arg("tsde_aug_update", "dtype");   // (its own message)
   const hipStream_t s = (hipStream_t)stream;
   for (int i = 0; i < nseg; ++i) {
     if (segs[i].n > 0 && (!segs[i].out || !segs[i].s)) return bad_arg("tsde_aug_update", "segment without state");
   }
   ProfScope p(TSDE_KID_AUG_UPDATE, s, true);
-  if (dtype == TSDE_F32) return fail(tsde::launch_aug_segments<float>(segs, nseg, cF, cG, s), "tsde_aug_update");
-  return fail(tsde::launch_aug_segments<double>(segs, nseg, cF, cG, s), "tsde_aug_update");
+  return fail(tsde::launch_aug_segments(dtype, segs, nseg, cF, cG, s), "tsde_aug_update");
 }
 
 int tsde_linear_interp(void* out, const void* ya, const void* yb, int64_t n, double w0, double w1, int dtype,
                        void* stream) {
   if (!out || !ya || !yb) return bad_arg("tsde_linear_interp", "null argument");
   const hipStream_t s = (hipStream_t)stream;
-  TSDE_DISPATCH(dtype, "tsde_linear_interp", tsde::launch_interp<float>(out, ya, yb, n, w0, w1, s),
-                tsde::launch_interp<double>(out, ya, yb, n, w0, w1, s));
+  TSDE_DISPATCH(dtype, "tsde_linear_interp", tsde::launch_interp(dtype, out, ya, yb, n, w0, w1, s));
 }
 
 int tsde_error_norm(double* out, double* workspace, const void* y_full, const void* y_half, int64_t n, double rtol,
@@ -419,8 +390,7 @@ int tsde_error_norm(double* out, double* workspace, const void* y_full, const vo
   if (n <= 0) return bad_arg("tsde_error_norm", "n must be positive");
   const hipStream_t s = (hipStream_t)stream;
   TSDE_DISPATCH(dtype, "tsde_error_norm",
-                tsde::launch_error_norm<float>(out, workspace, y_full, y_half, n, rtol, atol, eps, s),
-                tsde::launch_error_norm<double>(out, workspace, y_full, y_half, n, rtol, atol, eps, s));
+                tsde::launch_error_norm(dtype, out, workspace, y_full, y_half, n, rtol, atol, eps, s));
 }
 
 int tsde_adaptive_begin(double* ctl, void* scal, double out_t, const double* stage_fracs, int n_fracs, int dtype,
@@ -429,8 +399,7 @@ int tsde_adaptive_begin(double* ctl, void* scal, double out_t, const double* sta
   if (n_fracs < 1 || n_fracs > TSDE_ADAPTIVE_MAX_STAGES - 1) return bad_arg("tsde_adaptive_begin", "bad number of stages");
   const hipStream_t s = (hipStream_t)stream;
   TSDE_DISPATCH(dtype, "tsde_adaptive_begin",
-                tsde::launch_adaptive_begin<float>(ctl, scal, out_t, nullptr, 0, stage_fracs, n_fracs, s),
-                tsde::launch_adaptive_begin<double>(ctl, scal, out_t, nullptr, 0, stage_fracs, n_fracs, s));
+                tsde::launch_adaptive_begin(dtype, ctl, scal, out_t, nullptr, 0, stage_fracs, n_fracs, s));
 }
 
 int tsde_adaptive_begin_outputs(double* ctl, void* scal, const double* out_times, int32_t n_out, const double* stage_fracs,
@@ -440,9 +409,7 @@ int tsde_adaptive_begin_outputs(double* ctl, void* scal, const double* out_times
   if (n_out < 1) return bad_arg(where, "need at least one output time");
   if (n_fracs < 1 || n_fracs > TSDE_ADAPTIVE_MAX_STAGES - 1) return bad_arg(where, "bad number of stages");
   const hipStream_t s = (hipStream_t)stream;
-  TSDE_DISPATCH(dtype, where,
-                tsde::launch_adaptive_begin<float>(ctl, scal, 0.0, out_times, n_out, stage_fracs, n_fracs, s),
-                tsde::launch_adaptive_begin<double>(ctl, scal, 0.0, out_times, n_out, stage_fracs, n_fracs, s));
+  TSDE_DISPATCH(dtype, where, tsde::launch_adaptive_begin(dtype, ctl, scal, 0.0, out_times, n_out, stage_fracs, n_fracs, s));
 }
 
 int tsde_adaptive_control_outputs(double* ctl, void* scal, const double* error, const double* out_times,
@@ -453,10 +420,8 @@ int tsde_adaptive_control_outputs(double* ctl, void* scal, const double* error, 
   if (n_fracs < 1 || n_fracs > TSDE_ADAPTIVE_MAX_STAGES - 1) return bad_arg(where, "bad number of stages");
   const hipStream_t s = (hipStream_t)stream;
   TSDE_DISPATCH(dtype, where,
-                tsde::launch_adaptive_control<float>(ctl, scal, error, out_times, accept_log, log_capacity, stage_fracs,
-                                                     n_fracs, s),
-                tsde::launch_adaptive_control<double>(ctl, scal, error, out_times, accept_log, log_capacity, stage_fracs,
-                                                      n_fracs, s));
+                tsde::launch_adaptive_control(dtype, ctl, scal, error, out_times, accept_log, log_capacity, stage_fracs,
+                                              n_fracs, s));
 }
 
 int tsde_adaptive_emit(const void* ys_slot, const void* prev_y, const void* curr_y, int64_t n, const double* ctl,
@@ -465,8 +430,7 @@ int tsde_adaptive_emit(const void* ys_slot, const void* prev_y, const void* curr
   if (!ys_slot || !prev_y || !curr_y || !ctl || !out_times) return bad_arg(where, "null argument");
   if (n <= 0) return bad_arg(where, "n must be positive");
   const hipStream_t s = (hipStream_t)stream;
-  TSDE_DISPATCH(dtype, where, tsde::launch_adaptive_emit<float>(ys_slot, prev_y, curr_y, n, ctl, out_times, s),
-                tsde::launch_adaptive_emit<double>(ys_slot, prev_y, curr_y, n, ctl, out_times, s));
+  TSDE_DISPATCH(dtype, where, tsde::launch_adaptive_emit(dtype, ys_slot, prev_y, curr_y, n, ctl, out_times, s));
 }
 
 int tsde_adaptive_control(double* ctl, void* scal, const double* error, const double* stage_fracs, int n_fracs,
@@ -475,16 +439,14 @@ int tsde_adaptive_control(double* ctl, void* scal, const double* error, const do
   if (n_fracs < 1 || n_fracs > TSDE_ADAPTIVE_MAX_STAGES - 1) return bad_arg("tsde_adaptive_control", "bad number of stages");
   const hipStream_t s = (hipStream_t)stream;
   TSDE_DISPATCH(dtype, "tsde_adaptive_control",
-                tsde::launch_adaptive_control<float>(ctl, scal, error, nullptr, nullptr, 0, stage_fracs, n_fracs, s),
-                tsde::launch_adaptive_control<double>(ctl, scal, error, nullptr, nullptr, 0, stage_fracs, n_fracs, s));
+                tsde::launch_adaptive_control(dtype, ctl, scal, error, nullptr, nullptr, 0, stage_fracs, n_fracs, s));
 }
 
 int tsde_adaptive_commit(void* prev_y, void* curr_y, const void* y_next, int64_t n, const void* scal, int dtype,
                          void* stream) {
   if (!prev_y || !curr_y || !y_next || !scal) return bad_arg("tsde_adaptive_commit", "null argument");
   const hipStream_t s = (hipStream_t)stream;
-  TSDE_DISPATCH(dtype, "tsde_adaptive_commit", tsde::launch_adaptive_commit<float>(prev_y, curr_y, y_next, n, scal, s),
-                tsde::launch_adaptive_commit<double>(prev_y, curr_y, y_next, n, scal, s));
+  TSDE_DISPATCH(dtype, "tsde_adaptive_commit", tsde::launch_adaptive_commit(dtype, prev_y, curr_y, y_next, n, scal, s));
 }
 
 int tsde_merge_halves(void* W, void* U, const void* Wa, const void* Ha, const void* Wb, const void* Hb, int64_t n,
@@ -493,8 +455,7 @@ int tsde_merge_halves(void* W, void* U, const void* Wa, const void* Ha, const vo
   if (!ctl && !(ha + hb > 0.0)) return bad_arg("tsde_merge_halves", "need ctl or positive widths");
   if (U && (!Ha || !Hb)) return bad_arg("tsde_merge_halves", "U needs the space-time Levy areas of both halves");
   const hipStream_t s = (hipStream_t)stream;
-  TSDE_DISPATCH(dtype, "tsde_merge_halves", tsde::launch_merge_halves<float>(W, U, Wa, Ha, Wb, Hb, n, ctl, ha, hb, s),
-                tsde::launch_merge_halves<double>(W, U, Wa, Ha, Wb, Hb, n, ctl, ha, hb, s));
+  TSDE_DISPATCH(dtype, "tsde_merge_halves", tsde::launch_merge_halves(dtype, W, U, Wa, Ha, Wb, Hb, n, ctl, ha, hb, s));
 }
 
 static int trajectory_affine_diag(const char* where, void* ys, void* sens, const void* y0, int64_t rows, int64_t d,
@@ -516,11 +477,8 @@ static int trajectory_affine_diag(const char* where, void* ys, void* sens, const
   const tsde::NoiseKey key = make_key(entropy, elem0);
   ProfScope p(TSDE_KID_TRAJECTORY, s);
   TSDE_DISPATCH(dtype, where,
-                tsde::launch_trajectory_affine_diag<float>(ys, sens, y0, rows, d, drift_rate, drift_shift, diff_rate,
-                                                           diff_shift, coef_step_stride, method, traj, key, entropy_dev, s),
-                tsde::launch_trajectory_affine_diag<double>(ys, sens, y0, rows, d, drift_rate, drift_shift, diff_rate,
-                                                            diff_shift, coef_step_stride, method, traj, key, entropy_dev,
-                                                            s));
+                tsde::launch_trajectory_affine_diag(dtype, ys, sens, y0, rows, d, drift_rate, drift_shift, diff_rate,
+                                                    diff_shift, coef_step_stride, method, traj, key, entropy_dev, s));
 }
 
 int tsde_trajectory_affine_diag(void* ys, const void* y0, int64_t rows, int64_t d, const void* drift_rate,
@@ -657,10 +615,8 @@ static int prog_diag(const char* where, void* ys, void* sens, const int8_t* para
   const tsde::NoiseKey key = make_key(entropy, elem0);
   ProfScope p(TSDE_KID_TRAJECTORY, s);
   TSDE_DISPATCH(dtype, where,
-                tsde::launch_trajectory_prog_diag<float>(ys, sens, param_slot, y0, rows, d, code, f_len, g_len, dg_len, consts,
-                                                         n_const, scalar_noise != 0, method, traj, key, entropy_dev, s),
-                tsde::launch_trajectory_prog_diag<double>(ys, sens, param_slot, y0, rows, d, code, f_len, g_len, dg_len, consts,
-                                                          n_const, scalar_noise != 0, method, traj, key, entropy_dev, s));
+                tsde::launch_trajectory_prog_diag(dtype, ys, sens, param_slot, y0, rows, d, code, f_len, g_len, dg_len, consts,
+                                                  n_const, scalar_noise != 0, method, traj, key, entropy_dev, s));
 }
 
 int tsde_trajectory_prog_diag(void* ys, const void* y0, int64_t rows, int64_t d, const uint32_t* code, int32_t f_len,
@@ -728,10 +684,8 @@ int tsde_trajectory_prog_additive(void* ys, const void* y0, int64_t rows, int64_
   const tsde::NoiseKey key = make_key(entropy, elem0);
   ProfScope p(TSDE_KID_TRAJECTORY, s);
   TSDE_DISPATCH(dtype, where,
-                tsde::launch_trajectory_prog_additive<float>(ys, y0, rows, d, m, code, f_len, consts, n_const, g_table,
-                                                             g_time_dependent != 0, method, traj, key, entropy_dev, s),
-                tsde::launch_trajectory_prog_additive<double>(ys, y0, rows, d, m, code, f_len, consts, n_const, g_table,
-                                                              g_time_dependent != 0, method, traj, key, entropy_dev, s));
+                tsde::launch_trajectory_prog_additive(dtype, ys, y0, rows, d, m, code, f_len, consts, n_const, g_table,
+                                                      g_time_dependent != 0, method, traj, key, entropy_dev, s));
 }
 
 int64_t tsde_trajectory_mlp_general_lds(int64_t d, int64_t m, int64_t drift_hidden, int64_t diffusion_hidden,
@@ -818,10 +772,8 @@ int tsde_trajectory_expr_diag_timed(void* ys, const void* y0, int64_t rows, int6
   const tsde::NoiseKey key = make_key(entropy, elem0);
   ProfScope p(TSDE_KID_TRAJECTORY, s);
   TSDE_DISPATCH(dtype, where,
-                tsde::launch_trajectory_expr_diag<float>(ys, y0, rows, d, coef, coef_step_stride, f_kind, g_kind, method,
-                                                         traj, key, entropy_dev, s),
-                tsde::launch_trajectory_expr_diag<double>(ys, y0, rows, d, coef, coef_step_stride, f_kind, g_kind, method,
-                                                          traj, key, entropy_dev, s));
+                tsde::launch_trajectory_expr_diag(dtype, ys, y0, rows, d, coef, coef_step_stride, f_kind, g_kind, method, traj,
+                                                  key, entropy_dev, s));
 }
 
 int tsde_adjoint_mlp_diag(void* y, void* a, void* stash_a, void* stash_hid, void* stash_delta, void* stash_y,

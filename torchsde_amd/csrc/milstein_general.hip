@@ -119,49 +119,44 @@ __global__ void __launch_bounds__(kBlock) gf_correction_generic_kernel(const GfG
   }
 }
 
-template <typename T>
-hipError_t launch_milstein_gf_general_support(void* yk, const void* y0, const void* f, const void* g, int64_t B,
+hipError_t launch_milstein_gf_general_support(int dtype, void* yk, const void* y0, const void* f, const void* g, int64_t B,
                                               int64_t d, int64_t m, double dt, double sqrt_dt, int ito, hipStream_t s) {
-  if (B <= 0 || d <= 0 || m <= 0) return hipSuccess;
-  GfGeneralArgs<T> a{(T*)yk, (const T*)y0, (const T*)f, (const T*)g, nullptr, nullptr, B, d, m, coef<T>(dt),
-                     coef<T>(sqrt_dt), ito};
-  const int grid = grid_for(B * d);
-  if (m % 4 == 0 && aligned16(g))
-    hipLaunchKernelGGL((gf_support_kernel<T, true>), dim3(grid), dim3(kBlock), 0, s, a);
-  else
-    hipLaunchKernelGGL((gf_support_kernel<T, false>), dim3(grid), dim3(kBlock), 0, s, a);
-  return hipGetLastError();
-}
-
-template <typename T>
-hipError_t launch_milstein_gf_general_correction(void* corr, const void* g, const void* gk, const void* I, int64_t B,
-                                                 int64_t d, int64_t m, double sqrt_dt, hipStream_t s) {
-  if (B <= 0 || d <= 0 || m <= 0) return hipSuccess;
-  GfGeneralArgs<T> a{(T*)corr, nullptr, nullptr, (const T*)g, (const T*)gk, (const T*)I, B, d, m, coef<T>(0.0),
-                     coef<T>(sqrt_dt), 0};
-  const int64_t G = m / 4;
-  const bool pow2 = (m % 4 == 0) && G >= 1 && G <= 64 && ((G & (G - 1)) == 0);
-  const bool fast = pow2 && aligned16(g) && aligned16(gk) && aligned16(I) && (d * G) % 64 == 0;
-  const int64_t nc = fast ? (d * G) / 64 : 0;
-  if (fast && (nc == 1 || nc == 2 || nc == 4)) {
-    int64_t blocks = (B + (kBlock / 64) - 1) / (kBlock / 64);   // one wave per row; B/4 blocks, uncapped below 2^20
-    if (blocks > (1 << 20)) blocks = 1 << 20;
-    if (nc == 1) TSDE_LAUNCH((gf_correction_rows_kernel<T, 1>), dim3((unsigned)blocks), dim3(kBlock), 0, s, a);
-    else if (nc == 2) TSDE_LAUNCH((gf_correction_rows_kernel<T, 2>), dim3((unsigned)blocks), dim3(kBlock), 0, s, a);
-    else TSDE_LAUNCH((gf_correction_rows_kernel<T, 4>), dim3((unsigned)blocks), dim3(kBlock), 0, s, a);
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    if (B <= 0 || d <= 0 || m <= 0) return hipSuccess;
+    GfGeneralArgs<T> a{(T*)yk, (const T*)y0, (const T*)f, (const T*)g, nullptr, nullptr, B, d, m, coef<T>(dt),
+                       coef<T>(sqrt_dt), ito};
+    const int grid = grid_for(B * d);
+    if (m % 4 == 0 && aligned16(g))
+      hipLaunchKernelGGL((gf_support_kernel<T, true>), dim3(grid), dim3(kBlock), 0, s, a);
+    else
+      hipLaunchKernelGGL((gf_support_kernel<T, false>), dim3(grid), dim3(kBlock), 0, s, a);
     return hipGetLastError();
-  }
-  TSDE_LAUNCH(gf_correction_generic_kernel<T>, dim3(grid_for(B * d)), dim3(kBlock), 0, s, a);
-  return hipGetLastError();
+  });
 }
 
-template hipError_t launch_milstein_gf_general_support<float>(void*, const void*, const void*, const void*, int64_t,
-                                                              int64_t, int64_t, double, double, int, hipStream_t);
-template hipError_t launch_milstein_gf_general_support<double>(void*, const void*, const void*, const void*, int64_t,
-                                                               int64_t, int64_t, double, double, int, hipStream_t);
-template hipError_t launch_milstein_gf_general_correction<float>(void*, const void*, const void*, const void*, int64_t,
-                                                                 int64_t, int64_t, double, hipStream_t);
-template hipError_t launch_milstein_gf_general_correction<double>(void*, const void*, const void*, const void*, int64_t,
-                                                                  int64_t, int64_t, double, hipStream_t);
+hipError_t launch_milstein_gf_general_correction(int dtype, void* corr, const void* g, const void* gk, const void* I, int64_t B,
+                                                 int64_t d, int64_t m, double sqrt_dt, hipStream_t s) {
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    if (B <= 0 || d <= 0 || m <= 0) return hipSuccess;
+    GfGeneralArgs<T> a{(T*)corr, nullptr, nullptr, (const T*)g, (const T*)gk, (const T*)I, B, d, m, coef<T>(0.0),
+                       coef<T>(sqrt_dt), 0};
+    const int64_t G = m / 4;
+    const bool pow2 = (m % 4 == 0) && G >= 1 && G <= 64 && ((G & (G - 1)) == 0);
+    const bool fast = pow2 && aligned16(g) && aligned16(gk) && aligned16(I) && (d * G) % 64 == 0;
+    const int64_t nc = fast ? (d * G) / 64 : 0;
+    if (fast && (nc == 1 || nc == 2 || nc == 4)) {
+      int64_t blocks = (B + (kBlock / 64) - 1) / (kBlock / 64);   // one wave per row; B/4 blocks, uncapped below 2^20
+      if (blocks > (1 << 20)) blocks = 1 << 20;
+      if (nc == 1) TSDE_LAUNCH((gf_correction_rows_kernel<T, 1>), dim3((unsigned)blocks), dim3(kBlock), 0, s, a);
+      else if (nc == 2) TSDE_LAUNCH((gf_correction_rows_kernel<T, 2>), dim3((unsigned)blocks), dim3(kBlock), 0, s, a);
+      else TSDE_LAUNCH((gf_correction_rows_kernel<T, 4>), dim3((unsigned)blocks), dim3(kBlock), 0, s, a);
+      return hipGetLastError();
+    }
+    TSDE_LAUNCH(gf_correction_generic_kernel<T>, dim3(grid_for(B * d)), dim3(kBlock), 0, s, a);
+    return hipGetLastError();
+  });
+}
 
 }  // namespace tsde

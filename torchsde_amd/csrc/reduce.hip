@@ -77,25 +77,22 @@ __global__ void __launch_bounds__(kBlock) error_final_kernel(double* __restrict_
   }
 }
 
-template <typename T>
-hipError_t launch_error_norm(double* out, double* workspace, const void* yf, const void* yh, int64_t n, double rtol,
+hipError_t launch_error_norm(int dtype, double* out, double* workspace, const void* yf, const void* yh, int64_t n, double rtol,
                              double atol, double eps, hipStream_t s) {
-  const bool vec = (n % 4 == 0) && aligned16(yf) && aligned16(yh);
+  const bool vec = vec_ok(n, yf, yh);
   int64_t blocks = ((vec ? n >> 2 : n) + kBlock - 1) / kBlock;
   if (blocks < 1) blocks = 1;
   if (blocks > kMaxPartials) blocks = kMaxPartials;
-  hipLaunchKernelGGL(error_partials_kernel<T>, dim3((unsigned)blocks), dim3(kBlock), 0, s, workspace, (const T*)yf,
-                     (const T*)yh, n, (T)rtol, (T)atol, (T)eps, vec ? 1 : 0);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(error_final_kernel, dim3(1), dim3(kBlock), 0, s, out, (const double*)workspace, (int)blocks,
-                     (double)n, (double)(T)eps);
-  return hipGetLastError();
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(error_partials_kernel<T>, dim3((unsigned)blocks), dim3(kBlock), 0, s, workspace, (const T*)yf,
+                       (const T*)yh, n, (T)rtol, (T)atol, (T)eps, vec ? 1 : 0);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(error_final_kernel, dim3(1), dim3(kBlock), 0, s, out, (const double*)workspace, (int)blocks,
+                       (double)n, (double)(T)eps);
+    return hipGetLastError();
+  });
 }
-
-template hipError_t launch_error_norm<float>(double*, double*, const void*, const void*, int64_t, double, double,
-                                             double, hipStream_t);
-template hipError_t launch_error_norm<double>(double*, double*, const void*, const void*, int64_t, double, double,
-                                              double, hipStream_t);
 
 }  // namespace tsde

@@ -7,27 +7,6 @@
 
 namespace tsde {
 
-template <typename T>
-static CellNoise<T> rh_noise(const tsde_noise_t* nz) {
-  CellNoise<T> c;
-  c.dW = (const T*)nz->dW;
-  c.dU = (const T*)nz->dU;
-  c.key.k0 = (uint32_t)nz->entropy;
-  c.key.k1 = (uint32_t)(nz->entropy >> 32);
-  c.key.elem0 = nz->elem0;
-  c.cell = nz->cell;
-  set_width<T>(c, nz->h);
-  c.bcast_d = nz->bcast_d;
-  c.key_dev = nz->entropy_dev;
-  return c;
-}
-
-static bool rh_noise_vec(const tsde_noise_t* nz) {
-  if (nz->dW == nullptr) return (nz->elem0 % 4) == 0;
-  if (nz->bcast_d > 0) return (nz->bcast_d % 4) == 0;
-  return aligned16(nz->dW);
-}
-
 // z1 = ((2*y0 - z0) + s*(f0*dt)) + s*(g0*dW)      reversible_heun.py:69 (s=+1), :109 (s=-1)
 template <typename T>
 struct RheunZOp {
@@ -167,20 +146,21 @@ struct HeunFinalOp {
   }
 };
 
-template <typename T>
-hipError_t launch_heun_final(void* y1, const void* y0, const void* f, const void* fp, const void* g, const void* gp,
+hipError_t launch_heun_final(int dtype, void* y1, const void* y0, const void* f, const void* fp, const void* g, const void* gp,
                              int64_t n, double dt, int mode, int prod, const tsde_noise_t* nz, hipStream_t s) {
-  bool vec = (n % 4 == 0) && aligned16(y1) && aligned16(y0) && aligned16(f) && (!fp || aligned16(fp)) && aligned16(g) &&
-             aligned16(gp);
-  if (prod) {
-    HeunFinalOp<T, true> op{(T*)y1, (const T*)y0, (const T*)f, (const T*)fp, (const T*)g, (const T*)gp, coef<T>(dt), mode,
-                            CellNoise<T>{}};
+  // with `prod` there is no noise to read, and `nz` may be null
+  const bool vec = vec_ok(n, y1, y0, f, fp, g, gp) && (prod || noise_vec_ok(nz, false));
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    if (prod) {
+      HeunFinalOp<T, true> op{(T*)y1, (const T*)y0, (const T*)f, (const T*)fp, (const T*)g, (const T*)gp, coef<T>(dt), mode,
+                              CellNoise<T>{}};
+      return launch_elementwise(op, n, vec, s, sizeof(T));
+    }
+    HeunFinalOp<T, false> op{(T*)y1, (const T*)y0, (const T*)f, (const T*)fp, (const T*)g, (const T*)gp, coef<T>(dt), mode,
+                             cell_noise_of<T>(nz)};
     return launch_elementwise(op, n, vec, s, sizeof(T));
-  }
-  HeunFinalOp<T, false> op{(T*)y1, (const T*)y0, (const T*)f, (const T*)fp, (const T*)g, (const T*)gp, coef<T>(dt), mode,
-                           rh_noise<T>(nz)};
-  vec = vec && rh_noise_vec(nz);
-  return launch_elementwise(op, n, vec, s, sizeof(T));
+  });
 }
 
 // ---- Davie / Foster approximation of the Levy area of one interval (brownian_interval.py:78-99) ------------------
@@ -302,103 +282,93 @@ __global__ void __launch_bounds__(kBlock) iterated_integrals_kernel(T* __restric
   }
 }
 
-template <typename T>
-hipError_t launch_iterated_integrals(void* I, const void* W, const void* A, int64_t B, int64_t m, double dt, int ito,
+hipError_t launch_iterated_integrals(int dtype, void* I, const void* W, const void* A, int64_t B, int64_t m, double dt, int ito,
                                      hipStream_t s) {
   const int64_t total = B * m * m;
-  if (total <= 0) return hipSuccess;
-  hipLaunchKernelGGL(iterated_integrals_kernel<T>, dim3(grid_for(total)), dim3(kBlock), 0, s, (T*)I, (const T*)W,
-                     (const T*)A, B, m, (T)dt, ito);
-  return hipGetLastError();
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    if (total <= 0) return hipSuccess;
+    hipLaunchKernelGGL(iterated_integrals_kernel<T>, dim3(grid_for(total)), dim3(kBlock), 0, s, (T*)I, (const T*)W,
+                       (const T*)A, B, m, (T)dt, ito);
+    return hipGetLastError();
+  });
 }
 
 // `fuse`: write I = 0.5*(W W^T - [diag] dt) + A instead of A (tsde_levy_iterated_integrals). Returns
 // hipErrorNotSupported when the fused form is asked for a shape only the per-entry kernel serves.
-template <typename T>
-hipError_t launch_levy_area(void* A, const void* W, const void* H, int64_t B, int64_t m, double h, int foster,
-                            NoiseKey key, const uint64_t* key_dev, uint32_t cell, uint64_t node, hipStream_t s,
-                            int fuse, double dt, int ito) {
+hipError_t launch_levy_area(int dtype, void* A, const void* W, const void* H, int64_t B, int64_t m, double h, int foster,
+                            NoiseKey key, const uint64_t* key_dev, uint32_t cell, uint64_t node, hipStream_t s, int fuse,
+                            double dt, int ito) {
   const int64_t total = B * m * m;
-  if (total <= 0) return hipSuccess;
-  static const bool rows_off = [] { const char* e = getenv("TSDE_LEVY_ROWS"); return e && e[0] == '0'; }();
-  const size_t lds = (size_t)kLevyRowsPerBlock * (size_t)(m * m + 2 * m) * sizeof(T);
-  const bool rows_ok = !rows_off && (m % 2 == 0) && lds <= (48u << 10) && ((key.elem0 * (uint64_t)m) % 4 == 0);
-  if (rows_ok) {
-    int64_t blocks = (B + kLevyRowsPerBlock - 1) / kLevyRowsPerBlock;
-    if (blocks > kMaxGrid * 4) blocks = kMaxGrid * 4;
-    hipLaunchKernelGGL(levy_area_rows_kernel<T>, dim3((unsigned)blocks), dim3(kBlock), lds, s, (T*)A, (const T*)W,
-                       (const T*)H, B, (int)m, h, foster, key, key_dev, cell, node, fuse, (T)dt, ito);
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    if (total <= 0) return hipSuccess;
+    static const bool rows_off = [] { const char* e = getenv("TSDE_LEVY_ROWS"); return e && e[0] == '0'; }();
+    const size_t lds = (size_t)kLevyRowsPerBlock * (size_t)(m * m + 2 * m) * sizeof(T);
+    const bool rows_ok = !rows_off && (m % 2 == 0) && lds <= (48u << 10) && ((key.elem0 * (uint64_t)m) % 4 == 0);
+    if (rows_ok) {
+      int64_t blocks = (B + kLevyRowsPerBlock - 1) / kLevyRowsPerBlock;
+      if (blocks > kMaxGrid * 4) blocks = kMaxGrid * 4;
+      hipLaunchKernelGGL(levy_area_rows_kernel<T>, dim3((unsigned)blocks), dim3(kBlock), lds, s, (T*)A, (const T*)W,
+                         (const T*)H, B, (int)m, h, foster, key, key_dev, cell, node, fuse, (T)dt, ito);
+      return hipGetLastError();
+    }
+    if (fuse) return hipErrorNotSupported;
+    hipLaunchKernelGGL(levy_area_kernel<T>, dim3(grid_for(total)), dim3(kBlock), 0, s, (T*)A, (const T*)W, (const T*)H, B,
+                       m, h, foster, key, key_dev, cell, node);
     return hipGetLastError();
-  }
-  if (fuse) return hipErrorNotSupported;
-  hipLaunchKernelGGL(levy_area_kernel<T>, dim3(grid_for(total)), dim3(kBlock), 0, s, (T*)A, (const T*)W, (const T*)H, B,
-                     m, h, foster, key, key_dev, cell, node);
-  return hipGetLastError();
+  });
 }
 
-template <typename T>
-hipError_t launch_rheun_z(void* z1, const void* y0, const void* z0, const void* f0, const void* g0, int64_t n, double dt,
-                          double sgn, const tsde_noise_t* nz, hipStream_t s) {
-  RheunZOp<T> op{(T*)z1, (const T*)y0, (const T*)z0, (const T*)f0, (const T*)g0, (T)dt, (T)sgn, rh_noise<T>(nz)};
-  const bool vec = (n % 4 == 0) && aligned16(z1) && aligned16(y0) && aligned16(z0) && aligned16(f0) && aligned16(g0) &&
-                   rh_noise_vec(nz);
-  return launch_elementwise(op, n, vec, s, sizeof(T));
+hipError_t launch_rheun_z(int dtype, void* z1, const void* y0, const void* z0, const void* f0, const void* g0, int64_t n,
+                          double dt, double sgn, const tsde_noise_t* nz, hipStream_t s) {
+  const bool vec = vec_ok(n, z1, y0, z0, f0, g0) && noise_vec_ok(nz, false);
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    RheunZOp<T> op{(T*)z1, (const T*)y0, (const T*)z0, (const T*)f0, (const T*)g0, (T)dt, (T)sgn, cell_noise_of<T>(nz)};
+    return launch_elementwise(op, n, vec, s, sizeof(T));
+  });
 }
 
-template <typename T>
-hipError_t launch_rheun_y(void* y1, const void* y0, const void* f0, const void* f1, const void* g0, const void* g1,
+hipError_t launch_rheun_y(int dtype, void* y1, const void* y0, const void* f0, const void* f1, const void* g0, const void* g1,
                           int64_t n, double half_dt, double sgn, const tsde_noise_t* nz, hipStream_t s) {
-  RheunYOp<T> op{(T*)y1,      (const T*)y0, (const T*)f0, (const T*)f1,   (const T*)g0,
-                 (const T*)g1, (T)half_dt,   (T)sgn,       rh_noise<T>(nz)};
-  const bool vec = (n % 4 == 0) && aligned16(y1) && aligned16(y0) && aligned16(f0) && aligned16(f1) && aligned16(g0) &&
-                   aligned16(g1) && rh_noise_vec(nz);
-  return launch_elementwise(op, n, vec, s, sizeof(T));
+  const bool vec = vec_ok(n, y1, y0, f0, f1, g0, g1) && noise_vec_ok(nz, false);
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    RheunYOp<T> op{(T*)y1,       (const T*)y0, (const T*)f0, (const T*)f1, (const T*)g0,
+                   (const T*)g1, (T)half_dt,   (T)sgn,       cell_noise_of<T>(nz)};
+    return launch_elementwise(op, n, vec, s, sizeof(T));
+  });
 }
 
-template <typename T>
-hipError_t launch_lincomb2(void* out, const void* x, const void* y, int64_t n, double a, double b, hipStream_t s) {
-  Lincomb2Op<T> op{(T*)out, (const T*)x, (const T*)y, (T)a, (T)b};
-  const bool vec = (n % 4 == 0) && aligned16(out) && aligned16(x) && aligned16(y);
-  return launch_elementwise(op, n, vec, s, sizeof(T));
+hipError_t launch_lincomb2(int dtype, void* out, const void* x, const void* y, int64_t n, double a, double b, hipStream_t s) {
+  const bool vec = vec_ok(n, out, x, y);
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    Lincomb2Op<T> op{(T*)out, (const T*)x, (const T*)y, (T)a, (T)b};
+    return launch_elementwise(op, n, vec, s, sizeof(T));
+  });
 }
 
-template <typename T>
-hipError_t launch_rheun_adj_a(void* af0_out, void* ag0_out, const void* ay, const void* af0, const void* ag0, int64_t n,
-                              double half_dt, const tsde_noise_t* nz, hipStream_t s) {
-  RheunAdjAOp<T> op{(T*)af0_out, (T*)ag0_out, (const T*)ay, (const T*)af0, (const T*)ag0, (T)half_dt, rh_noise<T>(nz)};
-  const bool vec = (n % 4 == 0) && aligned16(af0_out) && aligned16(ag0_out) && aligned16(ay) && aligned16(af0) &&
-                   aligned16(ag0) && rh_noise_vec(nz);
-  return launch_elementwise(op, n, vec, s, sizeof(T));
+hipError_t launch_rheun_adj_a(int dtype, void* af0_out, void* ag0_out, const void* ay, const void* af0, const void* ag0,
+                              int64_t n, double half_dt, const tsde_noise_t* nz, hipStream_t s) {
+  const bool vec = vec_ok(n, af0_out, ag0_out, ay, af0, ag0) && noise_vec_ok(nz, false);
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    RheunAdjAOp<T> op{(T*)af0_out, (T*)ag0_out, (const T*)ay, (const T*)af0, (const T*)ag0, (T)half_dt, cell_noise_of<T>(nz)};
+    return launch_elementwise(op, n, vec, s, sizeof(T));
+  });
 }
 
-template <typename T>
-hipError_t launch_rheun_adj_b(void* ay1, void* az1, void* af1, void* ag1, const void* ay, const void* az0,
-                              const void* vjp_z, int64_t n, double dt, double half_dt, const tsde_noise_t* nz,
-                              hipStream_t s) {
-  RheunAdjBOp<T> op{(T*)ay1, (T*)az1, (T*)af1, (T*)ag1, (const T*)ay, (const T*)az0, (const T*)vjp_z,
-                    (T)dt,   (T)half_dt, rh_noise<T>(nz)};
-  const bool vec = (n % 4 == 0) && aligned16(ay1) && aligned16(az1) && aligned16(af1) && aligned16(ag1) &&
-                   aligned16(ay) && aligned16(az0) && aligned16(vjp_z) && rh_noise_vec(nz);
-  return launch_elementwise(op, n, vec, s, sizeof(T));
+hipError_t launch_rheun_adj_b(int dtype, void* ay1, void* az1, void* af1, void* ag1, const void* ay, const void* az0,
+                              const void* vjp_z, int64_t n, double dt, double half_dt, const tsde_noise_t* nz, hipStream_t s) {
+  const bool vec = vec_ok(n, ay1, az1, af1, ag1, ay, az0, vjp_z) && noise_vec_ok(nz, false);
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    RheunAdjBOp<T> op{(T*)ay1, (T*)az1, (T*)af1, (T*)ag1, (const T*)ay, (const T*)az0, (const T*)vjp_z,
+                      (T)dt,   (T)half_dt, cell_noise_of<T>(nz)};
+    return launch_elementwise(op, n, vec, s, sizeof(T));
+  });
 }
-
-#define TSDE_RH_INSTANTIATE(T)                                                                                       \
-  template hipError_t launch_heun_final<T>(void*, const void*, const void*, const void*, const void*, const void*,   \
-                                           int64_t, double, int, int, const tsde_noise_t*, hipStream_t);             \
-  template hipError_t launch_iterated_integrals<T>(void*, const void*, const void*, int64_t, int64_t, double, int,   \
-                                                   hipStream_t);                                                     \
-  template hipError_t launch_levy_area<T>(void*, const void*, const void*, int64_t, int64_t, double, int, NoiseKey,  \
-                                          const uint64_t*, uint32_t, uint64_t, hipStream_t, int, double, int);       \
-  template hipError_t launch_rheun_z<T>(void*, const void*, const void*, const void*, const void*, int64_t, double,  \
-                                        double, const tsde_noise_t*, hipStream_t);                                   \
-  template hipError_t launch_rheun_y<T>(void*, const void*, const void*, const void*, const void*, const void*,      \
-                                        int64_t, double, double, const tsde_noise_t*, hipStream_t);                  \
-  template hipError_t launch_lincomb2<T>(void*, const void*, const void*, int64_t, double, double, hipStream_t);     \
-  template hipError_t launch_rheun_adj_a<T>(void*, void*, const void*, const void*, const void*, int64_t, double,    \
-                                            const tsde_noise_t*, hipStream_t);                                       \
-  template hipError_t launch_rheun_adj_b<T>(void*, void*, void*, void*, const void*, const void*, const void*,       \
-                                            int64_t, double, double, const tsde_noise_t*, hipStream_t);
-TSDE_RH_INSTANTIATE(float)
-TSDE_RH_INSTANTIATE(double)
 
 }  // namespace tsde

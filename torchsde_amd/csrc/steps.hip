@@ -693,166 +693,152 @@ __global__ void __launch_bounds__(kBlock) general_generic_kernel(const GeneralAr
   }
 }
 
-// ---- launchers -----------------------------------------------------------------------------------
-template <typename T>
-static CellNoise<T> make_noise(const tsde_noise_t* nz) {
-  CellNoise<T> c;
-  c.dW = (const T*)nz->dW;
-  c.dU = (const T*)nz->dU;
-  c.key.k0 = (uint32_t)nz->entropy;
-  c.key.k1 = (uint32_t)(nz->entropy >> 32);
-  c.key.elem0 = nz->elem0;
-  c.cell = nz->cell;
-  set_width<T>(c, nz->h);
-  c.bcast_d = nz->bcast_d;
-  c.key_dev = nz->entropy_dev;
-  return c;
-}
-
-static bool noise_vec_ok(const tsde_noise_t* nz, bool need_u) {
-  if (nz->dW == nullptr) return (nz->elem0 % 4) == 0;
-  if (nz->bcast_d > 0) return (nz->bcast_d % 4) == 0;  // 4 consecutive elements share a row only if d % 4 == 0
-  return aligned16(nz->dW) && (!need_u || aligned16(nz->dU));
-}
-
-template <typename T>
-hipError_t launch_step_diag(void* y1, const void* y0, const void* f, const void* g, int64_t n, double cf, double cg,
+// ---- launchers (tsde_launch.h: by_dtype, cell_noise_of, vec_ok, noise_vec_ok) ------------------------
+hipError_t launch_step_diag(int dtype, void* y1, const void* y0, const void* f, const void* g, int64_t n, double cf, double cg,
                             const tsde_noise_t* nz, hipStream_t s) {
-  StepDiagOp<T> op{(T*)y1, (const T*)y0, (const T*)f, (const T*)g, coef<T>(cf), (T)cg, make_noise<T>(nz)};
-  const bool vec = (n % 4 == 0) && aligned16(y1) && aligned16(y0) && aligned16(f) && aligned16(g) &&
-                   noise_vec_ok(nz, false);
-  return launch_elementwise(op, n, vec, s, sizeof(T));
+  const bool vec = vec_ok(n, y1, y0, f, g) && noise_vec_ok(nz, false);
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    StepDiagOp<T> op{(T*)y1, (const T*)y0, (const T*)f, (const T*)g, coef<T>(cf), (T)cg, cell_noise_of<T>(nz)};
+    return launch_elementwise(op, n, vec, s, sizeof(T));
+  });
 }
 
-template <typename T>
-hipError_t launch_cell_increment(void* W_out, void* U_out, int64_t n, const tsde_noise_t* nz, hipStream_t s) {
-  CellIncrementOp<T> op{(T*)W_out, (T*)U_out, make_noise<T>(nz)};
-  const bool vec = (n % 4 == 0) && aligned16(W_out) && (!U_out || aligned16(U_out)) && (nz->elem0 % 4 == 0);
-  return launch_elementwise(op, n, vec, s, sizeof(T));
+hipError_t launch_cell_increment(int dtype, void* W_out, void* U_out, int64_t n, const tsde_noise_t* nz, hipStream_t s) {
+  // (the entry point refuses dW != NULL, so this is the generated branch, elem0 % 4 == 0, whether or not U is asked for)
+  const bool vec = vec_ok(n, W_out, U_out) && noise_vec_ok(nz, false);
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    CellIncrementOp<T> op{(T*)W_out, (T*)U_out, cell_noise_of<T>(nz)};
+    return launch_elementwise(op, n, vec, s, sizeof(T));
+  });
 }
 
-template <typename T>
-hipError_t launch_step_prod(void* y1, const void* y0, const void* f, const void* gp, int64_t n, double cf, double cg,
+hipError_t launch_step_prod(int dtype, void* y1, const void* y0, const void* f, const void* gp, int64_t n, double cf, double cg,
                             hipStream_t s) {
-  StepProdOp<T> op{(T*)y1, (const T*)y0, (const T*)f, (const T*)gp, coef<T>(cf), (T)cg};
-  const bool vec = (n % 4 == 0) && aligned16(y1) && aligned16(y0) && aligned16(f) && aligned16(gp);
-  return launch_elementwise(op, n, vec, s, sizeof(T));
+  const bool vec = vec_ok(n, y1, y0, f, gp);
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    StepProdOp<T> op{(T*)y1, (const T*)y0, (const T*)f, (const T*)gp, coef<T>(cf), (T)cg};
+    return launch_elementwise(op, n, vec, s, sizeof(T));
+  });
 }
 
-template <typename T>
-hipError_t launch_milstein_v(void* v_out, void* W_out, const void* g, int64_t n, double dt, int ito, double scale,
+hipError_t launch_milstein_v(int dtype, void* v_out, void* W_out, const void* g, int64_t n, double dt, int ito, double scale,
                              const tsde_noise_t* nz, hipStream_t s) {
-  MilsteinVOp<T> op{(T*)v_out, (T*)W_out, (const T*)g, coef<T>(dt), (T)scale, ito, make_noise<T>(nz)};
-  const bool vec = (n % 4 == 0) && aligned16(v_out) && (!W_out || aligned16(W_out)) && (!g || aligned16(g)) &&
-                   noise_vec_ok(nz, false);
-  return launch_elementwise(op, n, vec, s, sizeof(T));
+  const bool vec = vec_ok(n, v_out, W_out, g) && noise_vec_ok(nz, false);
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    MilsteinVOp<T> op{(T*)v_out, (T*)W_out, (const T*)g, coef<T>(dt), (T)scale, ito, cell_noise_of<T>(nz)};
+    return launch_elementwise(op, n, vec, s, sizeof(T));
+  });
 }
 
-template <typename T>
-hipError_t launch_milstein_diag(void* y1, const void* y0, const void* f, const void* g, const void* gdg, int64_t n,
+hipError_t launch_milstein_diag(int dtype, void* y1, const void* y0, const void* f, const void* g, const void* gdg, int64_t n,
                                 double dt, const tsde_noise_t* nz, hipStream_t s) {
-  MilsteinDiagOp<T> op{(T*)y1, (const T*)y0, (const T*)f, (const T*)g, (const T*)gdg, coef<T>(dt), make_noise<T>(nz)};
-  const bool vec = (n % 4 == 0) && aligned16(y1) && aligned16(y0) && aligned16(f) && aligned16(g) && aligned16(gdg) &&
-                   noise_vec_ok(nz, false);
-  return launch_elementwise(op, n, vec, s, sizeof(T));
+  const bool vec = vec_ok(n, y1, y0, f, g, gdg) && noise_vec_ok(nz, false);
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    MilsteinDiagOp<T> op{(T*)y1, (const T*)y0, (const T*)f, (const T*)g, (const T*)gdg, coef<T>(dt), cell_noise_of<T>(nz)};
+    return launch_elementwise(op, n, vec, s, sizeof(T));
+  });
 }
 
-template <typename T>
-hipError_t launch_milstein_gf_prime(void* yp, const void* y0, const void* f, const void* g, int64_t n, double dt,
+hipError_t launch_milstein_gf_prime(int dtype, void* yp, const void* y0, const void* f, const void* g, int64_t n, double dt,
                                     double sqrt_dt, int ito, hipStream_t s) {
-  MilsteinGfPrimeOp<T> op{(T*)yp, (const T*)y0, (const T*)f, (const T*)g, coef<T>(dt), coef<T>(sqrt_dt), ito};
-  const bool vec = (n % 4 == 0) && aligned16(yp) && aligned16(y0) && aligned16(f) && aligned16(g);
-  return launch_elementwise(op, n, vec, s, sizeof(T));
+  const bool vec = vec_ok(n, yp, y0, f, g);
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    MilsteinGfPrimeOp<T> op{(T*)yp, (const T*)y0, (const T*)f, (const T*)g, coef<T>(dt), coef<T>(sqrt_dt), ito};
+    return launch_elementwise(op, n, vec, s, sizeof(T));
+  });
 }
 
-template <typename T>
-hipError_t launch_milstein_gf_diag(void* y1, const void* y0, const void* f, const void* g, const void* gp, int64_t n,
+hipError_t launch_milstein_gf_diag(int dtype, void* y1, const void* y0, const void* f, const void* g, const void* gp, int64_t n,
                                    double dt, double sqrt_dt, int ito, const tsde_noise_t* nz, hipStream_t s) {
-  MilsteinGfDiagOp<T> op{(T*)y1, (const T*)y0, (const T*)f, (const T*)g, (const T*)gp, coef<T>(dt), coef<T>(sqrt_dt),
-                         ito,          make_noise<T>(nz)};
-  const bool vec = (n % 4 == 0) && aligned16(y1) && aligned16(y0) && aligned16(f) && aligned16(g) && aligned16(gp) &&
-                   noise_vec_ok(nz, false);
-  return launch_elementwise(op, n, vec, s, sizeof(T));
+  const bool vec = vec_ok(n, y1, y0, f, g, gp) && noise_vec_ok(nz, false);
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    MilsteinGfDiagOp<T> op{(T*)y1, (const T*)y0, (const T*)f, (const T*)g, (const T*)gp, coef<T>(dt), coef<T>(sqrt_dt),
+                           ito,    cell_noise_of<T>(nz)};
+    return launch_elementwise(op, n, vec, s, sizeof(T));
+  });
 }
-
-constexpr int kSrkIn[5] = {0, 3, 5, 4, 2}, kSrkOut[5] = {0, 3, 3, 2, 1};   // operand counts of stages 1..4
 
 template <typename T, int STAGE>
 static hipError_t launch_srk_stage_t(void* const out[3], const void* const in[5], int64_t n, double dt, double rdt,
                                      double sqrt_dt, const tsde_noise_t* nz, hipStream_t s) {
   SrkDiagOp<T, STAGE> op;
-  bool vec = (n % 4 == 0) && noise_vec_ok(nz, true);
-  for (int j = 0; j < 3; ++j) {
-    op.out[j] = j < kSrkOut[STAGE] ? (T*)out[j] : nullptr;
-    vec = vec && aligned16(op.out[j]);
-  }
-  for (int j = 0; j < 5; ++j) {
-    op.in[j] = j < kSrkIn[STAGE] ? (const T*)in[j] : nullptr;
-    vec = vec && aligned16(op.in[j]);
-  }
+  for (int j = 0; j < 3; ++j) op.out[j] = j < kSrkOut[STAGE] ? (T*)out[j] : nullptr;
+  for (int j = 0; j < 5; ++j) op.in[j] = j < kSrkIn[STAGE] ? (const T*)in[j] : nullptr;
+  const bool vec = vec_ok(n, op.out[0], op.out[1], op.out[2], op.in[0], op.in[1], op.in[2], op.in[3], op.in[4]) &&
+                   noise_vec_ok(nz, true);
   op.dt_ = coef<T>(dt);
   op.rdt_ = coef<T>(rdt);
   op.sqrt_dt_ = coef<T>(sqrt_dt);
-  op.nz = make_noise<T>(nz);
+  op.nz = cell_noise_of<T>(nz);
   return launch_elementwise(op, n, vec, s, sizeof(T));
 }
 
-template <typename T>
-hipError_t launch_srk_stage(int stage, void* const out[3], const void* const in[5], int64_t n, double dt, double rdt,
+hipError_t launch_srk_stage(int dtype, int stage, void* const out[3], const void* const in[5], int64_t n, double dt, double rdt,
                             double sqrt_dt, const tsde_noise_t* nz, hipStream_t s) {
-  switch (stage) {
-    case 1: return launch_srk_stage_t<T, 1>(out, in, n, dt, rdt, sqrt_dt, nz, s);
-    case 2: return launch_srk_stage_t<T, 2>(out, in, n, dt, rdt, sqrt_dt, nz, s);
-    case 3: return launch_srk_stage_t<T, 3>(out, in, n, dt, rdt, sqrt_dt, nz, s);
-    case 4: return launch_srk_stage_t<T, 4>(out, in, n, dt, rdt, sqrt_dt, nz, s);
-    default: return hipErrorInvalidValue;
-  }
-}
-
-template <typename T>
-hipError_t launch_aug_segments(const tsde_seg_t* segs, int nseg, double cF, double cG, hipStream_t s) {
-  int done = 0;
-  while (done < nseg) {
-    AugTable<T> tb;
-    tb.nseg = 0;
-    tb.chunk_begin[0] = 0;
-    while (done < nseg && tb.nseg < kAugMaxSeg) {
-      const tsde_seg_t& sg = segs[done++];
-      if (sg.n <= 0) continue;
-      const int k = tb.nseg++;
-      tb.seg[k] = AugSegOp<T>{(T*)sg.out, (const T*)sg.s, (const T*)sg.F, (const T*)sg.G, (const T*)sg.D,
-                              (T)cF,      (T)cG,          (T)sg.sF,       (T)sg.sG,       (T)sg.sD};
-      tb.n[k] = sg.n;
-      // chunks start at multiples of 4096 elements, so pointer alignment decides the vector path
-      tb.vec[k] = ((sg.n % 4 == 0) && aligned16(sg.out) && aligned16(sg.s) && (!sg.F || aligned16(sg.F)) &&
-                   (!sg.G || aligned16(sg.G)) && (!sg.D || aligned16(sg.D)))
-                      ? 1
-                      : 0;
-      tb.chunk_begin[k + 1] = tb.chunk_begin[k] + (int32_t)((sg.n + kAugChunk - 1) / kAugChunk);
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    switch (stage) {
+      case 1: return launch_srk_stage_t<T, 1>(out, in, n, dt, rdt, sqrt_dt, nz, s);
+      case 2: return launch_srk_stage_t<T, 2>(out, in, n, dt, rdt, sqrt_dt, nz, s);
+      case 3: return launch_srk_stage_t<T, 3>(out, in, n, dt, rdt, sqrt_dt, nz, s);
+      case 4: return launch_srk_stage_t<T, 4>(out, in, n, dt, rdt, sqrt_dt, nz, s);
+      default: return hipErrorInvalidValue;
     }
-    if (tb.nseg == 0) break;
-    const int total = tb.chunk_begin[tb.nseg];
-    const int grid = total < kMaxGrid ? total : kMaxGrid;
-    TSDE_LAUNCH(aug_multi_kernel<T>, dim3(grid), dim3(kBlock), 0, s, tb);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+  });
 }
 
-template <typename T>
-hipError_t launch_interp(void* out, const void* ya, const void* yb, int64_t n, double w0, double w1, hipStream_t s) {
-  InterpOp<T> op{(T*)out, (const T*)ya, (const T*)yb, coef<T>(w0), coef<T>(w1)};
-  const bool vec = (n % 4 == 0) && aligned16(out) && aligned16(ya) && aligned16(yb);
-  return launch_elementwise(op, n, vec, s, sizeof(T));
+hipError_t launch_aug_segments(int dtype, const tsde_seg_t* segs, int nseg, double cF, double cG, hipStream_t s) {
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    int done = 0;
+    while (done < nseg) {
+      AugTable<T> tb;
+      tb.nseg = 0;
+      tb.chunk_begin[0] = 0;
+      while (done < nseg && tb.nseg < kAugMaxSeg) {
+        const tsde_seg_t& sg = segs[done++];
+        if (sg.n <= 0) continue;
+        const int k = tb.nseg++;
+        tb.seg[k] = AugSegOp<T>{(T*)sg.out, (const T*)sg.s, (const T*)sg.F, (const T*)sg.G, (const T*)sg.D,
+                                (T)cF,      (T)cG,          (T)sg.sF,       (T)sg.sG,       (T)sg.sD};
+        tb.n[k] = sg.n;
+        // chunks start at multiples of 4096 elements, so pointer alignment decides the vector path
+        tb.vec[k] = vec_ok(sg.n, sg.out, sg.s, sg.F, sg.G, sg.D) ? 1 : 0;
+        tb.chunk_begin[k + 1] = tb.chunk_begin[k] + (int32_t)((sg.n + kAugChunk - 1) / kAugChunk);
+      }
+      if (tb.nseg == 0) break;
+      const int total = tb.chunk_begin[tb.nseg];
+      const int grid = total < kMaxGrid ? total : kMaxGrid;
+      TSDE_LAUNCH(aug_multi_kernel<T>, dim3(grid), dim3(kBlock), 0, s, tb);
+      const hipError_t e = hipGetLastError();
+      if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+  });
 }
 
+hipError_t launch_interp(int dtype, void* out, const void* ya, const void* yb, int64_t n, double w0, double w1, hipStream_t s) {
+  const bool vec = vec_ok(n, out, ya, yb);
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    InterpOp<T> op{(T*)out, (const T*)ya, (const T*)yb, coef<T>(w0), coef<T>(w1)};
+    return launch_elementwise(op, n, vec, s, sizeof(T));
+  });
+}
+
+// ---- the general-noise contraction: what launch_step_general and launch_step_shared have in common ----------------
+// `g`: (B, d, m), or with `shared` ONE (d, m) matrix. rows_per_tile is the chosen path's to set.
 template <typename T>
-hipError_t launch_step_general(void* y1, const void* y0, const void* f, const void* g, int64_t B, int64_t d, int64_t m,
-                               double ca, double cf, double cg, int weight_mode, double cw, double cu, double rdt,
-                               const tsde_noise_t* nz, hipStream_t s) {
-  if (B <= 0 || d <= 0) return hipSuccess;
-  if (m <= 0 || m > kGenMaxNoise) return hipErrorInvalidValue;
+static GeneralArgs<T> general_args(void* y1, const void* y0, const void* f, const void* g, int64_t B, int64_t d, int64_t m,
+                                   double ca, double cf, double cg, int weight_mode, double cw, double cu, double rdt,
+                                   const tsde_noise_t* nz, int shared) {
   GeneralArgs<T> a;
   a.y1 = (T*)y1;
   a.y0 = (const T*)y0;
@@ -868,108 +854,99 @@ hipError_t launch_step_general(void* y1, const void* y0, const void* f, const vo
   a.cw = (T)cw;
   a.cu = (T)cu;
   a.rdt_ = coef<T>(rdt);
-  a.nz = make_noise<T>(nz);
-  a.shared = 0;
+  a.nz = cell_noise_of<T>(nz);
+  a.rows_per_tile = 0;
+  a.shared = shared;
   a.vec_io = 0;
-  const int64_t G = m / 4;
-  const bool pow2 = (m % 4 == 0) && G >= 1 && G <= 64 && ((G & (G - 1)) == 0);
-  // the fast path loads increments (external) or forms Philox quads at row*m + 4*lane: needs 16-B alignment there
-  const bool noise_ok = nz->dW ? (aligned16(nz->dW) && (!nz->dU || aligned16(nz->dU))) : (nz->elem0 % 4 == 0);
-  const bool fast = pow2 && aligned16(g) && noise_ok;
-  if (fast && (d * G) % 64 == 0 && ((d * G) / 64 == 1 || (d * G) / 64 == 2 || (d * G) / 64 == 4 || (d * G) / 64 == 8)) {
-    const int nc = (int)((d * G) / 64);
-    // rows sharing one Philox call of their wave: as many as the call covers (64 / G), less while the launch would
-    // otherwise have fewer than ~4 waves per SIMD (1024 SIMDs) to overlap their loads with
-    static const int64_t min_waves = [] {
-      const char* e = getenv("TSDE_GENERAL_MIN_WAVES");      // (tuning knob of tools/bench_kernels.py; default below)
-      return e ? (int64_t)atoll(e) : (int64_t)4096;
-    }();
-    int64_t rw = 64 / G;
-    while (rw > 1 && (B + rw - 1) / rw < min_waves) rw >>= 1;
-    a.rows_per_tile = (int)rw;
-    const int64_t groups = (B + rw - 1) / rw;
-    int64_t blocks = (groups + (kBlock / 64) - 1) / (kBlock / 64);   // one wave per group of rows
-    if (blocks > kMaxGrid) blocks = kMaxGrid;
-    if (nc == 1) TSDE_LAUNCH((general_rows_kernel<T, 1>), dim3((int)blocks), dim3(kBlock), 0, s, a);
-    else if (nc == 2) TSDE_LAUNCH((general_rows_kernel<T, 2>), dim3((int)blocks), dim3(kBlock), 0, s, a);
-    else if (nc == 4) TSDE_LAUNCH((general_rows_kernel<T, 4>), dim3((int)blocks), dim3(kBlock), 0, s, a);
-    else TSDE_LAUNCH((general_rows_kernel<T, 8>), dim3((int)blocks), dim3(kBlock), 0, s, a);
-    return hipGetLastError();
-  }
-  if (fast) {
-    const int64_t total4 = B * d * G;
-    const int64_t spans = (total4 + 64 * kGenUnroll - 1) / (64 * kGenUnroll);   // one wave per span
-    int64_t blocks = (spans + (kBlock / 64) - 1) / (kBlock / 64);
-    if (blocks > kMaxGrid) blocks = kMaxGrid;
-    a.rows_per_tile = 0;
-    TSDE_LAUNCH(general_fast_kernel<T>, dim3((int)blocks), dim3(kBlock), 0, s, a);
-    return hipGetLastError();
-  }
-  // generic path: rows per tile bounded by the LDS staging buffer
-  int64_t rows = kGenMaxNoise / m;
-  const int64_t want = (2 * kBlock + d - 1) / d;
+  return a;
+}
+
+// The vector kernels load increments (external) or form Philox quads at row*m + 4*lane: needs 16-B alignment there.
+static bool general_noise_ok(const tsde_noise_t* nz) {
+  return nz->dW ? (aligned16(nz->dW) && aligned16(nz->dU)) : (nz->elem0 % 4 == 0);
+}
+
+// Shapes the vector kernels do not cover: one thread per output, the increments of a tile of rows staged in LDS (which
+// bounds the rows per tile), g -- or the shared S, still without materialising B copies of it -- read through the cache.
+template <typename T>
+static hipError_t launch_general_generic(GeneralArgs<T>& a, hipStream_t s) {
+  int64_t rows = kGenMaxNoise / a.m;
+  const int64_t want = (2 * kBlock + a.d - 1) / a.d;
   if (rows > want) rows = want;
   if (rows < 1) rows = 1;
   a.rows_per_tile = (int)rows;
-  const int64_t n_tiles = (B + rows - 1) / rows;
+  const int64_t n_tiles = (a.B + rows - 1) / rows;
   const int grid = (int)(n_tiles < kMaxGrid ? n_tiles : kMaxGrid);
   TSDE_LAUNCH(general_generic_kernel<T>, dim3(grid), dim3(kBlock), 0, s, a);
   return hipGetLastError();
 }
 
+hipError_t launch_step_general(int dtype, void* y1, const void* y0, const void* f, const void* g, int64_t B, int64_t d,
+                               int64_t m, double ca, double cf, double cg, int weight_mode, double cw, double cu, double rdt,
+                               const tsde_noise_t* nz, hipStream_t s) {
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    if (B <= 0 || d <= 0) return hipSuccess;
+    if (m <= 0 || m > kGenMaxNoise) return hipErrorInvalidValue;
+    GeneralArgs<T> a = general_args<T>(y1, y0, f, g, B, d, m, ca, cf, cg, weight_mode, cw, cu, rdt, nz, 0);
+    const int64_t G = m / 4;
+    const bool pow2 = (m % 4 == 0) && G >= 1 && G <= 64 && ((G & (G - 1)) == 0);
+    const bool fast = pow2 && aligned16(g) && general_noise_ok(nz);
+    if (fast && (d * G) % 64 == 0 && ((d * G) / 64 == 1 || (d * G) / 64 == 2 || (d * G) / 64 == 4 || (d * G) / 64 == 8)) {
+      const int nc = (int)((d * G) / 64);
+      // rows sharing one Philox call of their wave: as many as the call covers (64 / G), less while the launch would
+      // otherwise have fewer than ~4 waves per SIMD (1024 SIMDs) to overlap their loads with
+      static const int64_t min_waves = [] {
+        const char* e = getenv("TSDE_GENERAL_MIN_WAVES");      // (tuning knob of tools/bench_kernels.py; default below)
+        return e ? (int64_t)atoll(e) : (int64_t)4096;
+      }();
+      int64_t rw = 64 / G;
+      while (rw > 1 && (B + rw - 1) / rw < min_waves) rw >>= 1;
+      a.rows_per_tile = (int)rw;
+      const int64_t groups = (B + rw - 1) / rw;
+      int64_t blocks = (groups + (kBlock / 64) - 1) / (kBlock / 64);   // one wave per group of rows
+      if (blocks > kMaxGrid) blocks = kMaxGrid;
+      if (nc == 1) TSDE_LAUNCH((general_rows_kernel<T, 1>), dim3((int)blocks), dim3(kBlock), 0, s, a);
+      else if (nc == 2) TSDE_LAUNCH((general_rows_kernel<T, 2>), dim3((int)blocks), dim3(kBlock), 0, s, a);
+      else if (nc == 4) TSDE_LAUNCH((general_rows_kernel<T, 4>), dim3((int)blocks), dim3(kBlock), 0, s, a);
+      else TSDE_LAUNCH((general_rows_kernel<T, 8>), dim3((int)blocks), dim3(kBlock), 0, s, a);
+      return hipGetLastError();
+    }
+    if (fast) {
+      const int64_t total4 = B * d * G;
+      const int64_t spans = (total4 + 64 * kGenUnroll - 1) / (64 * kGenUnroll);   // one wave per span
+      int64_t blocks = (spans + (kBlock / 64) - 1) / (kBlock / 64);
+      if (blocks > kMaxGrid) blocks = kMaxGrid;
+      TSDE_LAUNCH(general_fast_kernel<T>, dim3((int)blocks), dim3(kBlock), 0, s, a);
+      return hipGetLastError();
+    }
+    return launch_general_generic(a, s);
+  });
+}
+
 // S: (d, m) row-major, contiguous. Matrix cores for m % 4 == 0 (the counter RNG and external increments are addressed in
 // quads of one row), m <= 64, d <= 128; other shapes take the generic per-output kernel with S shared.
-template <typename T>
-hipError_t launch_step_shared(void* y1, const void* y0, const void* f, const void* S, int64_t B, int64_t d, int64_t m,
-                              double ca, double cf, double cg, int weight_mode, double cw, double cu, double rdt,
+hipError_t launch_step_shared(int dtype, void* y1, const void* y0, const void* f, const void* S, int64_t B, int64_t d,
+                              int64_t m, double ca, double cf, double cg, int weight_mode, double cw, double cu, double rdt,
                               const tsde_noise_t* nz, hipStream_t s) {
-  if (B <= 0 || d <= 0) return hipSuccess;
-  if (m <= 0 || m > kGenMaxNoise) return hipErrorInvalidValue;
-  const bool noise_ok = nz->dW ? (aligned16(nz->dW) && (!nz->dU || aligned16(nz->dU))) : (nz->elem0 % 4 == 0);
-  // S^T staged in LDS: (d rounded to 16) rows of (m rounded to 16) + 4 elements; float64 at d > 112, m > 48 needs 68 KiB, which
-  // a device with 64 KiB per workgroup cannot give (queried once): such shapes take the generic kernel, like the odd ones
-  const size_t lds_needed = (size_t)((d + 15) / 16) * 16 * (((m + 15) & ~(int64_t)15) + 4) * sizeof(T);
-  const bool mfma = m <= 64 && m % 4 == 0 && d <= 128 && noise_ok && aligned16(S) && lds_needed <= dynamic_lds_limit();
-  GeneralArgs<T> a;
-  a.y1 = (T*)y1;
-  a.y0 = (const T*)y0;
-  a.f = (const T*)f;
-  a.g = (const T*)S;
-  a.B = B;
-  a.d = d;
-  a.m = m;
-  a.ca = (T)ca;
-  a.cf_ = coef<T>(cf);
-  a.cg = (T)cg;
-  a.weight_mode = weight_mode;
-  a.cw = (T)cw;
-  a.cu = (T)cu;
-  a.rdt_ = coef<T>(rdt);
-  a.nz = make_noise<T>(nz);
-  a.rows_per_tile = 0;
-  a.shared = 1;
-  a.vec_io = 0;
-  if (!mfma) {
-    // shapes the tiles do not cover (m not a multiple of 4, m > 64, d > 128): one thread per output, the increments of
-    // a tile of rows staged in LDS, S read through the cache -- still without materialising B copies of it
-    int64_t rows = kGenMaxNoise / m;
-    const int64_t want = (2 * kBlock + d - 1) / d;
-    if (rows > want) rows = want;
-    if (rows < 1) rows = 1;
-    a.rows_per_tile = (int)rows;
-    const int64_t n_tiles = (B + rows - 1) / rows;
-    const int grid = (int)(n_tiles < kMaxGrid ? n_tiles : kMaxGrid);
-    TSDE_LAUNCH(general_generic_kernel<T>, dim3(grid), dim3(kBlock), 0, s, a);
-    return hipGetLastError();
-  }
-  const int dt = (int)((d + 15) / 16);
-  const int m16 = (int)((m + 15) & ~(int64_t)15);
-  const size_t lds = (size_t)dt * 16 * (m16 + 4) * sizeof(T);
-  const int64_t tiles = (B + 15) / 16;
-  // one 16-row tile per wave, then grid-stride over at most as many blocks as are resident at once (4 per CU at the
-  // register count of the wider tiles): a block stages S once, however many tiles its waves go on to process
-  int64_t blocks = (tiles + (kBlock / 64) - 1) / (kBlock / 64);
-  if (blocks > 256 * 4) blocks = 256 * 4;
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    if (B <= 0 || d <= 0) return hipSuccess;
+    if (m <= 0 || m > kGenMaxNoise) return hipErrorInvalidValue;
+    GeneralArgs<T> a = general_args<T>(y1, y0, f, S, B, d, m, ca, cf, cg, weight_mode, cw, cu, rdt, nz, 1);
+    // S^T staged in LDS: (d rounded to 16) rows of (m rounded to 16) + 4 elements; float64 at d > 112, m > 48 needs 68 KiB,
+    // which a device with 64 KiB per workgroup cannot give (queried once): such shapes take the generic kernel, like the
+    // odd ones (m not a multiple of 4, m > 64, d > 128)
+    const int dt = (int)((d + 15) / 16);
+    const int m16 = (int)((m + 15) & ~(int64_t)15);
+    const size_t lds = (size_t)dt * 16 * (m16 + 4) * sizeof(T);
+    const bool mfma = m <= 64 && m % 4 == 0 && d <= 128 && general_noise_ok(nz) && aligned16(S) && lds <= dynamic_lds_limit();
+    if (!mfma) return launch_general_generic(a, s);
+    const int64_t tiles = (B + 15) / 16;
+    // one 16-row tile per wave, then grid-stride over at most as many blocks as are resident at once (4 per CU at the
+    // register count of the wider tiles): a block stages S once, however many tiles its waves go on to process
+    int64_t blocks = (tiles + (kBlock / 64) - 1) / (kBlock / 64);
+    if (blocks > 256 * 4) blocks = 256 * 4;
 #define TSDE_SHARED_CASE(N)                                                                                          \
   case N: {                                                                                                          \
     if (lds > 64 * 1024) {                                                                                           \
@@ -980,47 +957,20 @@ hipError_t launch_step_shared(void* y1, const void* y0, const void* f, const voi
     TSDE_LAUNCH((shared_mfma_kernel<T, N>), dim3((int)blocks), dim3(kBlock), lds, s, a);                             \
     break;                                                                                                           \
   }
-  switch (dt) {
-    TSDE_SHARED_CASE(1)
-    TSDE_SHARED_CASE(2)
-    TSDE_SHARED_CASE(3)
-    TSDE_SHARED_CASE(4)
-    TSDE_SHARED_CASE(5)
-    TSDE_SHARED_CASE(6)
-    TSDE_SHARED_CASE(7)
-    TSDE_SHARED_CASE(8)
-    default: return hipErrorNotSupported;
-  }
+    switch (dt) {
+      TSDE_SHARED_CASE(1)
+      TSDE_SHARED_CASE(2)
+      TSDE_SHARED_CASE(3)
+      TSDE_SHARED_CASE(4)
+      TSDE_SHARED_CASE(5)
+      TSDE_SHARED_CASE(6)
+      TSDE_SHARED_CASE(7)
+      TSDE_SHARED_CASE(8)
+      default: return hipErrorNotSupported;
+    }
 #undef TSDE_SHARED_CASE
-  return hipGetLastError();
+    return hipGetLastError();
+  });
 }
-
-#define TSDE_INSTANTIATE(T)                                                                                          \
-  template hipError_t launch_cell_increment<T>(void*, void*, int64_t, const tsde_noise_t*, hipStream_t);             \
-  template hipError_t launch_step_diag<T>(void*, const void*, const void*, const void*, int64_t, double, double,     \
-                                          const tsde_noise_t*, hipStream_t);                                         \
-  template hipError_t launch_step_prod<T>(void*, const void*, const void*, const void*, int64_t, double, double,     \
-                                          hipStream_t);                                                              \
-  template hipError_t launch_step_general<T>(void*, const void*, const void*, const void*, int64_t, int64_t, int64_t, \
-                                             double, double, double, int, double, double, double,                    \
-                                             const tsde_noise_t*, hipStream_t);                                      \
-  template hipError_t launch_step_shared<T>(void*, const void*, const void*, const void*, int64_t, int64_t, int64_t, \
-                                            double, double, double, int, double, double, double,                     \
-                                            const tsde_noise_t*, hipStream_t);                                       \
-  template hipError_t launch_milstein_v<T>(void*, void*, const void*, int64_t, double, int, double,                  \
-                                           const tsde_noise_t*, hipStream_t);                                        \
-  template hipError_t launch_milstein_diag<T>(void*, const void*, const void*, const void*, const void*, int64_t,    \
-                                              double, const tsde_noise_t*, hipStream_t);                             \
-  template hipError_t launch_milstein_gf_prime<T>(void*, const void*, const void*, const void*, int64_t, double,     \
-                                                  double, int, hipStream_t);                                         \
-  template hipError_t launch_milstein_gf_diag<T>(void*, const void*, const void*, const void*, const void*, int64_t, \
-                                                 double, double, int, const tsde_noise_t*, hipStream_t);             \
-  template hipError_t launch_srk_stage<T>(int, void* const[3], const void* const[5], int64_t, double, double, double, \
-                                          const tsde_noise_t*, hipStream_t);                                         \
-  template hipError_t launch_aug_segments<T>(const tsde_seg_t*, int, double, double, hipStream_t);                   \
-  template hipError_t launch_interp<T>(void*, const void*, const void*, int64_t, double, double, hipStream_t);
-
-TSDE_INSTANTIATE(float)
-TSDE_INSTANTIATE(double)
 
 }  // namespace tsde

@@ -715,27 +715,34 @@ static hipError_t launch_traj_m(const TrajArgs<T>& p, bool vec, bool pow2, hipSt
   return p.sens ? launch_traj_form<T, METHOD, true>(p, vec, s) : launch_traj_values<T, METHOD, false>(p, vec, pow2, s);
 }
 
-template <typename T>
-hipError_t launch_trajectory_affine_diag(void* ys, void* sens, const void* y0, int64_t rows, int64_t d, const void* a,
-                                         const void* b, const void* c, const void* e, int64_t cstride, int method,
-                                         const tsde_traj_t* tr, NoiseKey key, const uint64_t* key_dev, hipStream_t s) {
-  TrajArgs<T> p;
-  traj_common<T>(p, ys, y0, rows, d, tr, key, key_dev);
-  p.sens = (T*)sens;
-  p.a = (const T*)a;
-  p.b = (const T*)b;
-  p.c = (const T*)c;
-  p.e = (const T*)e;
-  p.cstride = cstride;
-  if ((b == nullptr) != (e == nullptr)) return hipErrorInvalidValue;   // the linear form takes BOTH shifts as null
-  if (b == nullptr && (cstride != 0 || sens)) return hipErrorInvalidValue;
-  if (nothing_to_do(p)) return hipSuccess;
-  const bool vec = may_vec(p, p.a, p.b, p.c, p.e, p.sens) &&
-                   (key.elem0 % 4 == 0) &&   // diagonal noise: a lane's 4 elements are one Philox quad
-                   (cstride % 4 == 0);       // coefficient tables: every row starts on a 16-byte group
-  const bool pow2 = (tr->flags & TSDE_TRAJ_POW2_STEPS) != 0;
-  return dispatch_method(method, [&](auto m) { return launch_traj_m<T, decltype(m)::value>(p, vec, pow2, s); });
+// (The four launchers of this file that the C entry points call dispatch on the dtype like the stepwise ones, tsde_launch.h:
+//  by_dtype. A specialised unit includes this file for its helpers and kernels only and leaves them out.)
+#ifndef TSDE_SPECIALISE_TU
+hipError_t launch_trajectory_affine_diag(int dtype, void* ys, void* sens, const void* y0, int64_t rows, int64_t d,
+                                         const void* a, const void* b, const void* c, const void* e, int64_t cstride,
+                                         int method, const tsde_traj_t* tr, NoiseKey key, const uint64_t* key_dev,
+                                         hipStream_t s) {
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    TrajArgs<T> p;
+    traj_common<T>(p, ys, y0, rows, d, tr, key, key_dev);
+    p.sens = (T*)sens;
+    p.a = (const T*)a;
+    p.b = (const T*)b;
+    p.c = (const T*)c;
+    p.e = (const T*)e;
+    p.cstride = cstride;
+    if ((b == nullptr) != (e == nullptr)) return hipErrorInvalidValue;   // the linear form takes BOTH shifts as null
+    if (b == nullptr && (cstride != 0 || sens)) return hipErrorInvalidValue;
+    if (nothing_to_do(p)) return hipSuccess;
+    const bool vec = may_vec(p, p.a, p.b, p.c, p.e, p.sens) &&
+                     (key.elem0 % 4 == 0) &&   // diagonal noise: a lane's 4 elements are one Philox quad
+                     (cstride % 4 == 0);       // coefficient tables: every row starts on a 16-byte group
+    const bool pow2 = (tr->flags & TSDE_TRAJ_POW2_STEPS) != 0;
+    return dispatch_method(method, [&](auto m) { return launch_traj_m<T, decltype(m)::value>(p, vec, pow2, s); });
+  });
 }
+#endif
 
 template <typename T>
 struct ExprArgs {
@@ -823,22 +830,26 @@ static hipError_t launch_expr_m(const ExprArgs<T>& p, bool vec, hipStream_t s) {
   return launch_lanes(trajectory_expr_kernel<T, METHOD, 1>, p.n, s, p);
 }
 
-template <typename T>
-hipError_t launch_trajectory_expr_diag(void* ys, const void* y0, int64_t rows, int64_t d, const void* const coef[8],
+#ifndef TSDE_SPECIALISE_TU
+hipError_t launch_trajectory_expr_diag(int dtype, void* ys, const void* y0, int64_t rows, int64_t d, const void* const coef[8],
                                        int64_t cstride, int f_kind, int g_kind, int method, const tsde_traj_t* tr,
                                        NoiseKey key, const uint64_t* key_dev, hipStream_t s) {
-  ExprArgs<T> p;
-  traj_common<T>(p, ys, y0, rows, d, tr, key, key_dev);
-  for (int c = 0; c < 8; ++c) p.coef[c] = (const T*)coef[c];
-  p.cstride = cstride;
-  p.f_kind = f_kind;
-  p.g_kind = g_kind;
-  if (nothing_to_do(p)) return hipSuccess;
-  const bool vec = may_vec(p, p.coef[0], p.coef[1], p.coef[2], p.coef[3], p.coef[4], p.coef[5], p.coef[6], p.coef[7]) &&
-                   (key.elem0 % 4 == 0) &&   // diagonal noise: a lane's 4 elements are one Philox quad
-                   (cstride % 4 == 0);       // coefficient tables: every row starts on a 16-byte group
-  return dispatch_method(method, [&](auto m) { return launch_expr_m<T, decltype(m)::value>(p, vec, s); });
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    ExprArgs<T> p;
+    traj_common<T>(p, ys, y0, rows, d, tr, key, key_dev);
+    for (int c = 0; c < 8; ++c) p.coef[c] = (const T*)coef[c];
+    p.cstride = cstride;
+    p.f_kind = f_kind;
+    p.g_kind = g_kind;
+    if (nothing_to_do(p)) return hipSuccess;
+    const bool vec = may_vec(p, p.coef[0], p.coef[1], p.coef[2], p.coef[3], p.coef[4], p.coef[5], p.coef[6], p.coef[7]) &&
+                     (key.elem0 % 4 == 0) &&   // diagonal noise: a lane's 4 elements are one Philox quad
+                     (cstride % 4 == 0);       // coefficient tables: every row starts on a 16-byte group
+    return dispatch_method(method, [&](auto m) { return launch_expr_m<T, decltype(m)::value>(p, vec, s); });
+  });
 }
+#endif
 
 // ---- expression PROGRAMS ------------------------------------------------------------------------------------------------
 // Drift, diffusion (and the diffusion's derivative, for Milstein) as small postfix programs over a four-deep value stack:
@@ -1506,29 +1517,24 @@ static hipError_t launch_additive_m(const ProgAdditiveArgs<T>& q, hipStream_t s)
   return hipErrorInvalidValue;
 }
 
-template <typename T>
-hipError_t launch_trajectory_prog_additive(void* ys, const void* y0, int64_t rows, int64_t d, int64_t m, const uint32_t* code,
-                                           int f_len, const void* consts, int n_const, const void* gtab, int time_dependent,
-                                           int method, const tsde_traj_t* tr, NoiseKey key, const uint64_t* key_dev,
-                                           hipStream_t s) {
+#ifndef TSDE_SPECIALISE_TU
+hipError_t launch_trajectory_prog_additive(int dtype, void* ys, const void* y0, int64_t rows, int64_t d, int64_t m,
+                                           const uint32_t* code, int f_len, const void* consts, int n_const, const void* gtab,
+                                           int time_dependent, int method, const tsde_traj_t* tr, NoiseKey key,
+                                           const uint64_t* key_dev, hipStream_t s) {
   if (f_len > kProgWords) return hipErrorInvalidValue;
-  const ProgAdditiveArgs<T> q = prog_additive_args(
-      prog_args<T>(ys, y0, rows, d, consts, n_const, 0, tr, key, key_dev, code, f_len), m, gtab, time_dependent, method);
-  // Euler, midpoint and SRK only (the kernel has no other scheme, and none is instantiated)
-  return dispatch_method(method, [&](auto m) {
-    constexpr int METHOD = decltype(m)::value;
-    if constexpr (METHOD == kEuler || METHOD == kMidpoint || METHOD == kSrk) return launch_additive_m<T, METHOD>(q, s);
-    else return hipErrorInvalidValue;
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    const ProgAdditiveArgs<T> q = prog_additive_args(
+        prog_args<T>(ys, y0, rows, d, consts, n_const, 0, tr, key, key_dev, code, f_len), m, gtab, time_dependent, method);
+    // Euler, midpoint and SRK only (the kernel has no other scheme, and none is instantiated)
+    return dispatch_method(method, [&](auto m) {
+      constexpr int METHOD = decltype(m)::value;
+      if constexpr (METHOD == kEuler || METHOD == kMidpoint || METHOD == kSrk) return launch_additive_m<T, METHOD>(q, s);
+      else return hipErrorInvalidValue;
+    });
   });
 }
-
-#ifndef TSDE_SPECIALISE_TU
-template hipError_t launch_trajectory_prog_additive<float>(void*, const void*, int64_t, int64_t, int64_t, const uint32_t*, int,
-                                                           const void*, int, const void*, int, int, const tsde_traj_t*,
-                                                           NoiseKey, const uint64_t*, hipStream_t);
-template hipError_t launch_trajectory_prog_additive<double>(void*, const void*, int64_t, int64_t, int64_t, const uint32_t*, int,
-                                                            const void*, int, const void*, int, int, const tsde_traj_t*,
-                                                            NoiseKey, const uint64_t*, hipStream_t);
 #endif
 
 // values, or (with `sens`) values and path-wise sensitivities
@@ -1538,41 +1544,19 @@ static hipError_t launch_prog_diag_m(const ProgArgs<T>& p, void* sens, const int
   return launch_prog_m<T, METHOD>(p, s);
 }
 
-template <typename T>
-hipError_t launch_trajectory_prog_diag(void* ys, void* sens, const int8_t* param_slot, const void* y0, int64_t rows, int64_t d,
-                                       const uint32_t* code, int f_len, int g_len, int dg_len, const void* consts, int n_const,
-                                       int scalar_noise, int method, const tsde_traj_t* tr, NoiseKey key,
+#ifndef TSDE_SPECIALISE_TU
+hipError_t launch_trajectory_prog_diag(int dtype, void* ys, void* sens, const int8_t* param_slot, const void* y0, int64_t rows,
+                                       int64_t d, const uint32_t* code, int f_len, int g_len, int dg_len, const void* consts,
+                                       int n_const, int scalar_noise, int method, const tsde_traj_t* tr, NoiseKey key,
                                        const uint64_t* key_dev, hipStream_t s) {
   if (f_len + g_len + dg_len > kProgWords) return hipErrorInvalidValue;
-  const ProgArgs<T> p = prog_args<T>(ys, y0, rows, d, consts, n_const, scalar_noise, tr, key, key_dev, code, f_len, g_len, dg_len);
-  return dispatch_method(method, [&](auto m) { return launch_prog_diag_m<T, decltype(m)::value>(p, sens, param_slot, s); });
+  return by_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    const ProgArgs<T> p =
+        prog_args<T>(ys, y0, rows, d, consts, n_const, scalar_noise, tr, key, key_dev, code, f_len, g_len, dg_len);
+    return dispatch_method(method, [&](auto m) { return launch_prog_diag_m<T, decltype(m)::value>(p, sens, param_slot, s); });
+  });
 }
-
-#ifndef TSDE_SPECIALISE_TU
-template hipError_t launch_trajectory_prog_diag<float>(void*, void*, const int8_t*, const void*, int64_t, int64_t,
-                                                       const uint32_t*, int, int, int, const void*, int, int, int,
-                                                       const tsde_traj_t*, NoiseKey, const uint64_t*, hipStream_t);
-template hipError_t launch_trajectory_prog_diag<double>(void*, void*, const int8_t*, const void*, int64_t, int64_t,
-                                                        const uint32_t*, int, int, int, const void*, int, int, int,
-                                                        const tsde_traj_t*, NoiseKey, const uint64_t*, hipStream_t);
-#endif
-
-#ifndef TSDE_SPECIALISE_TU
-template hipError_t launch_trajectory_expr_diag<float>(void*, const void*, int64_t, int64_t, const void* const[8],
-                                                       int64_t, int, int, int, const tsde_traj_t*, NoiseKey,
-                                                       const uint64_t*, hipStream_t);
-template hipError_t launch_trajectory_expr_diag<double>(void*, const void*, int64_t, int64_t, const void* const[8],
-                                                        int64_t, int, int, int, const tsde_traj_t*, NoiseKey,
-                                                        const uint64_t*, hipStream_t);
-#endif
-
-#ifndef TSDE_SPECIALISE_TU
-template hipError_t launch_trajectory_affine_diag<float>(void*, void*, const void*, int64_t, int64_t, const void*,
-                                                         const void*, const void*, const void*, int64_t, int,
-                                                         const tsde_traj_t*, NoiseKey, const uint64_t*, hipStream_t);
-template hipError_t launch_trajectory_affine_diag<double>(void*, void*, const void*, int64_t, int64_t, const void*,
-                                                          const void*, const void*, const void*, int64_t, int,
-                                                          const tsde_traj_t*, NoiseKey, const uint64_t*, hipStream_t);
 #endif
 
 }  // namespace tsde

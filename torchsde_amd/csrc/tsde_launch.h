@@ -1,4 +1,4 @@
-// Typed launchers behind the C ABI (capi.hip dispatches on dtype).
+// Launchers behind the C ABI (capi.hip hands the dtype on; a launcher dispatches on it once, `by_dtype`).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -145,121 +145,128 @@ struct QueryArgs {
   WalkCfg cfg;
 };
 
-template <typename T>
-hipError_t launch_normals(void* out, int64_t n, NoiseKey key, uint32_t cell, uint64_t node, uint32_t stream_id,
-                          hipStream_t s);
-template <typename T>
-hipError_t launch_query(void* W, void* U, void* H, int64_t n, NoiseKey key, const QueryArgs& qa, bool have_h,
-                        hipStream_t s);
-template <typename T>
-hipError_t launch_cell_increment(void* W_out, void* U_out, int64_t n, const tsde_noise_t* nz, hipStream_t s);
-template <typename T>
-hipError_t launch_step_diag(void* y1, const void* y0, const void* f, const void* g, int64_t n, double cf, double cg,
-                            const tsde_noise_t* nz, hipStream_t s);
-template <typename T>
-hipError_t launch_step_prod(void* y1, const void* y0, const void* f, const void* gp, int64_t n, double cf, double cg,
-                            hipStream_t s);
-template <typename T>
-hipError_t launch_step_general(void* y1, const void* y0, const void* f, const void* g, int64_t B, int64_t d, int64_t m,
-                               double ca, double cf, double cg, int weight_mode, double cw, double cu, double rdt,
-                               const tsde_noise_t* nz, hipStream_t s);
-template <typename T>
-hipError_t launch_step_shared(void* y1, const void* y0, const void* f, const void* S, int64_t B, int64_t d, int64_t m,
-                              double ca, double cf, double cg, int weight_mode, double cw, double cu, double rdt,
-                              const tsde_noise_t* nz, hipStream_t s);
-template <typename T>
-hipError_t launch_milstein_v(void* v_out, void* W_out, const void* g, int64_t n, double dt, int ito, double scale,
-                             const tsde_noise_t* nz, hipStream_t s);
-template <typename T>
-hipError_t launch_milstein_diag(void* y1, const void* y0, const void* f, const void* g, const void* gdg, int64_t n,
-                                double dt, const tsde_noise_t* nz, hipStream_t s);
-template <typename T>
-hipError_t launch_milstein_gf_prime(void* yp, const void* y0, const void* f, const void* g, int64_t n, double dt,
-                                    double sqrt_dt, int ito, hipStream_t s);
-template <typename T>
-hipError_t launch_milstein_gf_diag(void* y1, const void* y0, const void* f, const void* g, const void* gp, int64_t n,
-                                   double dt, double sqrt_dt, int ito, const tsde_noise_t* nz, hipStream_t s);
-template <typename T>
-hipError_t launch_srk_stage(int stage, void* const out[3], const void* const in[5], int64_t n, double dt, double rdt,
-                            double sqrt_dt, const tsde_noise_t* nz, hipStream_t s);
-template <typename T>
-hipError_t launch_milstein_gf_general_support(void* yk, const void* y0, const void* f, const void* g, int64_t B,
-                                              int64_t d, int64_t m, double dt, double sqrt_dt, int ito, hipStream_t s);
-template <typename T>
-hipError_t launch_milstein_gf_general_correction(void* corr, const void* g, const void* gk, const void* I, int64_t B,
-                                                 int64_t d, int64_t m, double sqrt_dt, hipStream_t s);
-template <typename T>
-hipError_t launch_aug_segments(const tsde_seg_t* segs, int nseg, double cF, double cG, hipStream_t s);
-template <typename T>
-hipError_t launch_interp(void* out, const void* ya, const void* yb, int64_t n, double w0, double w1, hipStream_t s);
-}  // namespace tsde
+// ---- the stepwise launch layer (steps.hip, rheun.hip, adaptive.hip, reduce.hip, milstein_general.hip, brownian.hip) -------
 
-namespace tsde {
+// A launcher takes the state dtype of its C entry point and writes its body once, for a value `t` of that type:
+//   return by_dtype(dtype, [&](auto t) { using T = decltype(t); ... });
+template <typename Body>
+hipError_t by_dtype(int dtype, Body&& body) {
+  if (dtype == TSDE_F32) return body(float{});
+  if (dtype == TSDE_F64) return body(double{});
+  return hipErrorInvalidValue;
+}
+
+// The noise of one step as the kernels take it (tsde_common.h: cell_noise): widths rounded to T on the host.
+template <typename T>
+CellNoise<T> cell_noise_of(const tsde_noise_t* nz) {
+  CellNoise<T> c;
+  c.dW = (const T*)nz->dW;
+  c.dU = (const T*)nz->dU;
+  c.key.k0 = (uint32_t)nz->entropy;
+  c.key.k1 = (uint32_t)(nz->entropy >> 32);
+  c.key.elem0 = nz->elem0;
+  c.cell = nz->cell;
+  set_width<T>(c, nz->h);
+  c.bcast_d = nz->bcast_d;
+  c.key_dev = nz->entropy_dev;
+  return c;
+}
+
+// May a lane take the increments of 4 consecutive elements at once? Generated: they are one Philox quad. External, one row
+// for the whole batch: 4 consecutive elements share a row only if d % 4 == 0. External, flat: 16-byte loads of dW (and dU).
+inline bool noise_vec_ok(const tsde_noise_t* nz, bool need_u) {
+  if (nz->dW == nullptr) return (nz->elem0 % 4) == 0;
+  if (nz->bcast_d > 0) return (nz->bcast_d % 4) == 0;
+  return aligned16(nz->dW) && (!need_u || aligned16(nz->dU));
+}
+
+// The 16-byte path of an elementwise launch: whole groups of 4 and every operand on a 16-byte boundary. A null pointer is an
+// absent operand and constrains nothing.
+template <typename... Ptr>
+bool vec_ok(int64_t n, Ptr... ptrs) {
+  return (n % 4 == 0) && (aligned16(ptrs) && ...);
+}
+
+constexpr int kSrkIn[5] = {0, 3, 5, 4, 2}, kSrkOut[5] = {0, 3, 3, 2, 1};   // operand counts of SRK (SRID2) stages 1..4
+
+hipError_t launch_normals(int dtype, void* out, int64_t n, NoiseKey key, uint32_t cell, uint64_t node, uint32_t stream_id,
+                          hipStream_t s);
+hipError_t launch_query(int dtype, void* W, void* U, void* H, int64_t n, NoiseKey key, const QueryArgs& qa, bool have_h,
+                        hipStream_t s);
+hipError_t launch_cell_increment(int dtype, void* W_out, void* U_out, int64_t n, const tsde_noise_t* nz, hipStream_t s);
+hipError_t launch_step_diag(int dtype, void* y1, const void* y0, const void* f, const void* g, int64_t n, double cf, double cg,
+                            const tsde_noise_t* nz, hipStream_t s);
+hipError_t launch_step_prod(int dtype, void* y1, const void* y0, const void* f, const void* gp, int64_t n, double cf, double cg,
+                            hipStream_t s);
+hipError_t launch_step_general(int dtype, void* y1, const void* y0, const void* f, const void* g, int64_t B, int64_t d,
+                               int64_t m, double ca, double cf, double cg, int weight_mode, double cw, double cu, double rdt,
+                               const tsde_noise_t* nz, hipStream_t s);
+hipError_t launch_step_shared(int dtype, void* y1, const void* y0, const void* f, const void* S, int64_t B, int64_t d,
+                              int64_t m, double ca, double cf, double cg, int weight_mode, double cw, double cu, double rdt,
+                              const tsde_noise_t* nz, hipStream_t s);
+hipError_t launch_milstein_v(int dtype, void* v_out, void* W_out, const void* g, int64_t n, double dt, int ito, double scale,
+                             const tsde_noise_t* nz, hipStream_t s);
+hipError_t launch_milstein_diag(int dtype, void* y1, const void* y0, const void* f, const void* g, const void* gdg, int64_t n,
+                                double dt, const tsde_noise_t* nz, hipStream_t s);
+hipError_t launch_milstein_gf_prime(int dtype, void* yp, const void* y0, const void* f, const void* g, int64_t n, double dt,
+                                    double sqrt_dt, int ito, hipStream_t s);
+hipError_t launch_milstein_gf_diag(int dtype, void* y1, const void* y0, const void* f, const void* g, const void* gp, int64_t n,
+                                   double dt, double sqrt_dt, int ito, const tsde_noise_t* nz, hipStream_t s);
+hipError_t launch_srk_stage(int dtype, int stage, void* const out[3], const void* const in[5], int64_t n, double dt, double rdt,
+                            double sqrt_dt, const tsde_noise_t* nz, hipStream_t s);
+hipError_t launch_milstein_gf_general_support(int dtype, void* yk, const void* y0, const void* f, const void* g, int64_t B,
+                                              int64_t d, int64_t m, double dt, double sqrt_dt, int ito, hipStream_t s);
+hipError_t launch_milstein_gf_general_correction(int dtype, void* corr, const void* g, const void* gk, const void* I, int64_t B,
+                                                 int64_t d, int64_t m, double sqrt_dt, hipStream_t s);
+hipError_t launch_aug_segments(int dtype, const tsde_seg_t* segs, int nseg, double cF, double cG, hipStream_t s);
+hipError_t launch_interp(int dtype, void* out, const void* ya, const void* yb, int64_t n, double w0, double w1, hipStream_t s);
 // rheun.hip
-template <typename T>
-hipError_t launch_heun_final(void* y1, const void* y0, const void* f, const void* fp, const void* g, const void* gp,
+hipError_t launch_heun_final(int dtype, void* y1, const void* y0, const void* f, const void* fp, const void* g, const void* gp,
                              int64_t n, double dt, int mode, int prod, const tsde_noise_t* nz, hipStream_t s);
-template <typename T>
-hipError_t launch_iterated_integrals(void* I, const void* W, const void* A, int64_t B, int64_t m, double dt, int ito,
+hipError_t launch_iterated_integrals(int dtype, void* I, const void* W, const void* A, int64_t B, int64_t m, double dt, int ito,
                                      hipStream_t s);
-template <typename T>
-hipError_t launch_levy_area(void* A, const void* W, const void* H, int64_t B, int64_t m, double h, int foster,
-                            NoiseKey key, const uint64_t* key_dev, uint32_t cell, uint64_t node, hipStream_t s,
-                            int fuse = 0, double dt = 0.0, int ito = 0);
-template <typename T>
-hipError_t launch_rheun_z(void* z1, const void* y0, const void* z0, const void* f0, const void* g0, int64_t n, double dt,
-                          double sgn, const tsde_noise_t* nz, hipStream_t s);
-template <typename T>
-hipError_t launch_rheun_y(void* y1, const void* y0, const void* f0, const void* f1, const void* g0, const void* g1,
+hipError_t launch_levy_area(int dtype, void* A, const void* W, const void* H, int64_t B, int64_t m, double h, int foster,
+                            NoiseKey key, const uint64_t* key_dev, uint32_t cell, uint64_t node, hipStream_t s, int fuse = 0,
+                            double dt = 0.0, int ito = 0);
+hipError_t launch_rheun_z(int dtype, void* z1, const void* y0, const void* z0, const void* f0, const void* g0, int64_t n,
+                          double dt, double sgn, const tsde_noise_t* nz, hipStream_t s);
+hipError_t launch_rheun_y(int dtype, void* y1, const void* y0, const void* f0, const void* f1, const void* g0, const void* g1,
                           int64_t n, double half_dt, double sgn, const tsde_noise_t* nz, hipStream_t s);
-template <typename T>
-hipError_t launch_lincomb2(void* out, const void* x, const void* y, int64_t n, double a, double b, hipStream_t s);
-template <typename T>
-hipError_t launch_rheun_adj_a(void* af0_out, void* ag0_out, const void* ay, const void* af0, const void* ag0, int64_t n,
-                              double half_dt, const tsde_noise_t* nz, hipStream_t s);
-template <typename T>
-hipError_t launch_rheun_adj_b(void* ay1, void* az1, void* af1, void* ag1, const void* ay, const void* az0,
-                              const void* vjp_z, int64_t n, double dt, double half_dt, const tsde_noise_t* nz,
-                              hipStream_t s);
+hipError_t launch_lincomb2(int dtype, void* out, const void* x, const void* y, int64_t n, double a, double b, hipStream_t s);
+hipError_t launch_rheun_adj_a(int dtype, void* af0_out, void* ag0_out, const void* ay, const void* af0, const void* ag0,
+                              int64_t n, double half_dt, const tsde_noise_t* nz, hipStream_t s);
+hipError_t launch_rheun_adj_b(int dtype, void* ay1, void* az1, void* af1, void* ag1, const void* ay, const void* az0,
+                              const void* vjp_z, int64_t n, double dt, double half_dt, const tsde_noise_t* nz, hipStream_t s);
 // reduce.hip
-template <typename T>
-hipError_t launch_error_norm(double* out, double* workspace, const void* yf, const void* yh, int64_t n, double rtol,
+hipError_t launch_error_norm(int dtype, double* out, double* workspace, const void* yf, const void* yh, int64_t n, double rtol,
                              double atol, double eps, hipStream_t s);
 // adaptive.hip
-template <typename T>
-hipError_t launch_adaptive_begin(double* ctl, void* scal, double out_t, const double* out_times, int n_out,
+hipError_t launch_adaptive_begin(int dtype, double* ctl, void* scal, double out_t, const double* out_times, int n_out,
                                  const double* fracs, int n_fracs, hipStream_t s);
-template <typename T>
-hipError_t launch_adaptive_control(double* ctl, void* scal, const double* error, const double* out_times,
+hipError_t launch_adaptive_control(int dtype, double* ctl, void* scal, const double* error, const double* out_times,
                                    double* accept_log, int log_capacity, const double* fracs, int n_fracs, hipStream_t s);
-template <typename T>
-hipError_t launch_adaptive_emit(const void* ys_slot, const void* prev_y, const void* curr_y, int64_t n, const double* ctl,
-                                const double* out_times, hipStream_t s);
-template <typename T>
-hipError_t launch_adaptive_commit(void* prev_y, void* curr_y, const void* y_next, int64_t n, const void* scal,
+hipError_t launch_adaptive_emit(int dtype, const void* ys_slot, const void* prev_y, const void* curr_y, int64_t n,
+                                const double* ctl, const double* out_times, hipStream_t s);
+hipError_t launch_adaptive_commit(int dtype, void* prev_y, void* curr_y, const void* y_next, int64_t n, const void* scal,
                                   hipStream_t s);
-template <typename T>
-hipError_t launch_merge_halves(void* W, void* U, const void* Wa, const void* Ha, const void* Wb, const void* Hb,
+hipError_t launch_merge_halves(int dtype, void* W, void* U, const void* Wa, const void* Ha, const void* Wb, const void* Hb,
                                int64_t n, const double* ctl, double ha, double hb, hipStream_t s);
 // trajectory.hip
-template <typename T>
-hipError_t launch_trajectory_affine_diag(void* ys, void* sens, const void* y0, int64_t rows, int64_t d, const void* a,
-                                         const void* b, const void* c, const void* e, int64_t cstride, int method,
-                                         const tsde_traj_t* tr, NoiseKey key, const uint64_t* key_dev, hipStream_t s);
-template <typename T>
-hipError_t launch_trajectory_expr_diag(void* ys, const void* y0, int64_t rows, int64_t d, const void* const coef[8],
-                                       int64_t cstride, int f_kind, int g_kind, int method, const tsde_traj_t* tr,
-                                       NoiseKey key, const uint64_t* key_dev, hipStream_t s);
-template <typename T>
-hipError_t launch_trajectory_prog_diag(void* ys, void* sens, const int8_t* param_slot, const void* y0, int64_t rows, int64_t d,
-                                       const uint32_t* code, int f_len, int g_len, int dg_len, const void* consts, int n_const,
-                                       int scalar_noise, int method, const tsde_traj_t* tr, NoiseKey key,
+hipError_t launch_trajectory_affine_diag(int dtype, void* ys, void* sens, const void* y0, int64_t rows, int64_t d,
+                                         const void* a, const void* b, const void* c, const void* e, int64_t cstride,
+                                         int method, const tsde_traj_t* tr, NoiseKey key, const uint64_t* key_dev,
+                                         hipStream_t s);
+hipError_t launch_trajectory_expr_diag(int dtype, void* ys, const void* y0, int64_t rows, int64_t d, const void* const coef[8],
+                                       int64_t cstride, int f_kind, int g_kind, int method, const tsde_traj_t* tr, NoiseKey key,
                                        const uint64_t* key_dev, hipStream_t s);
-template <typename T>
-hipError_t launch_trajectory_prog_additive(void* ys, const void* y0, int64_t rows, int64_t d, int64_t m, const uint32_t* code,
-                                           int f_len, const void* consts, int n_const, const void* gtab, int time_dependent,
-                                           int method, const tsde_traj_t* tr, NoiseKey key, const uint64_t* key_dev,
-                                           hipStream_t s);
+hipError_t launch_trajectory_prog_diag(int dtype, void* ys, void* sens, const int8_t* param_slot, const void* y0, int64_t rows,
+                                       int64_t d, const uint32_t* code, int f_len, int g_len, int dg_len, const void* consts,
+                                       int n_const, int scalar_noise, int method, const tsde_traj_t* tr, NoiseKey key,
+                                       const uint64_t* key_dev, hipStream_t s);
+hipError_t launch_trajectory_prog_additive(int dtype, void* ys, const void* y0, int64_t rows, int64_t d, int64_t m,
+                                           const uint32_t* code, int f_len, const void* consts, int n_const, const void* gtab,
+                                           int time_dependent, int method, const tsde_traj_t* tr, NoiseKey key,
+                                           const uint64_t* key_dev, hipStream_t s);
 // mlp_trajectory.hip
 hipError_t launch_trajectory_mlp_diag(void* ys, const void* y0, int64_t rows, int64_t d, int64_t h, const void* W1,
                                       const void* b1, const void* W2, const void* b2, const void* c, const void* e,

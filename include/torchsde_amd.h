@@ -708,6 +708,41 @@ int tsde_trajectory_mlp_diag_backward(void* lam, void* stash_lam, void* stash_hi
                                       uint64_t entropy, uint64_t elem0, const uint64_t* entropy_dev, int dtype,
                                       void* stream);
 
+/* tsde_trajectory_mlp_diag_backward for the solve of tsde_trajectory_mlp_diag_logqp: back-propagation through the solver
+ * of `sdeint(..., logqp=True)` (the stepping loop over `SDELogqp`, base_sde.py:240-306) for a per-channel affine prior drift
+ * h = prior_rate * y + prior_shift. Forward, per row:  l_{k+1} = l_k + 0.5 sum_i u_i^2 dt_k,  u = (f - h) / safe(g) at y_k.
+ * Reverse, with lam = dL/dy_{k+1} and a_l = dL/dl_{k+1} (per row; constant between outputs; it gains the column's cotangent
+ * where an output arrives, as lam gains grad_ys), f = W2^T act(W1 y_k + b1) + b2 formed again, and per channel
+ * w = a_l u / safe(g):
+ *     delta = (W2 (lam + w)) * act'(W1 y_k + b1) * dt_k,    stash_lam = dt_k (lam + w)
+ *     dL/dy_k = lam + W1^T delta + lam g' dW_k + dt_k (-prior_rate w - a_l u^2 g' / safe)          (g' = dg/dy)
+ *     row_rate  += lam y_k dW_k dg/de - dt_k a_l (u^2 / safe) dg/de y_k,    row_shift += lam dW_k dg/de - dt_k a_l (u^2 / safe) dg/de
+ *     row_prior_rate += -dt_k w y_k,    row_prior_shift += -dt_k w
+ * (dg/de = 1 for the affine diffusion, diff_amp s (1 - s) for the sigmoid.) safe(g) as in the forward kernel; where it replaces
+ * g (|g| <= 1e-7) it is a constant: no u^2 / safe terms there. The column's diffusion is 0, so Milstein's own terms are those of
+ * tsde_trajectory_mlp_diag_backward.
+ *   a_l          (rows)  in: dL/dl at boundary k_hi without the cotangent of an output at k_hi; out: at k_lo, likewise
+ *   grad_logqp   (n_grad, rows)  cotangent of the column at the output of boundary grad_step[j]
+ *   row_rate, row_shift, row_prior_rate, row_prior_shift (rows, d)  accumulated in place as tsde_adjoint_mlp_diag accumulates
+ *                row_rate: sums over the steps AND over each aligned group of 16 rows (row 16 k receives rows 16 k ..
+ *                16 k + 15; the other rows are left as they are); their sums over all rows are dL/d diff_rate, dL/d diff_shift,
+ *                dL/d prior_rate, dL/d prior_shift
+ *   b2, prior_rate, prior_shift (d)
+ *   bm_stride    row stride of the Brownian field, d + 1 for such a solve: element (row, channel) is elem0 + row * bm_stride +
+ *                channel, elem0 any value
+ *   method in {TSDE_TRAJ_EULER, TSDE_TRAJ_MILSTEIN_ITO} (the sigmoid diffusion with Euler only);
+ *   rows * (max(d, hidden) + 1) < 2^30. Everything else as tsde_trajectory_mlp_diag_backward. */
+int tsde_trajectory_mlp_diag_logqp_backward(void* lam, void* a_l, void* stash_lam, void* stash_hid, void* stash_delta,
+                                            void* row_rate, void* row_shift, void* row_prior_rate, void* row_prior_shift,
+                                            const void* ys_all, int32_t ys_first, const void* grad_ys,
+                                            const void* grad_logqp, const int32_t* grad_step, int32_t grad_last,
+                                            int64_t rows, int64_t d, int64_t hidden, const void* w1, const void* b1,
+                                            const void* w2, const void* b2, const void* diff_rate, const void* diff_shift,
+                                            const void* prior_rate, const void* prior_shift, int diff_kind, double diff_amp,
+                                            int activation, int method, int64_t bm_stride, const tsde_traj_t* traj,
+                                            int32_t k_lo, int32_t k_hi, uint64_t entropy, uint64_t elem0,
+                                            const uint64_t* entropy_dev, int dtype, void* stream);
+
 /* ---- The reversible Heun pair for neural SDEs, one launch each way (csrc/tsde_neural_rheun.h) ----------------------------
  * Replaces, for modules whose drift and diffusion are perceptrons of (t, y),
  *   forward:  base_solver.py:114-134 driving methods/reversible_heun.py:48-73 (ReversibleHeun.step; the carried (f, g, z) of

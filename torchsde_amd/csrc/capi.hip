@@ -853,6 +853,39 @@ int tsde_trajectory_mlp_diag_backward(void* lam, void* stash_lam, void* stash_hi
               where);
 }
 
+int tsde_trajectory_mlp_diag_logqp_backward(void* lam, void* a_l, void* stash_lam, void* stash_hid, void* stash_delta,
+                                            void* row_rate, void* row_shift, void* row_prior_rate, void* row_prior_shift,
+                                            const void* ys_all, int32_t ys_first, const void* grad_ys,
+                                            const void* grad_logqp, const int32_t* grad_step, int32_t grad_last,
+                                            int64_t rows, int64_t d, int64_t hidden, const void* w1, const void* b1,
+                                            const void* w2, const void* b2, const void* diff_rate, const void* diff_shift,
+                                            const void* prior_rate, const void* prior_shift, int diff_kind, double diff_amp,
+                                            int activation, int method, int64_t bm_stride, const tsde_traj_t* traj,
+                                            int32_t k_lo, int32_t k_hi, uint64_t entropy, uint64_t elem0,
+                                            const uint64_t* entropy_dev, int dtype, void* stream) {
+  const char* where = "tsde_trajectory_mlp_diag_logqp_backward";
+  const char* own =
+      method != TSDE_TRAJ_EULER && method != TSDE_TRAJ_MILSTEIN_ITO ? "method must be Euler or Ito Milstein"
+      : diff_kind != TSDE_DIFF_AFFINE && !(diff_kind == TSDE_DIFF_SIGMOID && method == TSDE_TRAJ_EULER)
+          ? "diffusion kind must be affine, or sigmoid with Euler" : nullptr;
+  if (const char* bad = mlp_entry_problem(
+          true, true, {lam, a_l, stash_lam, stash_hid, stash_delta, row_rate, row_shift, row_prior_rate, row_prior_shift, ys_all,
+                       w1, b1, w2, b2, diff_rate, diff_shift, prior_rate, prior_shift, traj},
+          {lam, stash_lam, stash_hid, stash_delta, row_rate, row_shift, row_prior_rate, row_prior_shift, ys_all, grad_ys}, own,
+          bm_stride < d ? "bm_stride must be at least d" : nullptr, rows, d, hidden, diff_kind, activation, dtype, traj, k_lo,
+          k_hi, ys_first))
+    return bad_arg(where, bad);
+  if (grad_last >= 0 && (!grad_ys || !grad_logqp || !grad_step)) return bad_arg(where, "grad_last >= 0 without cotangents");
+  const hipStream_t s = (hipStream_t)stream;
+  ProfScope p(TSDE_KID_MLP_BACKWARD, s);
+  return fail(tsde::launch_trajectory_mlp_diag_logqp_backward(
+                  lam, a_l, stash_lam, stash_hid, stash_delta, row_rate, row_shift, row_prior_rate, row_prior_shift, ys_all,
+                  ys_first, grad_ys, grad_logqp, grad_step, grad_last, rows, d, hidden, w1, b1, w2, b2, diff_rate, diff_shift,
+                  prior_rate, prior_shift, diff_kind, diff_amp, activation, method, traj, k_lo, k_hi, bm_stride,
+                  make_key(entropy, elem0), entropy_dev, s),
+              where);
+}
+
 int tsde_gram_partials(void* partials, void* colsum_partials, const void* a, int64_t lda, const void* b, int64_t ldb,
                        int64_t k, int64_t m, int64_t n, int32_t blocks, int dtype, void* stream) {
   const char* where = "tsde_gram_partials";

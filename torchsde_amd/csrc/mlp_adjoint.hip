@@ -86,16 +86,6 @@ struct MlpAdjKlArgs : MlpAdjArgs {
   int64_t bm_stride;        // row stride of the Brownian field: d + 1
 };
 
-// Sum of `v` over the 16 lanes of a DPP row, valid in the row's last lane (inclusive scan by row_shr 1, 2, 4, 8; lanes
-// shifted in from outside the row read 0).
-TSDE_D float row_total(float v) {
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x111, 0xf, 0xf, true));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x112, 0xf, 0xf, true));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x114, 0xf, 0xf, true));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x118, 0xf, 0xf, true));
-  return v;
-}
-
 // The kernel's LDS behind b2 / c / e (MlpLds): kAdjSums x D sums per wave -- rate, shift; KL: the prior's (hr, hs) after
 // them -- and, KL, hr and hs themselves.
 template <bool KL>
@@ -250,9 +240,7 @@ __global__ void __launch_bounds__(NW * 64)
           for (int r = 0; r < 4; ++r) {
             const float yt = y[t][r];
             const float g = diffusion_value(kSigmoid, p.diff_amp, cq[r], eq[r], yt).g;
-            const float safe = stable_divisor(g);
-            const float uk = ((f[t][r] + bq[r]) - (hrq[r] * yt + hsq[r])) / safe;
-            const float wk = (al * uk) / safe;
+            const float wk = kl_cotangent(f[t][r] + bq[r], hrq[r] * yt + hsq[r], g, al);
             ap[t][r] = real_d(t) ? a[t][r] + wk : a[t][r];       // (a padded channel: g may be 0 there; no share)
           }
           store_tile(p.stash_a + slot * p.B * dT, t, ap[t] * dt);
@@ -345,12 +333,9 @@ __global__ void __launch_bounds__(NW * 64)
           }
           if constexpr (KL) {
             // the column's share (see MlpAdjKlArgs): u and w as the cotangent phase formed them
-            const float safe = stable_divisor(g);
-            const float uk = ((f[t][r] + bq[r]) - (hrq[r] * yt + hsq[r])) / safe;
-            const float wk = (al * uk) / safe;
             // a_l dt u^2 / safe: none where the divisor is clamped (d safe / d g = 0), none in a padded channel (g may be 0)
-            const float kq = (real_d(t) && fabsf(g) > 1e-7f) ? ((al * dt) * (uk * uk)) / safe : 0.0f;
-            const float dtw = real_d(t) ? dt * wk : 0.0f;
+            const KlShare kl = kl_share(f[t][r] + bq[r], hrq[r] * yt + hsq[r], g, al, dt, real_d(t));
+            const float kq = kl.kq, dtw = kl.dtw;
             a1 = a1 - (hrq[r] * dtw + kq * gp);
             to_shift -= kq * q;
             to_rate -= (kq * q) * yt;

@@ -25,6 +25,8 @@
 //    weight- and bias-gradient sums. Each block owns a contiguous K range and accumulates the whole M x N result in
 //    MFMA accumulators across its 8 waves, streaming both operands through a double-buffered LDS tile; per-block
 //    partials are written out and summed in a fixed order by the caller (deterministic, unlike atomics).
+#include <type_traits>
+
 #include "tsde_common.h"
 #include "tsde_launch.h"
 #include "tsde_mlp.h"
@@ -60,9 +62,37 @@ struct MlpBackArgs {
   const uint64_t* key_dev;
 };
 
+// The KL instantiation (`sdeint(..., logqp=True)` under autograd, the solve of tsde_trajectory_mlp_diag_logqp with a per-channel
+// affine prior drift h = hr * y + hs): the forward step also advanced the column l_{k+1} = l_k + 0.5 sum_i u_i^2 dt_k,
+// u = (f - h) / safe(g) at y_k. Its cotangent a_l = dL/dl_{k+1} is per row, gains the column's cotangent where an output
+// arrives (as lam gains grad_ys) and is otherwise constant: nothing depends on l. It reaches the rest of the step through
+// u -- f = W2 act(z) + b2 is needed again, a fourth product per step from the same LDS copy of W2 -- with (tsde_mlp.h:
+// kl_share) w = a_l u / safe per channel:
+//   the cotangent fed to the W2 product, and stashed for dL/dW2, dL/db2, is dt (lam + w) instead of dt lam
+//   dL/dy_k  += dt (-hr w - a_l u^2 g' / safe)                                  (g' = q c as in the diffusion terms)
+//   dL/dc    += -dt a_l (u^2 / safe) q y_k        dL/de += -dt a_l (u^2 / safe) q
+//   dL/dhr   += -dt w y_k                          dL/dhs += -dt w
+// The replaced divisor (|g| <= 1e-7) is a constant without a derivative. The column's diffusion is 0, so Milstein's own terms
+// are unchanged. The Brownian field has row stride d + 1 and any elem0: dW_k comes from normal4_straddle, as the forward kernel
+// draws it. The elementwise phase runs BEFORE the W2 product here (it forms that product's operand and then no longer needs f).
+struct MlpBackKlArgs : MlpBackArgs {
+  float* a_l;               // (B)  in: dL/dl at boundary k_hi (before that boundary's own cotangent); out: at k_lo
+  const float* grad_logqp;  // (n_grad, B) cotangents of the column at the outputs
+  const float* b2;          // (d)
+  const float *hr, *hs;     // (d) prior drift coefficients
+  float* row_hrate;         // (B, d)  += sum_k -dt w y_k   (all four sums of this instantiation: over the steps AND over each
+  float* row_hshift;        // (B, d)  += sum_k -dt w        aligned group of 16 rows, into row 16 k -- as the adjoint kernel's)
+  int64_t bm_stride;        // row stride of the Brownian field: d + 1
+};
+
 // FULL: d == D and h == H (no channel padding inside the kernel), which removes every per-tile bounds test.
-template <int D, int H, int ACT, int NW, bool FULL>
-__global__ void __launch_bounds__(NW * 64) mlp_backward_kernel(const MlpBackArgs p) {
+// KIND (KL only; the plain sweep keeps its uniform branches): which elementwise phase the instantiation holds -- with all of
+// them in one kernel behind uniform branches the register allocator spilled hundreds of dwords at every shape.
+constexpr int kKlEulerAffine = 0, kKlEulerSigmoid = 1, kKlMilsteinAffine = 2;
+
+template <int D, int H, int ACT, int NW, bool FULL, bool KL = false, int KIND = 0>
+__global__ void __launch_bounds__(NW * 64)
+    mlp_backward_kernel(const std::conditional_t<KL, MlpBackKlArgs, MlpBackArgs> p) {
   constexpr int R = 16;
   using TL = Tile<R>;
   constexpr int TD = D / R, TH = H / R, kThreads = NW * 64;
@@ -74,11 +104,23 @@ __global__ void __launch_bounds__(NW * 64) mlp_backward_kernel(const MlpBackArgs
   float* b1s = lds + L::b1(D, H);           // H
   float* cs = lds + L::vec(D, H, 0);        // D
   float* es = lds + L::vec(D, H, 1);        // D
+  [[maybe_unused]] float* b2s = lds + L::vec(D, H, 2);      // D  (KL)
+  [[maybe_unused]] float* hrs = lds + L::vec(D, H, 3);      // D  (KL) prior drift h = hr * y + hs
+  [[maybe_unused]] float* hss = lds + L::vec(D, H, 4);      // D  (KL)
+  [[maybe_unused]] float* sums = lds + L::vec(D, H, 5);     // NW x 4 x D  (KL) per wave: rate, shift, prior rate, prior shift
   const int dT = p.d, hT = p.h;
   stage_perceptron<D, H, R, kThreads>(lds, p.W1, p.W2, p.b1, dT, hT);
   for (int i = threadIdx.x; i < D; i += kThreads) {
     cs[i] = i < dT ? p.c[i] : 0.0f;
     es[i] = i < dT ? p.e[i] : 0.0f;
+    if constexpr (KL) {
+      b2s[i] = i < dT ? p.b2[i] : 0.0f;
+      hrs[i] = i < dT ? p.hr[i] : 0.0f;
+      hss[i] = i < dT ? p.hs[i] : 0.0f;
+    }
+  }
+  if constexpr (KL) {
+    for (int i = threadIdx.x; i < NW * 4 * D; i += kThreads) sums[i] = 0.0f;
   }
   __syncthreads();
 
@@ -96,6 +138,15 @@ __global__ void __launch_bounds__(NW * 64) mlp_backward_kernel(const MlpBackArgs
   // no per-tile 64-bit address lives in vector registers across the sweep (the caller keeps rows * width < 2^30).
   const uint32_t off_d = (uint32_t)(row * dT) + 4 * part, off_h = (uint32_t)(row * hT) + 4 * part;
   const uint64_t quad0 = (key.elem0 + (uint64_t)(row * dT) + 4 * part) >> 2;   // RNG quad of tile 0; tile t: + 4 t
+  // KL: the lane's first element of the field, quad-aligned on every fourth row only (normal4_straddle); a_l of its row
+  [[maybe_unused]] uint64_t elem0_lane = 0;
+  [[maybe_unused]] float al = 0.0f;
+  [[maybe_unused]] const float own_row = row0 + n < p.B ? 1.0f : 0.0f;   // (a shadow lane adds nothing to the wave's sums)
+  [[maybe_unused]] float* wave_sums = sums + wave * 4 * D;
+  if constexpr (KL) {
+    elem0_lane = key.elem0 + (uint64_t)row * (uint64_t)p.bm_stride + 4 * part;
+    al = p.a_l[row];
+  }
   auto real_d = [&](int t) { return FULL || R * t + 4 * part < dT; };
   auto real_h = [&](int th) { return FULL || R * th + 4 * part < hT; };
   auto load_tile = [&](const float* base, int t) {
@@ -110,12 +161,17 @@ __global__ void __launch_bounds__(NW * 64) mlp_backward_kernel(const MlpBackArgs
     if (real_h(th)) *reinterpret_cast<f32x4*>(base + off_h + R * th) = v;
   };
 
-  f32x4 lam[TD], acc_rate[TD], acc_shift[TD];
+  // (KL: no per-row accumulators -- with lam, y, f and act'(z) they do not fit 256 registers at d = hidden = 128 -- but sums
+  //  over the wave's 16 rows in LDS, as the adjoint kernel keeps them)
+  f32x4 lam[TD];
+  [[maybe_unused]] f32x4 acc_rate[KL ? 1 : TD], acc_shift[KL ? 1 : TD];
 #pragma unroll
   for (int t = 0; t < TD; ++t) {
     lam[t] = load_tile(p.lam, t);
-    acc_rate[t] = {0.0f, 0.0f, 0.0f, 0.0f};
-    acc_shift[t] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if constexpr (!KL) {
+      acc_rate[t] = {0.0f, 0.0f, 0.0f, 0.0f};
+      acc_shift[t] = {0.0f, 0.0f, 0.0f, 0.0f};
+    }
   }
 
   // y_k is loaded one step ahead (issued before the last product of the previous step, which does not read it): a
@@ -135,13 +191,22 @@ __global__ void __launch_bounds__(NW * 64) mlp_backward_kernel(const MlpBackArgs
 #pragma unroll
     for (int t = 0; t < TD; ++t) {
       if (arrives) lam[t] += load_tile(p.grad_ys + (int64_t)jg * p.B * dT, t);
-      store_tile(p.stash_lam + slot * p.B * dT, t, lam[t] * dt);
+      if constexpr (!KL) store_tile(p.stash_lam + slot * p.B * dT, t, lam[t] * dt);     // (KL: once f is known, below)
+    }
+    if constexpr (KL) {
+      if (arrives) al += p.grad_logqp[(int64_t)jg * p.B + row];
     }
     if (arrives) --jg;
     __builtin_amdgcn_sched_barrier(0);
 
     // ---- hidden layer: z^T = W1^T y^T; keep act'(z), stash act(z) ---------------------------------------------------
+    // (KL: f^T += W2^T act(z)^T as each tile of act(z) completes)
     f32x4 hid[TH];
+    [[maybe_unused]] f32x4 f[KL ? TD : 1];
+    if constexpr (KL) {
+#pragma unroll
+      for (int t = 0; t < TD; ++t) f[t] = {0.0f, 0.0f, 0.0f, 0.0f};
+    }
 #pragma unroll
     for (int th = 0; th < TH; ++th) {
       f32x4 z = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -163,10 +228,79 @@ __global__ void __launch_bounds__(NW * 64) mlp_backward_kernel(const MlpBackArgs
         hid[th][r] = slope;
       }
       store_hidden(p.stash_hid + slot * p.B * hT, th, value);
+      if constexpr (KL) {
+        // (padded hidden units: act(0 + 0) is not 0 for softplus, but their W2 rows are zero in LDS)
+#pragma unroll
+        for (int t = 0; t < TD; ++t) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) f[t] = TL::mfma(W2s[(R * th + 4 * part + r) * S2 + R * t + n], value[r], f[t]);
+        }
+        reads_ahead<2 * TD, 2>();
+      }
       __builtin_amdgcn_sched_barrier(0);
     }
 
+    // ---- KL: the whole elementwise phase, ahead of the W2 product: w from f, the operand lam + w of that product (it takes
+    //      f's registers), dt (lam + w) to the stash, then the diffusion terms and the column's own on lam and the sums ------
+    if constexpr (KL) {
+      constexpr bool kSigmoid = KIND == kKlEulerSigmoid;
+#pragma unroll
+      for (int t = 0; t < TD; ++t) {
+        const int ch = R * t + 4 * part;
+        float zn[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        uint64_t elem = elem0_lane + R * t;
+        asm volatile("" : "+v"(elem));            // (keeps the step-invariant first Philox round inside the sweep)
+        if (real_d(t)) normal4_straddle<float>(key, elem, cell, 0, kStreamW, zn);
+        const f32x4 yt = y[t];
+        const f32x4 cq = lds_quad(cs, ch), eq = lds_quad(es, ch), bq = lds_quad(b2s, ch);
+        const f32x4 hrq = lds_quad(hrs, ch), hsq = lds_quad(hss, ch);
+        float rate_terms[4], shift_terms[4], hrate_terms[4], hshift_terms[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float yy = yt[r], cc = cq[r], l = lam[t][r];
+          const DiffusionValue dv = diffusion_value(kSigmoid, p.diff_amp, cc, eq[r], yy);
+          const KlShare kl = kl_share(f[t][r] + bq[r], hrq[r] * yy + hsq[r], dv.g, al, dt, real_d(t));
+          f[t][r] = real_d(t) ? l + kl.w : l;
+          const float kqq = kl.kq * dv.q;                              // a_l dt (u^2 / safe) dg/de
+          const float w = zn[r] * sw;
+          float to_shift, to_rate, step;
+          if constexpr (KIND != kKlMilsteinAffine) {
+            const float lw = (l * w) * dv.q;
+            to_shift = lw;
+            to_rate = lw * yy;
+            step = lw * cc;
+          } else {
+            const float v = milstein_v<float>(w, dt, 0.5f, true);         // (the KL column is carried for Ito SDEs only)
+            const float cy = cc * yy;
+            to_shift = l * (w + cc * v);
+            to_rate = l * (yy * w + v * ((cy + eq[r]) + cy));
+            step = l * (cc * w + (cc * cc) * v);
+          }
+          shift_terms[r] = row_total((to_shift - kqq) * own_row);
+          rate_terms[r] = row_total((to_rate - kqq * yy) * own_row);
+          hshift_terms[r] = row_total(-kl.dtw * own_row);
+          hrate_terms[r] = row_total(-(kl.dtw * yy) * own_row);
+          lam[t][r] = l + (step - (hrq[r] * kl.dtw + kqq * cc));
+          asm volatile("" : "+v"(lam[t][r]), "+v"(f[t][r]));     // (materialised here, as in the adjoint kernel)
+        }
+        store_tile(p.stash_lam + slot * p.B * dT, t, f[t] * dt);
+        // summed over the 16 rows of the wave (the 16 lanes of a DPP row hold one channel quad of 16 rows); the row's last
+        // lane adds the totals to the wave's LDS accumulators (ds_add_f32: one lane per address, in order per wave)
+        if (n == R - 1 && real_d(t)) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            atomicAdd(&wave_sums[ch + r], rate_terms[r]);
+            atomicAdd(&wave_sums[D + ch + r], shift_terms[r]);
+            atomicAdd(&wave_sums[2 * D + ch + r], hrate_terms[r]);
+            atomicAdd(&wave_sums[3 * D + ch + r], hshift_terms[r]);
+          }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+
     // ---- u^T = W2 lam^T (rows of W2s, four consecutive channels per lane); delta = u * act'(z) * dt ----------------
+    // (KL: W2 (lam + w)^T)
 #pragma unroll
     for (int th = 0; th < TH; ++th) {
       f32x4 u = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -174,7 +308,10 @@ __global__ void __launch_bounds__(NW * 64) mlp_backward_kernel(const MlpBackArgs
       for (int t = 0; t < TD; ++t) {
         const f32x4 a = *reinterpret_cast<const f32x4*>(&W2s[(R * th + n) * S2 + R * t + 4 * part]);
 #pragma unroll
-        for (int r = 0; r < 4; ++r) u = TL::mfma(a[r], lam[t][r], u);
+        for (int r = 0; r < 4; ++r) {
+          if constexpr (KL) u = TL::mfma(a[r], f[t][r], u);
+          else u = TL::mfma(a[r], lam[t][r], u);
+        }
         if ((t + 1) % 4 == 0) __builtin_amdgcn_sched_barrier(0);
       }
       hid[th] = (u * hid[th]) * dt;
@@ -183,6 +320,7 @@ __global__ void __launch_bounds__(NW * 64) mlp_backward_kernel(const MlpBackArgs
     }
 
     // ---- diffusion: dW_k again from the counter RNG; lam <- lam + lam c dW ------------------------------------------
+    if constexpr (!KL) {
 #pragma unroll
     for (int t = 0; t < TD; ++t) {
       const int ch = R * t + 4 * part;
@@ -219,6 +357,7 @@ __global__ void __launch_bounds__(NW * 64) mlp_backward_kernel(const MlpBackArgs
       }
       __builtin_amdgcn_sched_barrier(0);
     }
+    }
 
     if (k > p.k_lo) {
 #pragma unroll
@@ -245,8 +384,20 @@ __global__ void __launch_bounds__(NW * 64) mlp_backward_kernel(const MlpBackArgs
 #pragma unroll
   for (int t = 0; t < TD; ++t) {
     store_tile(p.lam, t, lam[t]);
-    store_tile(p.row_rate, t, load_tile(p.row_rate, t) + acc_rate[t]);
-    store_tile(p.row_shift, t, load_tile(p.row_shift, t) + acc_shift[t]);
+    if constexpr (!KL) {
+      store_tile(p.row_rate, t, load_tile(p.row_rate, t) + acc_rate[t]);
+      store_tile(p.row_shift, t, load_tile(p.row_shift, t) + acc_shift[t]);
+    }
+  }
+  if constexpr (KL) {
+    if (part == 0) p.a_l[row] = al;
+    // the wave's sums join row `row0` of the four (B, d) arrays
+    for (int i = lane; i < dT; i += 64) {
+      p.row_rate[row0 * dT + i] += wave_sums[i];
+      p.row_shift[row0 * dT + i] += wave_sums[D + i];
+      p.row_hrate[row0 * dT + i] += wave_sums[2 * D + i];
+      p.row_hshift[row0 * dT + i] += wave_sums[3 * D + i];
+    }
   }
 }
 
@@ -260,15 +411,30 @@ struct MlpBackwardPolicy {
   }
 };
 
-hipError_t launch_trajectory_mlp_diag_backward(void* lam, void* stash_lam, void* stash_hid, void* stash_delta,
-                                               void* row_rate, void* row_shift, const void* ys_all,
-                                               int32_t ys_first, const void* grad_ys, const int32_t* grad_step, int32_t grad_last,
-                                               int64_t rows, int64_t d, int64_t h, const void* W1, const void* b1,
-                                               const void* W2, const void* c, const void* e, int diff_kind,
-                                               double diff_amp, int act, int method, const tsde_traj_t* tr,
-                                               int32_t k_lo, int32_t k_hi, NoiseKey key, const uint64_t* key_dev,
-                                               hipStream_t s) {
-  MlpBackArgs p;
+// The KL instantiation. With per-row register accumulators for its four sums (7 D/4 + H/4 live registers per lane) the
+// d = hidden = 128 shape spilled 470 dwords as an 8-wave block and still 28 as a 4-wave block; with the sums in LDS (lam, y,
+// f / lam + w and act'(z): 3 D/4 + H/4) and one elementwise phase per instantiation (KIND) every shape runs as 8-wave blocks
+// without a spilled vector register and without scratch (profiles/logqp_backprop_resource_usage_new.txt: 235 registers at
+// d = hidden = 128).
+struct MlpBackwardKlPolicy {
+  template <int D, int H, int ACT, bool FULL>
+  static hipError_t launch(const MlpBackKlArgs& p, hipStream_t s) {
+    constexpr int NW = 8;
+    constexpr size_t lds_bytes = MlpLds<16>::bytes(D, H, 5, NW * 4 * D);
+    if (p.method != TSDE_TRAJ_EULER)
+      return launch_rows_per_wave<mlp_backward_kernel<D, H, ACT, NW, FULL, true, kKlMilsteinAffine>, NW, 16>(p, lds_bytes, s);
+    if (p.diff_kind == TSDE_DIFF_SIGMOID)
+      return launch_rows_per_wave<mlp_backward_kernel<D, H, ACT, NW, FULL, true, kKlEulerSigmoid>, NW, 16>(p, lds_bytes, s);
+    return launch_rows_per_wave<mlp_backward_kernel<D, H, ACT, NW, FULL, true, kKlEulerAffine>, NW, 16>(p, lds_bytes, s);
+  }
+};
+
+static void fill_back_args(MlpBackArgs& p, void* lam, void* stash_lam, void* stash_hid, void* stash_delta, void* row_rate,
+                           void* row_shift, const void* ys_all, int32_t ys_first, const void* grad_ys,
+                           const int32_t* grad_step, int32_t grad_last, int64_t rows, int64_t d, int64_t h, const void* W1,
+                           const void* b1, const void* W2, const void* c, const void* e, int diff_kind, double diff_amp,
+                           int method, const tsde_traj_t* tr, int32_t k_lo, int32_t k_hi, NoiseKey key,
+                           const uint64_t* key_dev) {
   fill_mlp_core(p, rows, d, h, W1, b1, W2, c, e, diff_kind, diff_amp, tr, key, key_dev);
   p.lam = (float*)lam;
   p.stash_lam = (float*)stash_lam;
@@ -284,8 +450,46 @@ hipError_t launch_trajectory_mlp_diag_backward(void* lam, void* stash_lam, void*
   p.method = method;
   p.k_lo = k_lo;
   p.k_hi = k_hi;
+}
+
+hipError_t launch_trajectory_mlp_diag_backward(void* lam, void* stash_lam, void* stash_hid, void* stash_delta,
+                                               void* row_rate, void* row_shift, const void* ys_all,
+                                               int32_t ys_first, const void* grad_ys, const int32_t* grad_step, int32_t grad_last,
+                                               int64_t rows, int64_t d, int64_t h, const void* W1, const void* b1,
+                                               const void* W2, const void* c, const void* e, int diff_kind,
+                                               double diff_amp, int act, int method, const tsde_traj_t* tr,
+                                               int32_t k_lo, int32_t k_hi, NoiseKey key, const uint64_t* key_dev,
+                                               hipStream_t s) {
+  MlpBackArgs p;
+  fill_back_args(p, lam, stash_lam, stash_hid, stash_delta, row_rate, row_shift, ys_all, ys_first, grad_ys, grad_step,
+                 grad_last, rows, d, h, W1, b1, W2, c, e, diff_kind, diff_amp, method, tr, k_lo, k_hi, key, key_dev);
   if (rows <= 0 || k_hi <= k_lo) return hipSuccess;
   return mlp_ladder<MlpBackwardPolicy>(p, act, s);
+}
+
+hipError_t launch_trajectory_mlp_diag_logqp_backward(void* lam, void* a_l, void* stash_lam, void* stash_hid,
+                                                     void* stash_delta, void* row_rate, void* row_shift, void* row_hrate,
+                                                     void* row_hshift, const void* ys_all, int32_t ys_first,
+                                                     const void* grad_ys, const void* grad_logqp, const int32_t* grad_step,
+                                                     int32_t grad_last, int64_t rows, int64_t d, int64_t h, const void* W1,
+                                                     const void* b1, const void* W2, const void* b2, const void* c,
+                                                     const void* e, const void* hr, const void* hs, int diff_kind,
+                                                     double diff_amp, int act, int method, const tsde_traj_t* tr,
+                                                     int32_t k_lo, int32_t k_hi, int64_t bm_stride, NoiseKey key,
+                                                     const uint64_t* key_dev, hipStream_t s) {
+  MlpBackKlArgs p;
+  fill_back_args(p, lam, stash_lam, stash_hid, stash_delta, row_rate, row_shift, ys_all, ys_first, grad_ys, grad_step,
+                 grad_last, rows, d, h, W1, b1, W2, c, e, diff_kind, diff_amp, method, tr, k_lo, k_hi, key, key_dev);
+  p.a_l = (float*)a_l;
+  p.grad_logqp = (const float*)grad_logqp;
+  p.b2 = (const float*)b2;
+  p.hr = (const float*)hr;
+  p.hs = (const float*)hs;
+  p.row_hrate = (float*)row_hrate;
+  p.row_hshift = (float*)row_hshift;
+  p.bm_stride = bm_stride;
+  if (rows <= 0 || k_hi <= k_lo) return hipSuccess;
+  return mlp_ladder<MlpBackwardKlPolicy>(p, act, s);
 }
 
 // ---- C = A^T B (and the column sums of A) over a tall K --------------------------------------------------------------

@@ -294,6 +294,16 @@ hipError_t launch_trajectory_mlp_diag_backward(void* lam, void* stash_lam, void*
                                                double diff_amp, int act, int method, const tsde_traj_t* tr,
                                                int32_t k_lo, int32_t k_hi, NoiseKey key, const uint64_t* key_dev,
                                                hipStream_t s);
+hipError_t launch_trajectory_mlp_diag_logqp_backward(void* lam, void* a_l, void* stash_lam, void* stash_hid,
+                                                     void* stash_delta, void* row_rate, void* row_shift, void* row_hrate,
+                                                     void* row_hshift, const void* ys_all, int32_t ys_first,
+                                                     const void* grad_ys, const void* grad_logqp, const int32_t* grad_step,
+                                                     int32_t grad_last, int64_t rows, int64_t d, int64_t h, const void* W1,
+                                                     const void* b1, const void* W2, const void* b2, const void* c,
+                                                     const void* e, const void* hr, const void* hs, int diff_kind,
+                                                     double diff_amp, int act, int method, const tsde_traj_t* tr,
+                                                     int32_t k_lo, int32_t k_hi, int64_t bm_stride, NoiseKey key,
+                                                     const uint64_t* key_dev, hipStream_t s);
 // mlp_adjoint.hip
 hipError_t launch_adjoint_mlp_diag(void* y, void* a, void* stash_a, void* stash_hid, void* stash_delta, void* stash_y,
                                    void* row_rate, void* row_shift, int64_t rows, int64_t d, int64_t h, const void* W1,

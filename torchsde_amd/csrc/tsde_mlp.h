@@ -118,6 +118,43 @@ TSDE_D float stable_divisor(float g) {
   return fabsf(g) > 1e-7f ? g : 1e-7f * sign;
 }
 
+// Sum of `v` over the 16 lanes of a DPP row, valid in the row's last lane (inclusive scan by row_shr 1, 2, 4, 8; lanes
+// shifted in from outside the row read 0).
+TSDE_D float row_total(float v) {
+  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x111, 0xf, 0xf, true));
+  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x112, 0xf, 0xf, true));
+  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x114, 0xf, 0xf, true));
+  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x118, 0xf, 0xf, true));
+  return v;
+}
+
+// What the KL column l (l' = 0.5 sum_i u_i^2, u = (f - h) / safe(g)) hands back to one channel of a reverse step, given the
+// column's cotangent a_l -- the stochastic adjoint (mlp_adjoint.hip) and back-propagation through the solver
+// (mlp_backward.hip) use the same three numbers:
+//   w   = a_l u / safe                 the drift network sees its cotangent + w; the prior's h = hr y + hs sees -w
+//   dtw = dt w                         dL/dy += -hr dtw;  dL/dhr += -dtw y;  dL/dhs += -dtw
+//   kq  = a_l dt u^2 / safe            dL/dy += -kq g';   dL/dtheta_g += -kq dg/dtheta
+// The replaced divisor is a constant (no kq where |g| <= 1e-7); a padded channel (`real` false: g may be 0 there) has no share
+// in dtw and kq, and its w is the caller's to drop.
+struct KlShare {
+  float w, dtw, kq;
+};
+TSDE_D float kl_cotangent(float f, float h, float g, float al) {
+  const float safe = stable_divisor(g);
+  const float uk = (f - h) / safe;
+  return (al * uk) / safe;
+}
+TSDE_D KlShare kl_share(float f, float h, float g, float al, float dt, bool real) {
+  const float safe = stable_divisor(g);
+  const float uk = (f - h) / safe;
+  const float wk = (al * uk) / safe;
+  KlShare s;
+  s.w = wk;
+  s.kq = (real && fabsf(g) > 1e-7f) ? ((al * dt) * (uk * uk)) / safe : 0.0f;
+  s.dtw = real ? dt * wk : 0.0f;
+  return s;
+}
+
 // ---- drift and diffusion perceptrons: mlp_general.hip, tsde_neural_rheun.h ------------------------------------------------
 
 // One normal of the field, out of line: the element-by-element paths (d % 4 != 0, m not a tile width, an unaligned field) are

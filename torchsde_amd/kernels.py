@@ -1398,6 +1398,127 @@ def trajectory_mlp_diag_differentiable(y0, module_params, activation, diffusion,
                                   bm, y0, *module_params)
 
 
+def assemble_logqp_output(states, column, l0):
+    """The (T, rows, d + 1) tensor `contract.parse_return` splits, from the states (T, rows, d) at the outputs (the first: y0),
+    the KL column's increase since t0 at the outputs after the first (T - 1, rows), and the column's start `l0` (rows)."""
+    d = states.shape[2]
+    ys = torch.empty(states.shape[:2] + (d + 1,), dtype=states.dtype, device=states.device)
+    ys[:, :, :d].copy_(states)
+    ys[0, :, d].copy_(l0)
+    torch.add(column, l0, out=ys[1:, :, d])
+    return ys
+
+
+class _MlpLogqpTrajectoryFn(torch.autograd.Function):
+    """`_MlpTrajectoryFn` for ``sdeint(..., logqp=True)``: the state has the KL column l as its last column
+    (contract.check_contract), the prior drift is h = hr * y + hs (mlp_adjoint.plan_logqp_sdeint). Forward: the KL instantiation
+    of the sampling kernel on the every-step schedule (states and column at every boundary). Backward: the KL instantiation of
+    the reverse sweep over chunks of steps, last first, each followed by the two weight-gradient products over its stash.
+
+    Over the `STATE_BYTES` budget the forward launch keeps the states at chunk boundaries (and outputs) only, and the backward
+    pass re-runs the KL sampling kernel over each chunk: the plain one cannot read a Brownian field of row stride d + 1.
+
+    Inputs after `y0`: the module's six perceptron / diffusion tensors; `hr_t`, `hs_t`, which carry the user's graph from the
+    prior's own parameters (recognise.prior_coefficient_graph) and receive dL/dhr, dL/dhs; the coefficient VALUES the kernels
+    take (detached). No double-backward path: a backward pass that builds a graph raises."""
+
+    N_PLAIN = 6                # arguments before y0
+    STASH_BYTES = 3 << 30      # per-chunk stash of the reverse sweep (three (steps, rows, width) float32 arrays)
+    STATE_BYTES = None         # budget for the state of every step; None = half of the device memory free at forward time
+
+    @staticmethod
+    def _chunk(n_steps, rows, d, hidden):
+        return PerceptronGradients.chunk_length(n_steps, rows, d + 2 * hidden, _MlpLogqpTrajectoryFn.STASH_BYTES)
+
+    @staticmethod
+    def forward(ctx, activation, diffusion, method, schedule_all, out_steps, bm, y0, w1, b1, w2, b2, rate, shift, hr_t, hs_t,
+                hr, hs):
+        from .mlp_adjoint import trajectory_mlp_diag_logqp
+        rows, d = y0.shape[0], y0.shape[1] - 1
+        hidden, n_steps = b1.numel(), schedule_all.n_steps
+        y0d = y0.detach()
+        net = PerceptronGradients.prepare(d, w1, b1, w2, b2, rate, shift)
+        budget = _MlpLogqpTrajectoryFn.STATE_BYTES
+        if budget is None:
+            budget = torch.cuda.mem_get_info(y0.device)[0] // 2
+        if (n_steps + 1) * rows * (d + 1) * 4 <= budget:
+            kept_at = None                                  # states[k] is the state at boundary k
+            schedule = schedule_all
+        else:
+            chunk = _MlpLogqpTrajectoryFn._chunk(n_steps, rows, d, hidden)
+            marks = sorted(set(range(n_steps, 0, -chunk)) | set(out_steps))
+            kept_at = {0: 0}
+            kept_at.update((k, i + 1) for i, k in enumerate(marks))
+            schedule = TrajectorySchedule.cached(schedule_all.host_rows, schedule_all.host_cells, marks,
+                                                 [(0.0, 1.0)] * len(marks), y0.device, y0.dtype)
+        states = torch.empty((schedule.n_out + 1, rows, d), dtype=y0.dtype, device=y0.device)
+        states[0].copy_(y0d[:, :d])
+        column = torch.empty((schedule.n_out, rows), dtype=y0.dtype, device=y0.device)
+        trajectory_mlp_diag_logqp(states[1:], column, states[0], *net, hr, hs, activation, diffusion, method, schedule, bm)
+        ctx.grad_step = _boundary_table(out_steps, y0.device)
+        ctx.save_for_backward(states, *net, hr, hs)
+        ctx.method, ctx.activation, ctx.hidden = int(method), int(activation), hidden
+        ctx.diffusion = (int(diffusion[0]), float(diffusion[1]))
+        ctx.schedule, ctx.bm, ctx.out_steps, ctx.kept_at = schedule_all, bm, out_steps, kept_at
+        ctx.param_shapes = (tuple(rate.shape), tuple(shift.shape))
+        # (stacks of views, not index_select: see _MlpTrajectoryFn.forward)
+        at = [k if kept_at is None else kept_at[k] for k in out_steps]
+        out_states = torch.stack([states[0]] + [states[i] for i in at], dim=0)
+        return assemble_logqp_output(out_states, torch.stack([column[i - 1] for i in at], dim=0), y0d[:, d])
+
+    @staticmethod
+    def backward(ctx, gys):
+        from .mlp_adjoint import trajectory_mlp_diag_logqp
+        if torch.is_grad_enabled():    # create_graph=True: the kernels below leave no graph, and none is prepared for this route
+            raise NotImplementedError("torchsde_amd: no differentiable backward pass was prepared for this call.")
+        states, w1_in, b1c, w2_in, b2c, rate, shift, hr, hs = ctx.saved_tensors
+        rows, d = states.shape[1], states.shape[2]
+        hidden, schedule, kept_at, bm = ctx.hidden, ctx.schedule, ctx.kept_at, ctx.bm
+        n_steps = schedule.n_steps
+        dev = states.device
+        g_state = gys[:, :, :d].contiguous()
+        g_column = gys[:, :, d].contiguous()
+        boundaries = np.asarray([0] + list(ctx.out_steps), dtype=np.int32)
+        chunk = _MlpLogqpTrajectoryFn._chunk(n_steps, rows, d, hidden)
+        sums = PerceptronGradients(rows, d, hidden, dev)
+        stash_lam, stash_hid, stash_delta = sums.stashes(chunk, (d, hidden, hidden))
+        rerun = rerun_column = None
+        if kept_at is not None:
+            rerun = torch.empty((chunk + 1, rows, d), dtype=torch.float32, device=dev)
+            rerun_column = torch.empty((chunk, rows), dtype=torch.float32, device=dev)
+        lam = torch.zeros((rows, d), dtype=torch.float32, device=dev)
+        a_l = torch.zeros(rows, dtype=torch.float32, device=dev)
+        row_sums = tuple(torch.zeros((rows, d), dtype=torch.float32, device=dev) for _ in range(4))
+        lib, dt_code, stream = _launch_env(states)
+        for k_hi in range(n_steps, 0, -chunk):
+            k_lo = max(0, k_hi - chunk)
+            n = k_hi - k_lo
+            if kept_at is None:
+                ys, ys_first = states, 0
+            else:                                   # the states of this chunk again, from the state kept at its start
+                rerun[0].copy_(states[kept_at[k_lo]])
+                trajectory_mlp_diag_logqp(rerun[1:n + 1], rerun_column[:n], rerun[0], w1_in, b1c, w2_in, b2c, rate, shift, hr,
+                                          hs, ctx.activation, ctx.diffusion, ctx.method, schedule.window(k_lo, k_hi), bm)
+                ys, ys_first = rerun, k_lo
+            grad_last = int(np.searchsorted(boundaries, k_hi, side="right")) - 1
+            code = lib.tsde_trajectory_mlp_diag_logqp_backward(
+                lam.data_ptr(), a_l.data_ptr(), stash_lam.data_ptr(), stash_hid.data_ptr(), stash_delta.data_ptr(),
+                *(t.data_ptr() for t in row_sums), ys.data_ptr(), ys_first, g_state.data_ptr(), g_column.data_ptr(),
+                ctx.grad_step.data_ptr(), grad_last, rows, d, hidden, w1_in.data_ptr(), b1c.data_ptr(), w2_in.data_ptr(),
+                b2c.data_ptr(), rate.data_ptr(), shift.data_ptr(), hr.data_ptr(), hs.data_ptr(), ctx.diffusion[0],
+                ctx.diffusion[1], ctx.activation, ctx.method, d + 1,
+                *_native.sweep_tail(schedule, k_lo, k_hi, bm, dt_code, stream))
+            _native.check(code, "tsde_trajectory_mlp_diag_logqp_backward")
+            sums.accumulate(n, stash_lam, stash_hid, stash_delta, ys[k_lo - ys_first:k_hi - ys_first])
+        grad_y0 = None
+        if ctx.needs_input_grad[_MlpLogqpTrajectoryFn.N_PLAIN]:
+            grad_y0 = torch.cat((lam + g_state[0], (a_l + g_column[0]).unsqueeze(1)), dim=1)
+        diffusion = PerceptronGradients.diffusion_gradients(row_sums[:2], ctx.param_shapes)
+        return ((None,) * _MlpLogqpTrajectoryFn.N_PLAIN
+                + (grad_y0, sums.g_w1, sums.g_b1, sums.g_w2, sums.g_b2, *diffusion, row_sums[2].sum(dim=0),
+                   row_sums[3].sum(dim=0), None, None))
+
+
 # ---- in-library event timing (bench.py's roofline) ----------------------------------------------------------
 def prof_begin(kid, capacity):
     _native.check(_native.load().tsde_prof_begin(kid, capacity), "tsde_prof_begin")

@@ -15,6 +15,10 @@ route for every other module, method and grid, and the parity reference for this
 two kernels (``tsde_trajectory_mlp_diag_logqp``, ``tsde_adjoint_mlp_diag_logqp``) when the prior drift is per-channel affine
 in y and does not read t: `plan_logqp`, `_MlpLogqpAdjointFn`. The row sum of the column is an f32 sum in the kernel's own
 order, so this route agrees with the stepwise one to rounding, not bit for bit.
+
+``sdeint(..., logqp=True)`` on the same module takes the same sampling kernel and, under autograd, the KL instantiation of
+the reverse sweep (``tsde_trajectory_mlp_diag_logqp_backward``, `kernels._MlpLogqpTrajectoryFn`): `plan_logqp_sdeint`,
+`LogqpSdeintRoute`. What the two planners share is `_logqp_frame`.
 """
 import torch
 
@@ -278,27 +282,63 @@ class LogqpRoute:
         return verdict
 
 
-def plan_logqp(sde, y0, ts, bm, method, adjoint_method, dt, adaptive, adjoint_adaptive, options, adjoint_options,
-               adjoint_params, extra_solver_state, solver):
-    """The `LogqpRoute` of ``sdeint_adjoint(sde, y0, ts, logqp=True)`` if the call can take the KL kernels, else None (it stays
-    on the stepwise stochastic adjoint). `sde` is ``ForwardSDE(SDELogqp([RenameMethodsSDE(] module [)]))`` and `y0` carries
-    the extra column (contract.check_contract). Conditions: everything `route` asks of the module -- an Ito SDE with diagonal
-    noise, drift ``lin2(act(lin1(y)))``, affine or sigmoid elementwise diffusion, the shape limits --, Euler or Milstein both
-    ways, outputs on step boundaries, a prior drift that is per-channel affine in y and does not read t
-    (recognise.recognise_prior), `adjoint_params` exactly the module's trainable parameters. `solver.recognised_perceptron`
-    cannot verify this call (its forward solve has a (B, d) state against a (B, d + 1) Brownian motion), so trust is earned
-    here as on the reversible-Heun route: the first solve of a (form, batch size, "logqp") on an SDE object runs BOTH routes,
-    returns the stepwise result and files the verdict of `solvers._both_routes_agree` -- values of ys and of the column,
-    gradients for y0 and every parameter. TSDE_VERIFY_EVERY applies; no verifying solve runs under stream capture."""
+class _LogqpFrame:
+    """What `plan_logqp` (``sdeint_adjoint``) and `plan_logqp_sdeint` (``sdeint``) both need of a ``logqp=True`` call on the
+    perceptron-drift module: the unwrapped module, its interpretation (`found`, `spec`, `own`: the six tensors), the prior's
+    coefficients (`hr`, `hs`), the module's other trainable parameters (`prior_params`), the ledger, and grid and steps."""
+
+    def shape_of(self, c):
+        return "number" if isinstance(c, (bool, int, float)) else tuple(c.shape)
+
+    def prior_vectors(self, y0):
+        from . import recognise
+        return (recognise.prior_vector(self.hr, self.d, y0.dtype, y0.device),
+                recognise.prior_vector(self.hs, self.d, y0.dtype, y0.device))
+
+    def verdict(self, key, y0):
+        """(verdict, reverify) of this solve of `key`, or None where the route declines: a form that was refused, or -- ahead
+        of a verifying solve -- a stream capture, a second interpretation on a probe of another height that finds other forms
+        or other tensors, calls that touch the object's Python-side state or a random generator."""
+        from . import recognise
+        ledger, d = self.ledger, self.d
+        verdict, reverify = ledger.verdict(key)
+        if verdict is not None and verdict is not True:
+            return None
+        if verdict is None:
+            if torch.cuda.is_current_stream_capturing():
+                return None
+            snapshot = ledger.snapshot(y0.device)
+            if snapshot[0] is None:
+                return None
+            try:
+                again, again_spec, (hr5, hs5) = self.interpret(rows=5)
+            except recognise.NotElementwise as e:
+                return ledger.refuse(str(e))
+            own5 = again.perceptron_parameters()
+            same = (again.structure() == self.found.structure() and again_spec[-2:] == self.spec[-2:] and own5 is not None
+                    and all(x is y or (not x.requires_grad and torch.equal(x, y)) for x, y in zip(own5, self.own))
+                    and all(self.shape_of(x) == self.shape_of(y)
+                            and bool((recognise.prior_vector(x, d, y0.dtype, y0.device)
+                                      == recognise.prior_vector(y, d, y0.dtype, y0.device)).all())
+                            for x, y in ((self.hr, hr5), (self.hs, hs5))))
+            if not same:
+                ledger.file(key, "two interpretations of the same code (probes of 2 and 5 rows) found different forms", reverify)
+                return None
+            side_effect = ledger.side_effect(snapshot, y0.device)
+            if side_effect is not None:
+                return ledger.refuse(side_effect)
+        return verdict, reverify
+
+
+def _logqp_frame(sde, y0, ts, bm, dt, solver):
+    """The `_LogqpFrame` of a ``logqp=True`` call, or None where no KL kernel can take it. `sde` is
+    ``ForwardSDE(SDELogqp([RenameMethodsSDE(] module [)]))`` and `y0` carries the extra column (contract.check_contract).
+    Conditions: an Ito SDE with diagonal noise, drift ``lin2(act(lin1(y)))``, affine or sigmoid elementwise diffusion, the shape
+    limits, this package's BrownianInterval in float32 with d + 1 columns, a fixed-step grid on its cells, a prior drift that
+    is per-channel affine in y and does not read t (recognise.recognise_prior)."""
     from . import recognise, trust
     from .sde import ForwardSDE, RenameMethodsSDE, SDELogqp
     from .settings import NOISE_TYPES
-    if (adaptive or adjoint_adaptive or extra_solver_state is not None or adjoint_method not in _BACKWARD_KINDS
-            or method not in (METHODS.euler, METHODS.milstein)
-            or adjoint_options.get(METHOD_OPTIONS.grad_free, False) or options.get(METHOD_OPTIONS.grad_free, False)
-            or not options.get("trajectory_kernel", True) or not adjoint_options.get("trajectory_kernel", True)
-            or not recognise.ENABLED or solver is None):
-        return None
     wrapped = getattr(sde, "_base_sde", None)
     if (type(sde) is not ForwardSDE or type(wrapped) is not SDELogqp or sde.sde_type != SDE_TYPES.ito
             or sde.noise_type != NOISE_TYPES.diagonal or sde.user_product):
@@ -307,7 +347,6 @@ def plan_logqp(sde, y0, ts, bm, method, adjoint_method, dt, adaptive, adjoint_ad
     module = inner._base_sde if type(inner) is RenameMethodsSDE else inner
     if not isinstance(module, torch.nn.Module) or hasattr(module, "_base_sde") or not hasattr(inner, "h"):
         return None
-    code = _FORWARD_CODES[(method, SDE_TYPES.ito)]
     if (not isinstance(bm, BrownianInterval) or bm._rootW is not None or bm._rootH is not None or bm._snap or y0.dim() != 2
             or not y0.is_cuda or y0.shape[1] < 2 or tuple(bm.shape) != tuple(y0.shape) or y0.dtype != torch.float32
             or bm.dtype != torch.float32 or ts.dtype != y0.dtype or y0.numel() == 0):
@@ -340,64 +379,162 @@ def plan_logqp(sde, y0, ts, bm, method, adjoint_method, dt, adaptive, adjoint_ad
     module_params = list(module.parameters())
     module_ids = {id(p) for p in module_params}
     own_ids = {id(p) for p in own}
-    if ({id(p) for p in adjoint_params} != {id(p) for p in module_params if p.requires_grad}
-            or any(p.requires_grad and id(p) not in module_ids for p in own)
+    if (any(p.requires_grad and id(p) not in module_ids for p in own)
             or hidden % 4 != 0 or y0.shape[0] * (max(d, hidden) + 1) >= 2 ** 30):
         return None
-    prior_params = [p for p in module_params if id(p) not in own_ids and p.requires_grad]
-
-    # ---- grids: every output on a forward step boundary, every backward step exactly one forward cell ------------------
     ts_host = timegrid.ts_to_host(ts)
     grid = timegrid.build(ts_host, dt)
-    if grid.n_steps == 0 or any(not (w0 == 0.0 and w1 == 1.0) for (_, _, w0, w1) in grid.outputs):
+    if grid.n_steps == 0:
         return None
     steps = K.solve_steps(grid, bm)
     if steps is None:
         return None
-    backward_dt = K.backward_step_sizes(bm, ts_host, dt, steps.cells, steps.out_step)
+    frame = _LogqpFrame()
+    frame.inner, frame.module, frame.d, frame.hidden, frame.ledger, frame.interpret = inner, module, d, hidden, ledger, interpret
+    frame.found, frame.spec, frame.own, frame.hr, frame.hs = found, spec, own, hr, hs
+    frame.module_params = module_params
+    frame.prior_params = [p for p in module_params if id(p) not in own_ids and p.requires_grad]
+    frame.ts_host, frame.grid, frame.steps, frame.t0 = ts_host, grid, steps, ts[0]
+    return frame
+
+
+def plan_logqp(sde, y0, ts, bm, method, adjoint_method, dt, adaptive, adjoint_adaptive, options, adjoint_options,
+               adjoint_params, extra_solver_state, solver):
+    """The `LogqpRoute` of ``sdeint_adjoint(sde, y0, ts, logqp=True)`` if the call can take the KL kernels, else None (it stays
+    on the stepwise stochastic adjoint). Conditions: everything `_logqp_frame` asks, Euler or Milstein both ways, outputs on
+    step boundaries, `adjoint_params` exactly the module's trainable parameters. `solver.recognised_perceptron`
+    cannot verify this call (its forward solve has a (B, d) state against a (B, d + 1) Brownian motion), so trust is earned
+    here as on the reversible-Heun route: the first solve of a (form, batch size, "logqp") on an SDE object runs BOTH routes,
+    returns the stepwise result and files the verdict of `solvers._both_routes_agree` -- values of ys and of the column,
+    gradients for y0 and every parameter. TSDE_VERIFY_EVERY applies; no verifying solve runs under stream capture."""
+    from . import recognise
+    if (adaptive or adjoint_adaptive or extra_solver_state is not None or adjoint_method not in _BACKWARD_KINDS
+            or method not in (METHODS.euler, METHODS.milstein)
+            or adjoint_options.get(METHOD_OPTIONS.grad_free, False) or options.get(METHOD_OPTIONS.grad_free, False)
+            or not options.get("trajectory_kernel", True) or not adjoint_options.get("trajectory_kernel", True)
+            or not recognise.ENABLED or solver is None):
+        return None
+    frame = _logqp_frame(sde, y0, ts, bm, dt, solver)
+    if frame is None:
+        return None
+    code = _FORWARD_CODES[(method, SDE_TYPES.ito)]
+    if {id(p) for p in adjoint_params} != {id(p) for p in frame.module_params if p.requires_grad}:
+        return None
+    # ---- grids: every output on a forward step boundary, every backward step exactly one forward cell ------------------
+    steps = frame.steps
+    if any(not (w0 == 0.0 and w1 == 1.0) for (_, _, w0, w1) in frame.grid.outputs):
+        return None
+    backward_dt = K.backward_step_sizes(bm, frame.ts_host, dt, steps.cells, steps.out_step)
     if backward_dt is None:
         return None
-
-    def shape_of(c):
-        return "number" if isinstance(c, (bool, int, float)) else tuple(c.shape)
-
-    key = ledger.key(found, y0, "logqp", method, adjoint_method, shape_of(hr), shape_of(hs))
-    verdict, reverify = ledger.verdict(key)
-    if verdict is not None and verdict is not True:
+    ledger, spec, own = frame.ledger, frame.spec, frame.own
+    key = ledger.key(frame.found, y0, "logqp", method, adjoint_method, frame.shape_of(frame.hr), frame.shape_of(frame.hs))
+    decided = frame.verdict(key, y0)
+    if decided is None:
         return None
-    if verdict is None:
-        # the verifying solve: a second interpretation on a probe of another height must find the same forms over the same
-        # tensors, and the calls must leave the object's Python-side state and the random generators alone
-        if torch.cuda.is_current_stream_capturing():
-            return None
-        snapshot = ledger.snapshot(y0.device)
-        if snapshot[0] is None:
-            return None
-        try:
-            again, again_spec, (hr5, hs5) = interpret(rows=5)
-        except recognise.NotElementwise as e:
-            return ledger.refuse(str(e))
-        own5 = again.perceptron_parameters()
-        same = (again.structure() == found.structure() and again_spec[-2:] == spec[-2:] and own5 is not None
-                and all(x is y or (not x.requires_grad and torch.equal(x, y)) for x, y in zip(own5, own))
-                and all(shape_of(x) == shape_of(y) and bool((recognise.prior_vector(x, d, y0.dtype, y0.device)
-                                                             == recognise.prior_vector(y, d, y0.dtype, y0.device)).all())
-                        for x, y in ((hr, hr5), (hs, hs5))))
-        if not same:
-            ledger.file(key, "two interpretations of the same code (probes of 2 and 5 rows) found different forms", reverify)
-            return None
-        side_effect = ledger.side_effect(snapshot, y0.device)
-        if side_effect is not None:
-            return ledger.refuse(side_effect)
+    verdict, reverify = decided
     schedule = steps.schedule(y0.device, y0.dtype)
     backward_schedule = steps.schedule(y0.device, y0.dtype, dt=backward_dt)
     args = (spec[-2], tuple(spec[-1]), code, _BACKWARD_KINDS[adjoint_method], schedule, backward_schedule,
             tuple(int(k) for k in steps.out_step), bm)
-    plan = LogqpRoute(solver, args, own, prior_params, (sde, ts_host, dt, list(own) + prior_params), ledger, key,
-                      verdict is True, reverify)
-    plan.prior = (inner, ts[0], d, recognise.prior_vector(hr, d, y0.dtype, y0.device),
-                  recognise.prior_vector(hs, d, y0.dtype, y0.device))
+    plan = LogqpRoute(solver, args, own, frame.prior_params, (sde, frame.ts_host, dt, list(own) + frame.prior_params), ledger,
+                      key, verdict is True, reverify)
+    plan.prior = (frame.inner, frame.t0, frame.d) + frame.prior_vectors(y0)
     return plan
+
+
+class LogqpSdeintRoute:
+    """One ``sdeint(..., logqp=True)`` call's plan on the KL kernels (`plan_logqp_sdeint`), the interface of `LogqpRoute`.
+    With autograd recording: `kernels._MlpLogqpTrajectoryFn` (the KL sampling kernel at every step, then the KL reverse
+    sweep); without: one launch of the KL sampling kernel."""
+
+    def __init__(self, solver, frame, args, recording, ledger, key, trusted, reverify):
+        self.solver, self.frame, self.args, self.recording = solver, frame, args, recording
+        self.ledger, self.key, self.trusted, self.reverify = ledger, key, trusted, reverify
+
+    def solve(self, y0, z_holder=None):
+        from . import recognise
+        frame = self.frame
+        hr, hs = frame.prior_vectors(y0)
+        if self.recording:
+            hr_t, hs_t = recognise.prior_coefficient_graph(frame.inner.h, frame.t0, frame.d, y0.dtype, y0.device)
+            return K._MlpLogqpTrajectoryFn.apply(*self.args, y0, *frame.own, hr_t, hs_t, hr, hs)
+        activation, diffusion, code, schedule, bm = self.args
+        rows, d = y0.shape[0], frame.d
+        y0d = y0.detach()
+        net = K.PerceptronGradients.prepare(d, *frame.own)
+        states = torch.empty((schedule.n_out + 1, rows, d), dtype=y0.dtype, device=y0.device)
+        states[0].copy_(y0d[:, :d])
+        column = torch.empty((schedule.n_out, rows), dtype=y0.dtype, device=y0.device)
+        trajectory_mlp_diag_logqp(states[1:], column, states[0], *net, hr, hs, activation, diffusion, code, schedule, bm)
+        return K.assemble_logqp_output(states, column, y0d[:, d])
+
+    def record(self, fast, stepwise, y0, extra_inputs=()):
+        what = "the KL perceptron kernels" + (" (back-propagation)" if self.recording else " (sampling)")
+        verdict = self.solver._both_routes_agree(fast, stepwise, y0, what, network=True, extra_inputs=extra_inputs)
+        self.ledger.file(self.key, verdict, self.reverify)
+        if verdict is True:
+            self.ledger.name_kernel(self.key, "tsde_trajectory_mlp_diag_logqp + tsde_trajectory_mlp_diag_logqp_backward"
+                                    if self.recording else "tsde_trajectory_mlp_diag_logqp")
+        return verdict
+
+
+def _leaves_reached(tensors):
+    """ids of the leaf tensors the autograd graphs of `tensors` reach."""
+    reached, seen = set(), set()
+    stack = [t.grad_fn for t in tensors]
+    reached.update(id(t) for t in tensors if t.is_leaf)
+    while stack:
+        fn = stack.pop()
+        if fn is None or fn in seen:
+            continue
+        seen.add(fn)                                     # (the node itself: the id of a collected wrapper is used again)
+        if hasattr(fn, "variable"):
+            reached.add(id(fn.variable))
+        stack.extend(nxt for nxt, _ in fn.next_functions)
+    return reached
+
+
+def plan_logqp_sdeint(sde, y0, ts, bm, method, dt, adaptive, options, extra, extra_solver_state, solver):
+    """The `LogqpSdeintRoute` of ``sdeint(sde, y0, ts, logqp=True)`` if the call can take the KL kernels, else None (it stays
+    on the stepwise solver). Conditions: everything `_logqp_frame` asks; Euler, or Milstein with the affine diffusion when
+    autograd records (the reverse sweep has no sigmoid Milstein terms); no `adaptive`, `extra`, given `extra_solver_state`,
+    ``options={"hip_graph": True}`` or ``options={"trajectory_kernel": False}``. With autograd recording (`y0` or a parameter
+    of the module requires a gradient) every output must sit on a step boundary, and every trainable parameter of the module
+    must be one of the six tensors or reached by the prior's coefficients: `kernels._MlpLogqpTrajectoryFn`. Without, outputs
+    inside steps are interpolated by the kernel. Trust as in `plan_logqp`, on keys of its own (..., "logqp", "backprop" |
+    "sampling", ...): the first solve of a key runs both routes and returns the stepwise result; TSDE_VERIFY_EVERY applies; no
+    verifying solve runs under stream capture."""
+    from . import graph, recognise
+    if (adaptive or extra or extra_solver_state is not None or method not in (METHODS.euler, METHODS.milstein)
+            or options.get(METHOD_OPTIONS.grad_free, False) or not options.get("trajectory_kernel", True)
+            or graph.mode_of(options) is True or not recognise.ENABLED or solver is None):
+        return None
+    frame = _logqp_frame(sde, y0, ts, bm, dt, solver)
+    if frame is None:
+        return None
+    code = _FORWARD_CODES[(method, SDE_TYPES.ito)]
+    spec, steps, ledger = frame.spec, frame.steps, frame.ledger
+    recording = torch.is_grad_enabled() and (y0.requires_grad or any(p.requires_grad for p in frame.module_params))
+    if recording:
+        if not steps.on_boundaries or (spec[-1][0] == _native.DIFF_SIGMOID and code != _native.TRAJ_EULER):
+            return None
+        hr_t, hs_t = recognise.prior_coefficient_graph(frame.inner.h, frame.t0, frame.d, y0.dtype, y0.device)
+        reached = _leaves_reached((hr_t, hs_t)) | {id(p) for p in frame.own}
+        if any(p.requires_grad and id(p) not in reached for p in frame.module_params):
+            return None
+    key = ledger.key(frame.found, y0, "logqp", "backprop" if recording else "sampling", method, frame.shape_of(frame.hr),
+                     frame.shape_of(frame.hs))
+    decided = frame.verdict(key, y0)
+    if decided is None:
+        return None
+    verdict, reverify = decided
+    if recording:
+        args = (spec[-2], tuple(spec[-1]), code, steps.schedule(y0.device, y0.dtype, every_step=True),
+                tuple(int(k) for k in steps.out_step), bm)
+    else:
+        args = (spec[-2], tuple(spec[-1]), code, steps.schedule(y0.device, y0.dtype), bm)
+    return LogqpSdeintRoute(solver, frame, args, recording, ledger, key, verdict is True, reverify)
 
 
 def route(sde, y0, ts, bm, method, adjoint_method, dt, adaptive, adjoint_adaptive, options, adjoint_options,

@@ -743,6 +743,38 @@ int tsde_trajectory_mlp_diag_logqp_backward(void* lam, void* a_l, void* stash_la
                                             int32_t k_lo, int32_t k_hi, uint64_t entropy, uint64_t elem0,
                                             const uint64_t* entropy_dev, int dtype, void* stream);
 
+/* tsde_trajectory_mlp_diag_backward and tsde_trajectory_mlp_diag_logqp_backward for outputs anywhere in a step: output j of the
+ * forward solve was the reference's interpolation (base_solver.py:147, interp.py:15-18)
+ *     out_j = w0_j y_k + w1_j y_{k+1},   k + 1 = grad_step[j]      (the column: w0_j l_k + w1_j l_{k+1})
+ * with (w0, w1) = (0, 1) for an output on boundary k + 1. Several outputs may share a step. In the iteration of step k, for
+ * every output j with grad_step[j] == k + 1:
+ *     before the step's products:   lam += w1_j grad_ys[j]        (a_l += w1_j grad_logqp[j]),   then stash_lam as above
+ *     after them (lam = dL/dy_k):   lam += w0_j grad_ys[j]        (a_l += w0_j grad_logqp[j], read from step k - 1 down)
+ * Both shares are added inside the iteration of step k, so a chunk [k_lo, k_hi) receives every share of the outputs with
+ * k_lo < grad_step <= k_hi and lam (a_l) at k_lo includes the w0 shares of the outputs inside step k_lo.
+ *   grad_w       (n_grad, 2) float32, device: (w0_j, w1_j). An entry (0, 1) takes the path of the entry points above -- the
+ *                cotangent is added as it is -- and a table of such entries gives their results bit for bit.
+ *   grad_step    (n_grad, ascending, device): output j lies in step grad_step[j] - 1 (on boundary grad_step[j] or inside);
+ *                grad_last = index of the last entry with grad_step <= k_hi, or -1
+ *   ys_all       the states at step BOUNDARIES, as above: an interpolated output is not one of them
+ * Everything else as the entry point of the same name without the suffix. */
+int tsde_trajectory_mlp_diag_backward_weighted(void* lam, void* stash_lam, void* stash_hid, void* stash_delta, void* row_rate,
+                                               void* row_shift, const void* ys_all, int32_t ys_first, const void* grad_ys,
+                                               const int32_t* grad_step, const void* grad_w, int32_t grad_last, int64_t rows,
+                                               int64_t d, int64_t hidden, const void* w1, const void* b1, const void* w2,
+                                               const void* diff_rate, const void* diff_shift, int diff_kind, double diff_amp,
+                                               int activation, int method, const tsde_traj_t* traj, int32_t k_lo,
+                                               int32_t k_hi, uint64_t entropy, uint64_t elem0, const uint64_t* entropy_dev,
+                                               int dtype, void* stream);
+int tsde_trajectory_mlp_diag_logqp_backward_weighted(
+    void* lam, void* a_l, void* stash_lam, void* stash_hid, void* stash_delta, void* row_rate, void* row_shift,
+    void* row_prior_rate, void* row_prior_shift, const void* ys_all, int32_t ys_first, const void* grad_ys,
+    const void* grad_logqp, const int32_t* grad_step, const void* grad_w, int32_t grad_last, int64_t rows, int64_t d,
+    int64_t hidden, const void* w1, const void* b1, const void* w2, const void* b2, const void* diff_rate,
+    const void* diff_shift, const void* prior_rate, const void* prior_shift, int diff_kind, double diff_amp, int activation,
+    int method, int64_t bm_stride, const tsde_traj_t* traj, int32_t k_lo, int32_t k_hi, uint64_t entropy, uint64_t elem0,
+    const uint64_t* entropy_dev, int dtype, void* stream);
+
 /* ---- The reversible Heun pair for neural SDEs, one launch each way (csrc/tsde_neural_rheun.h) ----------------------------
  * Replaces, for modules whose drift and diffusion are perceptrons of (t, y),
  *   forward:  base_solver.py:114-134 driving methods/reversible_heun.py:48-73 (ReversibleHeun.step; the carried (f, g, z) of

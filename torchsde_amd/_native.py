@@ -190,6 +190,15 @@ SIGNATURES = {
                                                          _c_i64] + [_c_ptr] * 8 +
                                                 [_c_int, _c_dbl, _c_int, _c_int, _c_i64, ctypes.POINTER(Traj), _c_i32, _c_i32,
                                                  _c_u64, _c_u64, _c_ptr, _c_int, _c_ptr]),
+    # (the two above with the outputs' interpolation weights, a pointer after grad_step)
+    "tsde_trajectory_mlp_diag_backward_weighted": (_c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i32, _c_ptr,
+                                                            _c_ptr, _c_ptr, _c_i32, _c_i64, _c_i64, _c_i64, _c_ptr, _c_ptr, _c_ptr,
+                                                            _c_ptr, _c_ptr, _c_int, _c_dbl, _c_int, _c_int, ctypes.POINTER(Traj),
+                                                            _c_i32, _c_i32, _c_u64, _c_u64, _c_ptr, _c_int, _c_ptr]),
+    "tsde_trajectory_mlp_diag_logqp_backward_weighted": (_c_int, [_c_ptr] * 10 + [_c_i32, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i32,
+                                                                  _c_i64, _c_i64, _c_i64] + [_c_ptr] * 8 +
+                                                         [_c_int, _c_dbl, _c_int, _c_int, _c_i64, ctypes.POINTER(Traj), _c_i32,
+                                                          _c_i32, _c_u64, _c_u64, _c_ptr, _c_int, _c_ptr]),
     "tsde_trajectory_expr_diag": (_c_int, [_c_ptr, _c_ptr, _c_i64, _c_i64, _c_ptr * 8, _c_int, _c_int, _c_int,
                                            ctypes.POINTER(Traj), _c_u64, _c_u64, _c_ptr, _c_int, _c_ptr]),
     "tsde_adjoint_mlp_diag": (_c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64,

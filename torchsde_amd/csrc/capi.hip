@@ -822,15 +822,14 @@ int tsde_adjoint_mlp_diag_logqp(void* y, void* a, const void* a_l, void* stash_a
               where);
 }
 
-int tsde_trajectory_mlp_diag_backward(void* lam, void* stash_lam, void* stash_hid, void* stash_delta, void* row_rate,
-                                      void* row_shift, const void* ys_all, int32_t ys_first, const void* grad_ys,
-                                      const int32_t* grad_step, int32_t grad_last, int64_t rows, int64_t d,
-                                      int64_t hidden, const void* w1, const void* b1, const void* w2,
-                                      const void* diff_rate, const void* diff_shift, int diff_kind, double diff_amp,
-                                      int activation, int method, const tsde_traj_t* traj, int32_t k_lo, int32_t k_hi,
-                                      uint64_t entropy, uint64_t elem0, const uint64_t* entropy_dev, int dtype,
-                                      void* stream) {
-  const char* where = "tsde_trajectory_mlp_diag_backward";
+// tsde_trajectory_mlp_diag_backward (grad_w null: every output on its boundary) and ..._weighted
+static int mlp_diag_backward(const char* where, void* lam, void* stash_lam, void* stash_hid, void* stash_delta, void* row_rate,
+                             void* row_shift, const void* ys_all, int32_t ys_first, const void* grad_ys,
+                             const int32_t* grad_step, const void* grad_w, int32_t grad_last, int64_t rows, int64_t d,
+                             int64_t hidden, const void* w1, const void* b1, const void* w2, const void* diff_rate,
+                             const void* diff_shift, int diff_kind, double diff_amp, int activation, int method,
+                             const tsde_traj_t* traj, int32_t k_lo, int32_t k_hi, uint64_t entropy, uint64_t elem0,
+                             const uint64_t* entropy_dev, int dtype, void* stream) {
   const char* own =
       method != TSDE_TRAJ_EULER && method != TSDE_TRAJ_MILSTEIN_ITO && method != TSDE_TRAJ_MILSTEIN_STRAT
           ? "method must be Euler or Milstein"
@@ -846,24 +845,52 @@ int tsde_trajectory_mlp_diag_backward(void* lam, void* stash_lam, void* stash_hi
   const hipStream_t s = (hipStream_t)stream;
   ProfScope p(TSDE_KID_MLP_BACKWARD, s);
   return fail(tsde::launch_trajectory_mlp_diag_backward(lam, stash_lam, stash_hid, stash_delta, row_rate, row_shift,
-                                                        ys_all, ys_first, grad_ys, grad_step, grad_last, rows, d, hidden, w1, b1,
+                                                        ys_all, ys_first, grad_ys, grad_step, grad_w, grad_last, rows, d, hidden,
+                                                        w1, b1,
                                                         w2, diff_rate, diff_shift, diff_kind, diff_amp, activation, method,
                                                         traj, k_lo, k_hi,
                                                         make_key(entropy, elem0), entropy_dev, s),
               where);
 }
 
-int tsde_trajectory_mlp_diag_logqp_backward(void* lam, void* a_l, void* stash_lam, void* stash_hid, void* stash_delta,
-                                            void* row_rate, void* row_shift, void* row_prior_rate, void* row_prior_shift,
-                                            const void* ys_all, int32_t ys_first, const void* grad_ys,
-                                            const void* grad_logqp, const int32_t* grad_step, int32_t grad_last,
-                                            int64_t rows, int64_t d, int64_t hidden, const void* w1, const void* b1,
-                                            const void* w2, const void* b2, const void* diff_rate, const void* diff_shift,
-                                            const void* prior_rate, const void* prior_shift, int diff_kind, double diff_amp,
-                                            int activation, int method, int64_t bm_stride, const tsde_traj_t* traj,
-                                            int32_t k_lo, int32_t k_hi, uint64_t entropy, uint64_t elem0,
-                                            const uint64_t* entropy_dev, int dtype, void* stream) {
-  const char* where = "tsde_trajectory_mlp_diag_logqp_backward";
+int tsde_trajectory_mlp_diag_backward(void* lam, void* stash_lam, void* stash_hid, void* stash_delta, void* row_rate,
+                                      void* row_shift, const void* ys_all, int32_t ys_first, const void* grad_ys,
+                                      const int32_t* grad_step, int32_t grad_last, int64_t rows, int64_t d,
+                                      int64_t hidden, const void* w1, const void* b1, const void* w2,
+                                      const void* diff_rate, const void* diff_shift, int diff_kind, double diff_amp,
+                                      int activation, int method, const tsde_traj_t* traj, int32_t k_lo, int32_t k_hi,
+                                      uint64_t entropy, uint64_t elem0, const uint64_t* entropy_dev, int dtype,
+                                      void* stream) {
+  return mlp_diag_backward("tsde_trajectory_mlp_diag_backward", lam, stash_lam, stash_hid, stash_delta, row_rate, row_shift,
+                           ys_all, ys_first, grad_ys, grad_step, nullptr, grad_last, rows, d, hidden, w1, b1, w2, diff_rate,
+                           diff_shift, diff_kind, diff_amp, activation, method, traj, k_lo, k_hi, entropy, elem0, entropy_dev,
+                           dtype, stream);
+}
+
+int tsde_trajectory_mlp_diag_backward_weighted(void* lam, void* stash_lam, void* stash_hid, void* stash_delta, void* row_rate,
+                                               void* row_shift, const void* ys_all, int32_t ys_first, const void* grad_ys,
+                                               const int32_t* grad_step, const void* grad_w, int32_t grad_last, int64_t rows,
+                                               int64_t d, int64_t hidden, const void* w1, const void* b1, const void* w2,
+                                               const void* diff_rate, const void* diff_shift, int diff_kind, double diff_amp,
+                                               int activation, int method, const tsde_traj_t* traj, int32_t k_lo,
+                                               int32_t k_hi, uint64_t entropy, uint64_t elem0, const uint64_t* entropy_dev,
+                                               int dtype, void* stream) {
+  const char* where = "tsde_trajectory_mlp_diag_backward_weighted";
+  if (grad_last >= 0 && !grad_w) return bad_arg(where, "grad_last >= 0 without weights");
+  return mlp_diag_backward(where, lam, stash_lam, stash_hid, stash_delta, row_rate, row_shift, ys_all, ys_first, grad_ys,
+                           grad_step, grad_w, grad_last, rows, d, hidden, w1, b1, w2, diff_rate, diff_shift, diff_kind, diff_amp,
+                           activation, method, traj, k_lo, k_hi, entropy, elem0, entropy_dev, dtype, stream);
+}
+
+// tsde_trajectory_mlp_diag_logqp_backward (grad_w null: every output on its boundary) and ..._weighted
+static int mlp_diag_logqp_backward(
+    const char* where, void* lam, void* a_l, void* stash_lam, void* stash_hid, void* stash_delta,
+    void* row_rate, void* row_shift, void* row_prior_rate, void* row_prior_shift, const void* ys_all, int32_t ys_first,
+    const void* grad_ys, const void* grad_logqp, const int32_t* grad_step, const void* grad_w, int32_t grad_last, int64_t rows,
+    int64_t d, int64_t hidden, const void* w1, const void* b1, const void* w2, const void* b2, const void* diff_rate,
+    const void* diff_shift, const void* prior_rate, const void* prior_shift, int diff_kind, double diff_amp, int activation,
+    int method, int64_t bm_stride, const tsde_traj_t* traj, int32_t k_lo, int32_t k_hi, uint64_t entropy, uint64_t elem0,
+    const uint64_t* entropy_dev, int dtype, void* stream) {
   const char* own =
       method != TSDE_TRAJ_EULER && method != TSDE_TRAJ_MILSTEIN_ITO ? "method must be Euler or Ito Milstein"
       : diff_kind != TSDE_DIFF_AFFINE && !(diff_kind == TSDE_DIFF_SIGMOID && method == TSDE_TRAJ_EULER)
@@ -880,10 +907,42 @@ int tsde_trajectory_mlp_diag_logqp_backward(void* lam, void* a_l, void* stash_la
   ProfScope p(TSDE_KID_MLP_BACKWARD, s);
   return fail(tsde::launch_trajectory_mlp_diag_logqp_backward(
                   lam, a_l, stash_lam, stash_hid, stash_delta, row_rate, row_shift, row_prior_rate, row_prior_shift, ys_all,
-                  ys_first, grad_ys, grad_logqp, grad_step, grad_last, rows, d, hidden, w1, b1, w2, b2, diff_rate, diff_shift,
+                  ys_first, grad_ys, grad_logqp, grad_step, grad_w, grad_last, rows, d, hidden, w1, b1, w2, b2, diff_rate, diff_shift,
                   prior_rate, prior_shift, diff_kind, diff_amp, activation, method, traj, k_lo, k_hi, bm_stride,
                   make_key(entropy, elem0), entropy_dev, s),
               where);
+}
+
+int tsde_trajectory_mlp_diag_logqp_backward(void* lam, void* a_l, void* stash_lam, void* stash_hid, void* stash_delta,
+                                            void* row_rate, void* row_shift, void* row_prior_rate, void* row_prior_shift,
+                                            const void* ys_all, int32_t ys_first, const void* grad_ys,
+                                            const void* grad_logqp, const int32_t* grad_step, int32_t grad_last,
+                                            int64_t rows, int64_t d, int64_t hidden, const void* w1, const void* b1,
+                                            const void* w2, const void* b2, const void* diff_rate, const void* diff_shift,
+                                            const void* prior_rate, const void* prior_shift, int diff_kind, double diff_amp,
+                                            int activation, int method, int64_t bm_stride, const tsde_traj_t* traj,
+                                            int32_t k_lo, int32_t k_hi, uint64_t entropy, uint64_t elem0,
+                                            const uint64_t* entropy_dev, int dtype, void* stream) {
+  return mlp_diag_logqp_backward("tsde_trajectory_mlp_diag_logqp_backward", lam, a_l, stash_lam, stash_hid, stash_delta, row_rate, row_shift, row_prior_rate,
+                                 row_prior_shift, ys_all, ys_first, grad_ys, grad_logqp, grad_step, nullptr, grad_last, rows, d,
+                                 hidden, w1, b1, w2, b2, diff_rate, diff_shift, prior_rate, prior_shift, diff_kind, diff_amp,
+                                 activation, method, bm_stride, traj, k_lo, k_hi, entropy, elem0, entropy_dev, dtype, stream);
+}
+
+int tsde_trajectory_mlp_diag_logqp_backward_weighted(
+    void* lam, void* a_l, void* stash_lam, void* stash_hid, void* stash_delta,
+    void* row_rate, void* row_shift, void* row_prior_rate, void* row_prior_shift, const void* ys_all, int32_t ys_first,
+    const void* grad_ys, const void* grad_logqp, const int32_t* grad_step, const void* grad_w, int32_t grad_last, int64_t rows,
+    int64_t d, int64_t hidden, const void* w1, const void* b1, const void* w2, const void* b2, const void* diff_rate,
+    const void* diff_shift, const void* prior_rate, const void* prior_shift, int diff_kind, double diff_amp, int activation,
+    int method, int64_t bm_stride, const tsde_traj_t* traj, int32_t k_lo, int32_t k_hi, uint64_t entropy, uint64_t elem0,
+    const uint64_t* entropy_dev, int dtype, void* stream) {
+  const char* where = "tsde_trajectory_mlp_diag_logqp_backward_weighted";
+  if (grad_last >= 0 && !grad_w) return bad_arg(where, "grad_last >= 0 without weights");
+  return mlp_diag_logqp_backward(where, lam, a_l, stash_lam, stash_hid, stash_delta, row_rate, row_shift, row_prior_rate,
+                                 row_prior_shift, ys_all, ys_first, grad_ys, grad_logqp, grad_step, grad_w, grad_last, rows, d,
+                                 hidden, w1, b1, w2, b2, diff_rate, diff_shift, prior_rate, prior_shift, diff_kind, diff_amp,
+                                 activation, method, bm_stride, traj, k_lo, k_hi, entropy, elem0, entropy_dev, dtype, stream);
 }
 
 int tsde_gram_partials(void* partials, void* colsum_partials, const void* a, int64_t lda, const void* b, int64_t ldb,

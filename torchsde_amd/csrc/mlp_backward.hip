@@ -44,8 +44,9 @@ struct MlpBackArgs {
   const float* ys_all;      // (.., B, d) states at step boundaries ys_first, ys_first + 1, ... (at least up to k_hi - 1)
   int32_t ys_first;
   const float* grad_ys;     // (n_grad, B, d) cotangents of the outputs
-  const int32_t* grad_step; // (n_grad) ascending boundary index of each output
-  int32_t grad_last;        // index of the last output at a boundary <= k_hi (-1: none)
+  const int32_t* grad_step; // (n_grad) ascending: output j sits in step grad_step[j] - 1, on boundary grad_step[j] or inside
+  const float* grad_w;      // (n_grad, 2) interpolation weights (w0, w1) of each output, or null: every output on its boundary
+  int32_t grad_last;        // index of the last output with grad_step <= k_hi (-1: none)
   const float* W1;          // (d, h) as in MlpArgs
   const float* b1;          // (h)
   const float* W2;          // (h, d)
@@ -90,7 +91,9 @@ struct MlpBackKlArgs : MlpBackArgs {
 // them in one kernel behind uniform branches the register allocator spilled hundreds of dwords at every shape.
 constexpr int kKlEulerAffine = 0, kKlEulerSigmoid = 1, kKlMilsteinAffine = 2;
 
-template <int D, int H, int ACT, int NW, bool FULL, bool KL = false, int KIND = 0>
+// WEIGHTED: outputs anywhere in a step (`grad_w`); without, every output sits on its boundary and `grad_w` is not read -- the
+// sweep as it was before outputs inside steps, instruction for instruction.
+template <int D, int H, int ACT, int NW, bool FULL, bool KL = false, int KIND = 0, bool WEIGHTED = false>
 __global__ void __launch_bounds__(NW * 64)
     mlp_backward_kernel(const std::conditional_t<KL, MlpBackKlArgs, MlpBackArgs> p) {
   constexpr int R = 16;
@@ -186,17 +189,42 @@ __global__ void __launch_bounds__(NW * 64)
     const float dt = srow[0], sw = srow[4];
     const uint32_t cell = p.cells[k];
     const int64_t slot = k - p.k_lo;
-    const bool arrives = jg >= 0 && p.grad_step[jg] == k + 1;     // an output sits on boundary k + 1
+    const bool arrives = jg >= 0 && p.grad_step[jg] == k + 1;     // an output sits on boundary k + 1 (WEIGHTED: in step k)
 
+    if constexpr (!WEIGHTED) {
 #pragma unroll
-    for (int t = 0; t < TD; ++t) {
-      if (arrives) lam[t] += load_tile(p.grad_ys + (int64_t)jg * p.B * dT, t);
-      if constexpr (!KL) store_tile(p.stash_lam + slot * p.B * dT, t, lam[t] * dt);     // (KL: once f is known, below)
+      for (int t = 0; t < TD; ++t) {
+        if (arrives) lam[t] += load_tile(p.grad_ys + (int64_t)jg * p.B * dT, t);
+        if constexpr (!KL) store_tile(p.stash_lam + slot * p.B * dT, t, lam[t] * dt);     // (KL: once f is known, below)
+      }
+      if constexpr (KL) {
+        if (arrives) al += p.grad_logqp[(int64_t)jg * p.B + row];
+      }
+      if (arrives) --jg;
+    } else {
+      // outputs jg, jg - 1, ... sit in step k: on boundary k + 1, or inside the step as w0 y_k + w1 y_{k+1} (base_solver.py:147,
+      // interp.py:15-18) -- their w1 share joins lam = dL/dy_{k+1} here, their w0 share dL/dy_k at the end of the iteration
+      if (arrives) {
+        do {
+          const float* gy = p.grad_ys + (int64_t)jg * p.B * dT;
+          const float w0 = p.grad_w[2 * jg], w1 = p.grad_w[2 * jg + 1];
+          if (w0 == 0.0f && w1 == 1.0f) {                              // on the boundary: the cotangent as it is
+#pragma unroll
+            for (int t = 0; t < TD; ++t) lam[t] += load_tile(gy, t);
+            if constexpr (KL) al += p.grad_logqp[(int64_t)jg * p.B + row];
+          } else {
+#pragma unroll
+            for (int t = 0; t < TD; ++t) lam[t] += load_tile(gy, t) * w1;
+            if constexpr (KL) al += p.grad_logqp[(int64_t)jg * p.B + row] * w1;
+          }
+          --jg;
+        } while (jg >= 0 && p.grad_step[jg] == k + 1);
+      }
+      if constexpr (!KL) {
+#pragma unroll
+        for (int t = 0; t < TD; ++t) store_tile(p.stash_lam + slot * p.B * dT, t, lam[t] * dt);
+      }
     }
-    if constexpr (KL) {
-      if (arrives) al += p.grad_logqp[(int64_t)jg * p.B + row];
-    }
-    if (arrives) --jg;
     __builtin_amdgcn_sched_barrier(0);
 
     // ---- hidden layer: z^T = W1^T y^T; keep act'(z), stash act(z) ---------------------------------------------------
@@ -379,6 +407,19 @@ __global__ void __launch_bounds__(NW * 64)
       lam[t] += back;
       __builtin_amdgcn_sched_barrier(0);
     }
+
+    // ---- lam is dL/dy_k: the w0 share of the outputs inside this step (a_l: from step k - 1 down). They are the outputs
+    //      above jg again, found from the table: nothing of them is kept across the step -------------------------------------
+    if constexpr (WEIGHTED) {
+      for (int j = jg + 1; j <= p.grad_last && p.grad_step[j] == k + 1; ++j) {
+        const float w0 = p.grad_w[2 * j];
+        if (w0 == 0.0f) continue;
+        const float* gy = p.grad_ys + (int64_t)j * p.B * dT;
+#pragma unroll
+        for (int t = 0; t < TD; ++t) lam[t] += load_tile(gy, t) * w0;
+        if constexpr (KL) al += p.grad_logqp[(int64_t)j * p.B + row] * w0;
+      }
+    }
   }
 
 #pragma unroll
@@ -407,6 +448,9 @@ struct MlpBackwardPolicy {
   template <int D, int H, int ACT, bool FULL>
   static hipError_t launch(const MlpBackArgs& p, hipStream_t s) {
     constexpr int NW = (!FULL && D == 128) ? 4 : 8;
+    if (p.grad_w != nullptr)
+      return launch_rows_per_wave<mlp_backward_kernel<D, H, ACT, NW, FULL, false, 0, true>, NW, 16>(
+          p, MlpLds<16>::bytes(D, H, 2), s);
     return launch_rows_per_wave<mlp_backward_kernel<D, H, ACT, NW, FULL>, NW, 16>(p, MlpLds<16>::bytes(D, H, 2), s);
   }
 };
@@ -421,19 +465,28 @@ struct MlpBackwardKlPolicy {
   static hipError_t launch(const MlpBackKlArgs& p, hipStream_t s) {
     constexpr int NW = 8;
     constexpr size_t lds_bytes = MlpLds<16>::bytes(D, H, 5, NW * 4 * D);
+    return p.grad_w != nullptr ? launch_kind<D, H, ACT, FULL, true>(p, lds_bytes, s)
+                               : launch_kind<D, H, ACT, FULL, false>(p, lds_bytes, s);
+  }
+  template <int D, int H, int ACT, bool FULL, bool WEIGHTED>
+  static hipError_t launch_kind(const MlpBackKlArgs& p, size_t lds_bytes, hipStream_t s) {
+    constexpr int NW = 8;
     if (p.method != TSDE_TRAJ_EULER)
-      return launch_rows_per_wave<mlp_backward_kernel<D, H, ACT, NW, FULL, true, kKlMilsteinAffine>, NW, 16>(p, lds_bytes, s);
+      return launch_rows_per_wave<mlp_backward_kernel<D, H, ACT, NW, FULL, true, kKlMilsteinAffine, WEIGHTED>, NW, 16>(
+          p, lds_bytes, s);
     if (p.diff_kind == TSDE_DIFF_SIGMOID)
-      return launch_rows_per_wave<mlp_backward_kernel<D, H, ACT, NW, FULL, true, kKlEulerSigmoid>, NW, 16>(p, lds_bytes, s);
-    return launch_rows_per_wave<mlp_backward_kernel<D, H, ACT, NW, FULL, true, kKlEulerAffine>, NW, 16>(p, lds_bytes, s);
+      return launch_rows_per_wave<mlp_backward_kernel<D, H, ACT, NW, FULL, true, kKlEulerSigmoid, WEIGHTED>, NW, 16>(
+          p, lds_bytes, s);
+    return launch_rows_per_wave<mlp_backward_kernel<D, H, ACT, NW, FULL, true, kKlEulerAffine, WEIGHTED>, NW, 16>(
+        p, lds_bytes, s);
   }
 };
 
 static void fill_back_args(MlpBackArgs& p, void* lam, void* stash_lam, void* stash_hid, void* stash_delta, void* row_rate,
                            void* row_shift, const void* ys_all, int32_t ys_first, const void* grad_ys,
-                           const int32_t* grad_step, int32_t grad_last, int64_t rows, int64_t d, int64_t h, const void* W1,
-                           const void* b1, const void* W2, const void* c, const void* e, int diff_kind, double diff_amp,
-                           int method, const tsde_traj_t* tr, int32_t k_lo, int32_t k_hi, NoiseKey key,
+                           const int32_t* grad_step, const void* grad_w, int32_t grad_last, int64_t rows, int64_t d, int64_t h,
+                           const void* W1, const void* b1, const void* W2, const void* c, const void* e, int diff_kind,
+                           double diff_amp, int method, const tsde_traj_t* tr, int32_t k_lo, int32_t k_hi, NoiseKey key,
                            const uint64_t* key_dev) {
   fill_mlp_core(p, rows, d, h, W1, b1, W2, c, e, diff_kind, diff_amp, tr, key, key_dev);
   p.lam = (float*)lam;
@@ -446,6 +499,7 @@ static void fill_back_args(MlpBackArgs& p, void* lam, void* stash_lam, void* sta
   p.ys_first = ys_first;
   p.grad_ys = (const float*)grad_ys;
   p.grad_step = grad_step;
+  p.grad_w = (const float*)grad_w;
   p.grad_last = grad_last;
   p.method = method;
   p.k_lo = k_lo;
@@ -454,7 +508,8 @@ static void fill_back_args(MlpBackArgs& p, void* lam, void* stash_lam, void* sta
 
 hipError_t launch_trajectory_mlp_diag_backward(void* lam, void* stash_lam, void* stash_hid, void* stash_delta,
                                                void* row_rate, void* row_shift, const void* ys_all,
-                                               int32_t ys_first, const void* grad_ys, const int32_t* grad_step, int32_t grad_last,
+                                               int32_t ys_first, const void* grad_ys, const int32_t* grad_step,
+                                               const void* grad_w, int32_t grad_last,
                                                int64_t rows, int64_t d, int64_t h, const void* W1, const void* b1,
                                                const void* W2, const void* c, const void* e, int diff_kind,
                                                double diff_amp, int act, int method, const tsde_traj_t* tr,
@@ -462,7 +517,7 @@ hipError_t launch_trajectory_mlp_diag_backward(void* lam, void* stash_lam, void*
                                                hipStream_t s) {
   MlpBackArgs p;
   fill_back_args(p, lam, stash_lam, stash_hid, stash_delta, row_rate, row_shift, ys_all, ys_first, grad_ys, grad_step,
-                 grad_last, rows, d, h, W1, b1, W2, c, e, diff_kind, diff_amp, method, tr, k_lo, k_hi, key, key_dev);
+                 grad_w, grad_last, rows, d, h, W1, b1, W2, c, e, diff_kind, diff_amp, method, tr, k_lo, k_hi, key, key_dev);
   if (rows <= 0 || k_hi <= k_lo) return hipSuccess;
   return mlp_ladder<MlpBackwardPolicy>(p, act, s);
 }
@@ -471,15 +526,15 @@ hipError_t launch_trajectory_mlp_diag_logqp_backward(void* lam, void* a_l, void*
                                                      void* stash_delta, void* row_rate, void* row_shift, void* row_hrate,
                                                      void* row_hshift, const void* ys_all, int32_t ys_first,
                                                      const void* grad_ys, const void* grad_logqp, const int32_t* grad_step,
-                                                     int32_t grad_last, int64_t rows, int64_t d, int64_t h, const void* W1,
-                                                     const void* b1, const void* W2, const void* b2, const void* c,
+                                                     const void* grad_w, int32_t grad_last, int64_t rows, int64_t d, int64_t h,
+                                                     const void* W1, const void* b1, const void* W2, const void* b2, const void* c,
                                                      const void* e, const void* hr, const void* hs, int diff_kind,
                                                      double diff_amp, int act, int method, const tsde_traj_t* tr,
                                                      int32_t k_lo, int32_t k_hi, int64_t bm_stride, NoiseKey key,
                                                      const uint64_t* key_dev, hipStream_t s) {
   MlpBackKlArgs p;
   fill_back_args(p, lam, stash_lam, stash_hid, stash_delta, row_rate, row_shift, ys_all, ys_first, grad_ys, grad_step,
-                 grad_last, rows, d, h, W1, b1, W2, c, e, diff_kind, diff_amp, method, tr, k_lo, k_hi, key, key_dev);
+                 grad_w, grad_last, rows, d, h, W1, b1, W2, c, e, diff_kind, diff_amp, method, tr, k_lo, k_hi, key, key_dev);
   p.a_l = (float*)a_l;
   p.grad_logqp = (const float*)grad_logqp;
   p.b2 = (const float*)b2;

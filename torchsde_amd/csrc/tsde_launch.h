@@ -288,7 +288,8 @@ size_t neural_footprint(int64_t d, int64_t m, int64_t hf, int64_t hg, int64_t ou
 // mlp_backward.hip
 hipError_t launch_trajectory_mlp_diag_backward(void* lam, void* stash_lam, void* stash_hid, void* stash_delta,
                                                void* row_rate, void* row_shift, const void* ys_all,
-                                               int32_t ys_first, const void* grad_ys, const int32_t* grad_step, int32_t grad_last,
+                                               int32_t ys_first, const void* grad_ys, const int32_t* grad_step,
+                                               const void* grad_w, int32_t grad_last,
                                                int64_t rows, int64_t d, int64_t h, const void* W1, const void* b1,
                                                const void* W2, const void* c, const void* e, int diff_kind,
                                                double diff_amp, int act, int method, const tsde_traj_t* tr,
@@ -298,7 +299,8 @@ hipError_t launch_trajectory_mlp_diag_logqp_backward(void* lam, void* a_l, void*
                                                      void* stash_delta, void* row_rate, void* row_shift, void* row_hrate,
                                                      void* row_hshift, const void* ys_all, int32_t ys_first,
                                                      const void* grad_ys, const void* grad_logqp, const int32_t* grad_step,
-                                                     int32_t grad_last, int64_t rows, int64_t d, int64_t h, const void* W1,
+                                                     const void* grad_w, int32_t grad_last, int64_t rows, int64_t d, int64_t h,
+                                                     const void* W1,
                                                      const void* b1, const void* W2, const void* b2, const void* c,
                                                      const void* e, const void* hr, const void* hs, int diff_kind,
                                                      double diff_amp, int act, int method, const tsde_traj_t* tr,

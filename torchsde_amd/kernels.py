@@ -1283,19 +1283,109 @@ class PerceptronGradients:
         return grads
 
 
-_boundary_tables = collections.OrderedDict()
+class OutputMap:
+    """Where the outputs of a differentiable perceptron-drift solve lie: output i (after y0) in step `steps[i] - 1`, on boundary
+    `steps[i]` or -- `weights[i] = (w0, w1)` other than (0, 1) -- inside the step as w0 y_k + w1 y_{k+1} (timegrid's output map).
+    `weights` is None when every output sits on its boundary: the solve then takes the launches it always took.
+
+    The sampling kernel's emitter serves the interpolated outputs (several per step included): `layout(marks)` is the output
+    list of ONE launch that writes the boundaries `marks` and the outputs inside steps, and where each lands."""
+
+    def __init__(self, steps, weights=None):
+        self.steps = tuple(int(k) for k in steps)
+        pairs = None if weights is None else tuple((float(w0), float(w1)) for (w0, w1) in weights)
+        self.weights = None if pairs is None or _on_boundaries(pairs) else pairs
+        self._tables = {}
+
+    _recent = collections.OrderedDict()
+
+    @classmethod
+    def cached(cls, steps, weights=None):
+        """The map of a solve the process has seen before, with its device tables (remembered like the schedules)."""
+        key = (tuple(int(k) for k in steps), None if weights is None else tuple((float(a), float(b)) for a, b in weights))
+        hit = cls._recent.get(key)
+        if hit is None:
+            hit = cls._recent[key] = cls(*key)
+            while len(cls._recent) > 8:
+                cls._recent.popitem(last=False)
+        else:
+            cls._recent.move_to_end(key)
+        return hit
+
+    def on_boundary(self, i):
+        return self.weights is None or self.weights[i] == (0.0, 1.0)
+
+    def boundary_outputs(self):
+        """The boundaries that are outputs themselves."""
+        return {k for i, k in enumerate(self.steps) if self.on_boundary(i)}
+
+    def layout(self, marks):
+        """(out_step, out_w, row_of_boundary, out_rows) of a launch that writes boundary k for every k in `marks` (which holds
+        every boundary output) and every output inside a step: the launch's output list in the emitter's order (ascending
+        steps), the row of `states` = [y0, *launch outputs] each boundary lands in, and the row of each of this map's outputs
+        (y0 first)."""
+        marks = set(marks)
+        inside = {}
+        for i, k in enumerate(self.steps):
+            if not self.on_boundary(i):
+                inside.setdefault(k, []).append(i)
+        out_step, out_w, row_of_boundary, out_rows = [], [], {0: 0}, [0] * (len(self.steps) + 1)
+        for k in sorted(marks | set(inside)):
+            for i in inside.get(k, ()):
+                out_step.append(k)
+                out_w.append(self.weights[i])
+                out_rows[i + 1] = len(out_step)
+            if k in marks:
+                out_step.append(k)
+                out_w.append((0.0, 1.0))
+                row_of_boundary[k] = len(out_step)
+        for i, k in enumerate(self.steps):
+            if self.on_boundary(i):
+                out_rows[i + 1] = row_of_boundary[k]
+        return out_step, out_w, row_of_boundary, out_rows
+
+    def _table(self, name, device, make):
+        key = (name, str(device))
+        if key not in self._tables:
+            self._tables[key] = torch.from_numpy(make()).to(device)
+        return self._tables[key]
+
+    def grad_step(self, device):
+        """Device table [0, *steps] (int32): `grad_step` of the reverse sweep, y0 first."""
+        return self._table("step", device, lambda: np.asarray((0,) + self.steps, dtype=np.int32))
+
+    def grad_w(self, device):
+        """Device table (len(steps) + 1, 2) float32 of the weights, y0 first as (0, 1); None when all are on boundaries."""
+        if self.weights is None:
+            return None
+        return self._table("w", device, lambda: np.asarray(((0.0, 1.0),) + self.weights, dtype=np.float32))
+
+    def boundary_rows(self, n_steps, device):
+        """Device index (int64) of the rows of boundaries 0 .. n_steps in the states of `layout(range(1, n_steps + 1))`."""
+        def make():
+            rows = self.layout(range(1, n_steps + 1))[2]
+            return np.asarray([rows[k] for k in range(n_steps + 1)], dtype=np.int64)
+        return self._table(("rows", n_steps), device, make)
 
 
-def _boundary_table(out_steps, device):
-    """Device table [0, *out_steps] (int32) of the step boundaries the outputs sit on; remembered like the schedules."""
-    key = (tuple(out_steps), str(device))
-    table = _boundary_tables.get(key)
-    if table is None:
-        table = torch.from_numpy(np.asarray((0,) + tuple(out_steps), dtype=np.int32)).to(device)
-        _boundary_tables[key] = table
-        while len(_boundary_tables) > 8:
-            _boundary_tables.popitem(last=False)
-    return table
+def _solve_layout(outputs, schedule_all, rows, width, budget, chunk, device, dtype):
+    """What the forward launch of a differentiable perceptron-drift solve writes (`_MlpTrajectoryFn`, `_MlpLogqpTrajectoryFn`):
+    (schedule, kept_at, out_rows, gather). Within `budget` bytes for `width` floats per row and boundary: every boundary
+    (`kept_at` None); over it: the chunk boundaries and the outputs (`kept_at`: boundary -> row of the launch's states).
+    `out_rows`: the row of each output, y0 first. `gather`: the device index of the boundary rows when outputs inside steps sit
+    between them in the launch's states, else None."""
+    n_steps = schedule_all.n_steps
+    if (n_steps + 1) * rows * width * 4 <= budget:
+        if outputs.weights is None:
+            return schedule_all, None, [0] + list(outputs.steps), None
+        out_step, out_w, _, out_rows = outputs.layout(range(1, n_steps + 1))
+        kept_at, gather = None, outputs.boundary_rows(n_steps, device)
+    else:
+        marks = set(range(n_steps, 0, -chunk)) | outputs.boundary_outputs()
+        out_step, out_w, kept_at, out_rows = outputs.layout(marks)
+        gather = None
+    schedule = TrajectorySchedule.cached(schedule_all.host_rows, schedule_all.host_cells, out_step, out_w, device, dtype)
+    return schedule, kept_at, out_rows, gather
 
 
 class _MlpTrajectoryFn(torch.autograd.Function):
@@ -1303,6 +1393,11 @@ class _MlpTrajectoryFn(torch.autograd.Function):
     kernel, writing the state at EVERY step (HBM is plentiful on this part; the reverse sweep needs them). Backward:
     the reverse sweep kernel over chunks of steps (last first), each followed by the two weight-gradient products over
     that chunk's stash -- the gradient back-propagation through the stepwise solver gives, without an autograd tape.
+
+    Outputs may lie anywhere (`outputs`: an `OutputMap`). Those inside steps are written by the same forward launch, which
+    interpolates them as the no-grad solve does (base_solver.py:147); the boundary states are then copied out from between
+    them, and the reverse sweep takes the weights (``tsde_trajectory_mlp_diag_backward_weighted``): w1 of an output's cotangent
+    joins dL/dy_{k+1} before the step's products, w0 joins dL/dy_k after them.
 
     When every step's state would not fit the budget (very large batch x steps), the forward launch keeps only the
     states at the chunk boundaries and the backward pass re-runs the sampling kernel over each chunk first (same
@@ -1319,7 +1414,7 @@ class _MlpTrajectoryFn(torch.autograd.Function):
         return PerceptronGradients.chunk_length(n_steps, rows, d + 2 * hidden, _MlpTrajectoryFn.STASH_BYTES)
 
     @staticmethod
-    def forward(ctx, activation, diffusion, method, schedule_all, out_steps, bm, y0, w1, b1, w2, b2, rate, shift):
+    def forward(ctx, activation, diffusion, method, schedule_all, outputs, bm, y0, w1, b1, w2, b2, rate, shift):
         rows, d = y0.shape
         hidden, n_steps = b1.numel(), schedule_all.n_steps
         y0c = _native.contiguous(y0.detach())
@@ -1327,28 +1422,24 @@ class _MlpTrajectoryFn(torch.autograd.Function):
         budget = _MlpTrajectoryFn.STATE_BYTES
         if budget is None:
             budget = torch.cuda.mem_get_info(y0.device)[0] // 2
-        if (n_steps + 1) * rows * d * 4 <= budget:
-            kept_at = None                                  # states[k] is the state at boundary k
-            schedule = schedule_all
-        else:
-            chunk = _MlpTrajectoryFn._chunk(n_steps, rows, d, hidden)
-            marks = sorted(set(range(n_steps, 0, -chunk)) | set(out_steps))
-            kept_at = {0: 0}
-            kept_at.update((k, i + 1) for i, k in enumerate(marks))
-            schedule = TrajectorySchedule.cached(schedule_all.host_rows, schedule_all.host_cells, marks,
-                                                 [(0.0, 1.0)] * len(marks), y0.device, y0.dtype)
+        # (kept_at None: states[k] is the state at boundary k)
+        schedule, kept_at, out_rows, gather = _solve_layout(outputs, schedule_all, rows, d, budget,
+                                                            _MlpTrajectoryFn._chunk(n_steps, rows, d, hidden), y0.device,
+                                                            y0.dtype)
         states = torch.empty((schedule.n_out + 1, rows, d), dtype=y0.dtype, device=y0.device)
         states[0].copy_(y0c)
         trajectory_mlp_diag(states[1:], y0c, *net, activation, diffusion, method, schedule, bm)
-        ctx.grad_step = _boundary_table(out_steps, y0.device)
+        # (a stack of views, not index_select: building an index tensor is a blocking host->device copy that would wait
+        #  for the forward launch)
+        ys = torch.stack([states[i] for i in out_rows], dim=0)
+        if gather is not None:          # the reverse sweep reads the boundary states one after the other (a remembered index)
+            states = states.index_select(0, gather)
         ctx.save_for_backward(states, *net)
         ctx.method, ctx.activation, ctx.hidden = int(method), int(activation), hidden
         ctx.diffusion = (int(diffusion[0]), float(diffusion[1]))
-        ctx.schedule, ctx.bm, ctx.out_steps, ctx.kept_at = schedule_all, bm, out_steps, kept_at
+        ctx.schedule, ctx.bm, ctx.outputs, ctx.kept_at = schedule_all, bm, outputs, kept_at
         ctx.param_shapes = (tuple(rate.shape), tuple(shift.shape))
-        # (a stack of views, not index_select: building an index tensor is a blocking host->device copy that would wait
-        #  for the forward launch)
-        return torch.stack([states[k if kept_at is None else kept_at[k]] for k in (0,) + tuple(out_steps)], dim=0)
+        return ys
 
     @staticmethod
     @torch.autograd.function.once_differentiable      # kernels, not torch ops: no graph of the backward pass exists
@@ -1359,7 +1450,11 @@ class _MlpTrajectoryFn(torch.autograd.Function):
         n_steps = schedule.n_steps
         dev = states.device
         gys = _native.contiguous(gys)
-        boundaries = np.asarray([0] + list(ctx.out_steps), dtype=np.int32)
+        boundaries = np.asarray((0,) + ctx.outputs.steps, dtype=np.int32)
+        grad_step, grad_w = ctx.outputs.grad_step(dev), ctx.outputs.grad_w(dev)
+        # (outputs inside steps: the entry point that takes their weights; without, the one it always was)
+        symbol = "tsde_trajectory_mlp_diag_backward" + ("" if grad_w is None else "_weighted")
+        weights = () if grad_w is None else (grad_w.data_ptr(),)
         chunk = _MlpTrajectoryFn._chunk(n_steps, rows, d, hidden)
         sums = PerceptronGradients(rows, d, hidden, dev)
         stash_lam, stash_hid, stash_delta = sums.stashes(chunk, (d, hidden, hidden))
@@ -1378,24 +1473,26 @@ class _MlpTrajectoryFn(torch.autograd.Function):
                                     ctx.diffusion, ctx.method, schedule.window(k_lo, k_hi), bm)
                 ys, ys_first = rerun, k_lo
             grad_last = int(np.searchsorted(boundaries, k_hi, side="right")) - 1
-            code = lib.tsde_trajectory_mlp_diag_backward(
+            code = getattr(lib, symbol)(
                 lam.data_ptr(), stash_lam.data_ptr(), stash_hid.data_ptr(), stash_delta.data_ptr(), row_rate.data_ptr(),
-                row_shift.data_ptr(), ys.data_ptr(), ys_first, gys.data_ptr(), ctx.grad_step.data_ptr(), grad_last,
+                row_shift.data_ptr(), ys.data_ptr(), ys_first, gys.data_ptr(), grad_step.data_ptr(), *weights, grad_last,
                 rows, d, hidden, w1_in.data_ptr(), b1c.data_ptr(), w2_in.data_ptr(), rate.data_ptr(), shift.data_ptr(),
                 ctx.diffusion[0], ctx.diffusion[1], ctx.activation, ctx.method,
                 *_native.sweep_tail(schedule, k_lo, k_hi, bm, dt_code, stream))
-            _native.check(code, "tsde_trajectory_mlp_diag_backward")
+            _native.check(code, symbol)
             sums.accumulate(n, stash_lam, stash_hid, stash_delta, ys[k_lo - ys_first:k_hi - ys_first])
         grad_y0 = lam + gys[0] if ctx.needs_input_grad[6] else None
         diffusion = PerceptronGradients.diffusion_gradients((row_rate, row_shift), ctx.param_shapes)
         return (None, None, None, None, None, None, grad_y0, sums.g_w1, sums.g_b1, sums.g_w2, sums.g_b2, *diffusion)
 
 
-def trajectory_mlp_diag_differentiable(y0, module_params, activation, diffusion, method, schedule_all, out_steps, bm):
+def trajectory_mlp_diag_differentiable(y0, module_params, activation, diffusion, method, schedule_all, out_steps, bm,
+                                       out_w=None):
     """ys (len(out_steps) + 1, rows, d) with a grad_fn towards y0 and the six parameters
-    (lin1.weight, lin1.bias, lin2.weight, lin2.bias, diff_rate, diff_shift)."""
-    return _MlpTrajectoryFn.apply(activation, tuple(diffusion), method, schedule_all, tuple(int(k) for k in out_steps),
-                                  bm, y0, *module_params)
+    (lin1.weight, lin1.bias, lin2.weight, lin2.bias, diff_rate, diff_shift). `out_w`: the outputs' interpolation weights
+    (`SolveSteps.out_w`); None: every output on boundary out_steps[i]."""
+    return _MlpTrajectoryFn.apply(activation, tuple(diffusion), method, schedule_all, OutputMap.cached(out_steps, out_w), bm,
+                                  y0, *module_params)
 
 
 def assemble_logqp_output(states, column, l0):
@@ -1412,8 +1509,10 @@ def assemble_logqp_output(states, column, l0):
 class _MlpLogqpTrajectoryFn(torch.autograd.Function):
     """`_MlpTrajectoryFn` for ``sdeint(..., logqp=True)``: the state has the KL column l as its last column
     (contract.check_contract), the prior drift is h = hr * y + hs (mlp_adjoint.plan_logqp_sdeint). Forward: the KL instantiation
-    of the sampling kernel on the every-step schedule (states and column at every boundary). Backward: the KL instantiation of
-    the reverse sweep over chunks of steps, last first, each followed by the two weight-gradient products over its stash.
+    of the sampling kernel on the every-step schedule (states and column at every boundary, and at the outputs inside steps:
+    `OutputMap`). Backward: the KL instantiation of the reverse sweep over chunks of steps, last first, each followed by the two
+    weight-gradient products over its stash; with outputs inside steps, ``tsde_trajectory_mlp_diag_logqp_backward_weighted``,
+    which splits the cotangents of state and column by the interpolation weights.
 
     Over the `STATE_BYTES` budget the forward launch keeps the states at chunk boundaries (and outputs) only, and the backward
     pass re-runs the KL sampling kernel over each chunk: the plain one cannot read a Brownian field of row stride d + 1.
@@ -1431,7 +1530,7 @@ class _MlpLogqpTrajectoryFn(torch.autograd.Function):
         return PerceptronGradients.chunk_length(n_steps, rows, d + 2 * hidden, _MlpLogqpTrajectoryFn.STASH_BYTES)
 
     @staticmethod
-    def forward(ctx, activation, diffusion, method, schedule_all, out_steps, bm, y0, w1, b1, w2, b2, rate, shift, hr_t, hs_t,
+    def forward(ctx, activation, diffusion, method, schedule_all, outputs, bm, y0, w1, b1, w2, b2, rate, shift, hr_t, hs_t,
                 hr, hs):
         from .mlp_adjoint import trajectory_mlp_diag_logqp
         rows, d = y0.shape[0], y0.shape[1] - 1
@@ -1441,30 +1540,25 @@ class _MlpLogqpTrajectoryFn(torch.autograd.Function):
         budget = _MlpLogqpTrajectoryFn.STATE_BYTES
         if budget is None:
             budget = torch.cuda.mem_get_info(y0.device)[0] // 2
-        if (n_steps + 1) * rows * (d + 1) * 4 <= budget:
-            kept_at = None                                  # states[k] is the state at boundary k
-            schedule = schedule_all
-        else:
-            chunk = _MlpLogqpTrajectoryFn._chunk(n_steps, rows, d, hidden)
-            marks = sorted(set(range(n_steps, 0, -chunk)) | set(out_steps))
-            kept_at = {0: 0}
-            kept_at.update((k, i + 1) for i, k in enumerate(marks))
-            schedule = TrajectorySchedule.cached(schedule_all.host_rows, schedule_all.host_cells, marks,
-                                                 [(0.0, 1.0)] * len(marks), y0.device, y0.dtype)
+        # (kept_at None: states[k] is the state at boundary k)
+        schedule, kept_at, out_rows, gather = _solve_layout(outputs, schedule_all, rows, d + 1, budget,
+                                                            _MlpLogqpTrajectoryFn._chunk(n_steps, rows, d, hidden), y0.device,
+                                                            y0.dtype)
         states = torch.empty((schedule.n_out + 1, rows, d), dtype=y0.dtype, device=y0.device)
         states[0].copy_(y0d[:, :d])
         column = torch.empty((schedule.n_out, rows), dtype=y0.dtype, device=y0.device)
         trajectory_mlp_diag_logqp(states[1:], column, states[0], *net, hr, hs, activation, diffusion, method, schedule, bm)
-        ctx.grad_step = _boundary_table(out_steps, y0.device)
+        # (stacks of views, not index_select: see _MlpTrajectoryFn.forward)
+        out_states = torch.stack([states[i] for i in out_rows], dim=0)
+        ys = assemble_logqp_output(out_states, torch.stack([column[i - 1] for i in out_rows[1:]], dim=0), y0d[:, d])
+        if gather is not None:          # the reverse sweep reads the boundary states one after the other (a remembered index)
+            states = states.index_select(0, gather)
         ctx.save_for_backward(states, *net, hr, hs)
         ctx.method, ctx.activation, ctx.hidden = int(method), int(activation), hidden
         ctx.diffusion = (int(diffusion[0]), float(diffusion[1]))
-        ctx.schedule, ctx.bm, ctx.out_steps, ctx.kept_at = schedule_all, bm, out_steps, kept_at
+        ctx.schedule, ctx.bm, ctx.outputs, ctx.kept_at = schedule_all, bm, outputs, kept_at
         ctx.param_shapes = (tuple(rate.shape), tuple(shift.shape))
-        # (stacks of views, not index_select: see _MlpTrajectoryFn.forward)
-        at = [k if kept_at is None else kept_at[k] for k in out_steps]
-        out_states = torch.stack([states[0]] + [states[i] for i in at], dim=0)
-        return assemble_logqp_output(out_states, torch.stack([column[i - 1] for i in at], dim=0), y0d[:, d])
+        return ys
 
     @staticmethod
     def backward(ctx, gys):
@@ -1478,7 +1572,10 @@ class _MlpLogqpTrajectoryFn(torch.autograd.Function):
         dev = states.device
         g_state = gys[:, :, :d].contiguous()
         g_column = gys[:, :, d].contiguous()
-        boundaries = np.asarray([0] + list(ctx.out_steps), dtype=np.int32)
+        boundaries = np.asarray((0,) + ctx.outputs.steps, dtype=np.int32)
+        grad_step, grad_w = ctx.outputs.grad_step(dev), ctx.outputs.grad_w(dev)
+        symbol = "tsde_trajectory_mlp_diag_logqp_backward" + ("" if grad_w is None else "_weighted")      # (as _MlpTrajectoryFn)
+        weights = () if grad_w is None else (grad_w.data_ptr(),)
         chunk = _MlpLogqpTrajectoryFn._chunk(n_steps, rows, d, hidden)
         sums = PerceptronGradients(rows, d, hidden, dev)
         stash_lam, stash_hid, stash_delta = sums.stashes(chunk, (d, hidden, hidden))
@@ -1501,14 +1598,14 @@ class _MlpLogqpTrajectoryFn(torch.autograd.Function):
                                           hs, ctx.activation, ctx.diffusion, ctx.method, schedule.window(k_lo, k_hi), bm)
                 ys, ys_first = rerun, k_lo
             grad_last = int(np.searchsorted(boundaries, k_hi, side="right")) - 1
-            code = lib.tsde_trajectory_mlp_diag_logqp_backward(
+            code = getattr(lib, symbol)(
                 lam.data_ptr(), a_l.data_ptr(), stash_lam.data_ptr(), stash_hid.data_ptr(), stash_delta.data_ptr(),
                 *(t.data_ptr() for t in row_sums), ys.data_ptr(), ys_first, g_state.data_ptr(), g_column.data_ptr(),
-                ctx.grad_step.data_ptr(), grad_last, rows, d, hidden, w1_in.data_ptr(), b1c.data_ptr(), w2_in.data_ptr(),
+                grad_step.data_ptr(), *weights, grad_last, rows, d, hidden, w1_in.data_ptr(), b1c.data_ptr(), w2_in.data_ptr(),
                 b2c.data_ptr(), rate.data_ptr(), shift.data_ptr(), hr.data_ptr(), hs.data_ptr(), ctx.diffusion[0],
                 ctx.diffusion[1], ctx.activation, ctx.method, d + 1,
                 *_native.sweep_tail(schedule, k_lo, k_hi, bm, dt_code, stream))
-            _native.check(code, "tsde_trajectory_mlp_diag_logqp_backward")
+            _native.check(code, symbol)
             sums.accumulate(n, stash_lam, stash_hid, stash_delta, ys[k_lo - ys_first:k_hi - ys_first])
         grad_y0 = None
         if ctx.needs_input_grad[_MlpLogqpTrajectoryFn.N_PLAIN]:

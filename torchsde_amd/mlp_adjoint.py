@@ -445,8 +445,8 @@ def plan_logqp(sde, y0, ts, bm, method, adjoint_method, dt, adaptive, adjoint_ad
 
 class LogqpSdeintRoute:
     """One ``sdeint(..., logqp=True)`` call's plan on the KL kernels (`plan_logqp_sdeint`), the interface of `LogqpRoute`.
-    With autograd recording: `kernels._MlpLogqpTrajectoryFn` (the KL sampling kernel at every step, then the KL reverse
-    sweep); without: one launch of the KL sampling kernel."""
+    With autograd recording: `kernels._MlpLogqpTrajectoryFn` (the KL sampling kernel at every step and at the outputs inside
+    steps, then the KL reverse sweep); without: one launch of the KL sampling kernel."""
 
     def __init__(self, solver, frame, args, recording, ledger, key, trusted, reverify):
         self.solver, self.frame, self.args, self.recording = solver, frame, args, recording
@@ -474,7 +474,8 @@ class LogqpSdeintRoute:
         verdict = self.solver._both_routes_agree(fast, stepwise, y0, what, network=True, extra_inputs=extra_inputs)
         self.ledger.file(self.key, verdict, self.reverify)
         if verdict is True:
-            self.ledger.name_kernel(self.key, "tsde_trajectory_mlp_diag_logqp + tsde_trajectory_mlp_diag_logqp_backward"
+            weighted = "_weighted (outputs inside steps)" if "interpolated outputs" in self.key else ""
+            self.ledger.name_kernel(self.key, "tsde_trajectory_mlp_diag_logqp + tsde_trajectory_mlp_diag_logqp_backward" + weighted
                                     if self.recording else "tsde_trajectory_mlp_diag_logqp")
         return verdict
 
@@ -500,11 +501,13 @@ def plan_logqp_sdeint(sde, y0, ts, bm, method, dt, adaptive, options, extra, ext
     on the stepwise solver). Conditions: everything `_logqp_frame` asks; Euler, or Milstein with the affine diffusion when
     autograd records (the reverse sweep has no sigmoid Milstein terms); no `adaptive`, `extra`, given `extra_solver_state`,
     ``options={"hip_graph": True}`` or ``options={"trajectory_kernel": False}``. With autograd recording (`y0` or a parameter
-    of the module requires a gradient) every output must sit on a step boundary, and every trainable parameter of the module
-    must be one of the six tensors or reached by the prior's coefficients: `kernels._MlpLogqpTrajectoryFn`. Without, outputs
-    inside steps are interpolated by the kernel. Trust as in `plan_logqp`, on keys of its own (..., "logqp", "backprop" |
-    "sampling", ...): the first solve of a key runs both routes and returns the stepwise result; TSDE_VERIFY_EVERY applies; no
-    verifying solve runs under stream capture."""
+    of the module requires a gradient) every trainable parameter of the module must be one of the six tensors or reached by
+    the prior's coefficients: `kernels._MlpLogqpTrajectoryFn`. Outputs inside steps are interpolated by the sampling kernel
+    either way; under autograd the reverse sweep splits their cotangents by the interpolation weights. Trust as in
+    `plan_logqp`, on keys of its own (..., "logqp", "backprop" | "sampling", ["interpolated outputs",] ...): the first solve of
+    a key runs both routes and returns the stepwise result -- a grid that interpolates an output under autograd has a key of
+    its own, so trust earned on an aligned grid does not cover it; TSDE_VERIFY_EVERY applies; no verifying solve runs under
+    stream capture."""
     from . import graph, recognise
     if (adaptive or extra or extra_solver_state is not None or method not in (METHODS.euler, METHODS.milstein)
             or options.get(METHOD_OPTIONS.grad_free, False) or not options.get("trajectory_kernel", True)
@@ -517,21 +520,24 @@ def plan_logqp_sdeint(sde, y0, ts, bm, method, dt, adaptive, options, extra, ext
     spec, steps, ledger = frame.spec, frame.steps, frame.ledger
     recording = torch.is_grad_enabled() and (y0.requires_grad or any(p.requires_grad for p in frame.module_params))
     if recording:
-        if not steps.on_boundaries or (spec[-1][0] == _native.DIFF_SIGMOID and code != _native.TRAJ_EULER):
+        if spec[-1][0] == _native.DIFF_SIGMOID and code != _native.TRAJ_EULER:
             return None
         hr_t, hs_t = recognise.prior_coefficient_graph(frame.inner.h, frame.t0, frame.d, y0.dtype, y0.device)
         reached = _leaves_reached((hr_t, hs_t)) | {id(p) for p in frame.own}
         if any(p.requires_grad and id(p) not in reached for p in frame.module_params):
             return None
-    key = ledger.key(frame.found, y0, "logqp", "backprop" if recording else "sampling", method, frame.shape_of(frame.hr),
-                     frame.shape_of(frame.hs))
+    # (a grid that interpolates an output under autograd runs the weighted reverse sweep and the merged forward launch: code
+    #  that trust earned on an aligned grid has not seen, so it earns its own)
+    interpolates = ("interpolated outputs",) if recording and not steps.on_boundaries else ()
+    key = ledger.key(frame.found, y0, "logqp", "backprop" if recording else "sampling", *interpolates, method,
+                     frame.shape_of(frame.hr), frame.shape_of(frame.hs))
     decided = frame.verdict(key, y0)
     if decided is None:
         return None
     verdict, reverify = decided
     if recording:
         args = (spec[-2], tuple(spec[-1]), code, steps.schedule(y0.device, y0.dtype, every_step=True),
-                tuple(int(k) for k in steps.out_step), bm)
+                K.OutputMap.cached(steps.out_step, steps.out_w), bm)
     else:
         args = (spec[-2], tuple(spec[-1]), code, steps.schedule(y0.device, y0.dtype), bm)
     return LogqpSdeintRoute(solver, frame, args, recording, ledger, key, verdict is True, reverify)

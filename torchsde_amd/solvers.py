@@ -962,11 +962,11 @@ class BaseSDESolver:
             return None
         kind = coefficients[0] if isinstance(coefficients[0], str) else "affine_diagonal"
         if kind == "mlp_differentiable":
-            if not steps.on_boundaries:
-                return None
+            # (outputs anywhere: the sampling kernel interpolates those inside steps, the reverse sweep splits their cotangents)
             schedule_all = steps.schedule(y0.device, y0.dtype, every_step=True)
             return K.trajectory_mlp_diag_differentiable(y0, coefficients[3:], coefficients[1], coefficients[2],
-                                                        self._trajectory_code(), schedule_all, steps.out_step, bm)
+                                                        self._trajectory_code(), schedule_all, steps.out_step, bm,
+                                                        out_w=steps.out_w)
         schedule = steps.schedule(y0.device, y0.dtype)
         if kind == "program_differentiable":
             _, f_code, g_code, dg_code, const_values, rows_with_grad, scalar_noise = coefficients

@@ -1305,6 +1305,244 @@ __global__ void __launch_bounds__(kBlock) trajectory_prog_sens_kernel(const Prog
   }
 }
 
+// ---- row-coupled systems and their path-wise sensitivities ---------------------------------------------------------------
+// Training THROUGH the solver for a small row-coupled system (torchsde_amd/recognise_rows.py: channels that read each other):
+// one lane owns a whole row, as in `trajectory_prog_kernel` with W = D and a generated model, and beside its D values it
+// carries NT tangent planes of D values -- d/dy0 of the row (D planes, when y0 needs a gradient), then one plane per trainable
+// scalar constant of the user's module. The planes are not diagonal: channel c depends on channel c' of y0. A generated model
+// (specialise.source_rows_sens) evaluates the system's statements on `Tan`, a scalar with NT tangents; the schemes run on
+// `RowTan`, a row of them stored plane by plane, with the Brownian increment a plain Vec<T, D>.
+template <typename T, int NT>
+struct Tan {
+  T v;
+  T d[NT];
+  Tan() = default;
+  TSDE_D explicit Tan(T value) : v(value) {
+#pragma unroll
+    for (int i = 0; i < NT; ++i) d[i] = (T)0;
+  }
+};
+// a constant whose own tangent slot K is 1: literal, so that the compiler folds the zeros of every other slot
+template <int K, typename T, int NT>
+TSDE_D Tan<T, NT> tan_seed(T value) {
+  Tan<T, NT> r(value);
+  r.d[K] = (T)1;
+  return r;
+}
+#define TSDE_TAN_LINEAR(OP)                                                                    \
+  template <typename T, int NT>                                                                \
+  TSDE_D Tan<T, NT> operator OP(const Tan<T, NT>& x, const Tan<T, NT>& y) {                    \
+    Tan<T, NT> r;                                                                              \
+    r.v = x.v OP y.v;                                                                          \
+    _Pragma("unroll") for (int i = 0; i < NT; ++i) r.d[i] = x.d[i] OP y.d[i];                  \
+    return r;                                                                                  \
+  }                                                                                            \
+  template <typename T, int NT>                                                                \
+  TSDE_D Tan<T, NT> operator OP(const Tan<T, NT>& x, T s) {                                    \
+    Tan<T, NT> r = x;                                                                          \
+    r.v = x.v OP s;                                                                            \
+    return r;                                                                                  \
+  }
+TSDE_TAN_LINEAR(+)
+TSDE_TAN_LINEAR(-)
+#undef TSDE_TAN_LINEAR
+template <typename T, int NT>
+TSDE_D Tan<T, NT> operator+(T s, const Tan<T, NT>& x) {
+  Tan<T, NT> r = x;
+  r.v = s + x.v;
+  return r;
+}
+template <typename T, int NT>
+TSDE_D Tan<T, NT> operator-(T s, const Tan<T, NT>& x) {
+  Tan<T, NT> r;
+  r.v = s - x.v;
+#pragma unroll
+  for (int i = 0; i < NT; ++i) r.d[i] = -x.d[i];
+  return r;
+}
+template <typename T, int NT>
+TSDE_D Tan<T, NT> operator*(const Tan<T, NT>& x, const Tan<T, NT>& y) {
+  Tan<T, NT> r;
+  r.v = x.v * y.v;
+#pragma unroll
+  for (int i = 0; i < NT; ++i) r.d[i] = x.d[i] * y.v + x.v * y.d[i];
+  return r;
+}
+template <typename T, int NT>
+TSDE_D Tan<T, NT> operator*(const Tan<T, NT>& x, T s) {
+  Tan<T, NT> r;
+  r.v = x.v * s;
+#pragma unroll
+  for (int i = 0; i < NT; ++i) r.d[i] = x.d[i] * s;
+  return r;
+}
+template <typename T, int NT>
+TSDE_D Tan<T, NT> operator*(T s, const Tan<T, NT>& x) {
+  Tan<T, NT> r;
+  r.v = s * x.v;
+#pragma unroll
+  for (int i = 0; i < NT; ++i) r.d[i] = s * x.d[i];
+  return r;
+}
+// (quotients as `Dual`'s: the tangent from the rounded quotient and one reciprocal)
+template <typename T, int NT>
+TSDE_D Tan<T, NT> operator/(const Tan<T, NT>& x, const Tan<T, NT>& y) {
+  Tan<T, NT> r;
+  const T inv = (T)1 / y.v;
+  r.v = x.v / y.v;
+#pragma unroll
+  for (int i = 0; i < NT; ++i) r.d[i] = (x.d[i] - r.v * y.d[i]) * inv;
+  return r;
+}
+template <typename T, int NT>
+TSDE_D Tan<T, NT> operator/(const Tan<T, NT>& x, T s) {
+  Tan<T, NT> r;
+  const T inv = (T)1 / s;
+  r.v = x.v / s;
+#pragma unroll
+  for (int i = 0; i < NT; ++i) r.d[i] = x.d[i] * inv;
+  return r;
+}
+template <typename T, int NT>
+TSDE_D Tan<T, NT> operator/(T s, const Tan<T, NT>& y) {
+  Tan<T, NT> r;
+  const T inv = (T)1 / y.v;
+  r.v = s / y.v;
+#pragma unroll
+  for (int i = 0; i < NT; ++i) r.d[i] = -(r.v * y.d[i]) * inv;
+  return r;
+}
+// phi(x) with derivative `slope` at x.v (the slope rules are those of the elementwise programs: specialise._DUAL_HELPERS)
+template <typename T, int NT>
+TSDE_D Tan<T, NT> chain(const Tan<T, NT>& x, T value, T slope) {
+  Tan<T, NT> r;
+  r.v = value;
+#pragma unroll
+  for (int i = 0; i < NT; ++i) r.d[i] = slope * x.d[i];
+  return r;
+}
+
+// A row's D values and NT tangent planes; what `scheme_step`, `drift_diffusion_update` and the SRID2 helpers do to a state:
+// sums of states, products with a step scalar (either side) and with the row's increments.
+template <typename T, int D, int NT>
+struct RowTan {
+  Vec<T, D> v;
+  Vec<T, D> t[NT];
+  RowTan() = default;
+  TSDE_D explicit RowTan(T s) : v(s) {
+#pragma unroll
+    for (int k = 0; k < NT; ++k) t[k] = Vec<T, D>((T)0);
+  }
+  // channel c as a scalar with its tangents, and back
+  TSDE_D Tan<T, NT> channel(int c) const {
+    Tan<T, NT> r;
+    r.v = v.v[c];
+#pragma unroll
+    for (int k = 0; k < NT; ++k) r.d[k] = t[k].v[c];
+    return r;
+  }
+  TSDE_D void set(int c, const Tan<T, NT>& x) {
+    v.v[c] = x.v;
+#pragma unroll
+    for (int k = 0; k < NT; ++k) t[k].v[c] = x.d[k];
+  }
+  TSDE_D void set(int c, T x) {
+    v.v[c] = x;
+#pragma unroll
+    for (int k = 0; k < NT; ++k) t[k].v[c] = (T)0;
+  }
+};
+template <typename T, int D, int NT>
+TSDE_D RowTan<T, D, NT> operator+(const RowTan<T, D, NT>& x, const RowTan<T, D, NT>& y) {
+  RowTan<T, D, NT> r;
+  r.v = x.v + y.v;
+#pragma unroll
+  for (int k = 0; k < NT; ++k) r.t[k] = x.t[k] + y.t[k];
+  return r;
+}
+template <typename T, int D, int NT>
+TSDE_D RowTan<T, D, NT> operator+(const RowTan<T, D, NT>& x, T s) {
+  RowTan<T, D, NT> r = x;
+  r.v = x.v + s;
+  return r;
+}
+// `N`: a step scalar T, or the row's increments Vec<T, D>
+template <typename T, int D, int NT, typename N>
+TSDE_D RowTan<T, D, NT> operator*(const RowTan<T, D, NT>& x, const N& s) {
+  RowTan<T, D, NT> r;
+  r.v = x.v * s;
+#pragma unroll
+  for (int k = 0; k < NT; ++k) r.t[k] = x.t[k] * s;
+  return r;
+}
+template <typename T, int D, int NT>
+TSDE_D RowTan<T, D, NT> operator*(T s, const RowTan<T, D, NT>& x) {
+  RowTan<T, D, NT> r;
+  r.v = s * x.v;
+#pragma unroll
+  for (int k = 0; k < NT; ++k) r.t[k] = s * x.t[k];
+  return r;
+}
+
+template <typename T>
+struct RowsSensArgs {
+  ProgArgs<T> base;         // consts: one scalar per constant (n_const of them); no programs, no scalar noise
+  T* sens;                  // (n_out, NT, rows, d)
+};
+
+// One lane per row; values AND sensitivities of every requested output. `M`: the generated model on RowTan<T, D, NT>;
+// `M::kStateSlots`: y0 carries the first D tangent slots. The increments, the step header and the stage times are those of
+// `trajectory_prog_kernel` with W = D, and the value part of every operation is that kernel's: the same `ys`, bit for bit.
+template <typename T, int METHOD, int D, int NT, typename M>
+__global__ void __launch_bounds__(kBlock) trajectory_rows_sens_kernel(const RowsSensArgs<T> q) {
+  constexpr bool kNeedU = METHOD == kSrk;
+  using V = Vec<T, D>;
+  using S = RowTan<T, D, NT>;
+  const ProgArgs<T>& p = q.base;
+  const int64_t lane = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int64_t i = lane * D;
+  if (i >= p.n) return;
+  const Pack<T, D> y_init = load<T, D>(p.y0, i);
+  S y((T)0);
+#pragma unroll
+  for (int c = 0; c < D; ++c) {
+    y.v.v[c] = y_init.v[c];
+    if constexpr (M::kStateSlots) y.t[c].v[c] = (T)1;
+  }
+  M m;
+  m.setup(p, 0);
+  const NoiseKey key = launch_key(p.key, p.key_dev);
+  const uint64_t elem = key.elem0 + (uint64_t)i;
+  int j = 0;
+  int next_out = next_output_step<false>(p.out_step, 0, p.n_out);
+  for (int k = 0; k < p.n_steps; ++k) {
+    const StepRow<T> r = step_row<false>(p.rows + (int64_t)k * 8, p.cells, k);
+    V w((T)0), u((T)0);
+    draw_increment<T, D, kNeedU, /*PAIRS=*/false>(PlainStepNoise(key, r.cell), r, elem, false, w.v, u.v);
+    stage_times<T, METHOD>(r.t0(), r.dt, m.tslot);
+    const S y1 = scheme_step<T, METHOD, S, M, V>(y, m, w, u, r.dt, r.half_dt, r.rdt, r.sqrt_dt);
+    if (__builtin_expect(k + 1 == next_out, 0)) {
+      while (j < p.n_out && p.out_step[j] == k + 1) {
+        const T w0 = p.out_w[2 * j], w1 = p.out_w[2 * j + 1];
+        const bool exact = (w0 == (T)0 && w1 == (T)1);
+        Pack<T, D> ov;
+#pragma unroll
+        for (int c = 0; c < D; ++c) ov.v[c] = exact ? y1.v.v[c] : (w0 * y.v.v[c] + w1 * y1.v.v[c]);
+        store<T, D>(p.ys + (int64_t)j * p.n, i, ov);
+#pragma unroll
+        for (int s = 0; s < NT; ++s) {
+#pragma unroll
+          for (int c = 0; c < D; ++c) ov.v[c] = exact ? y1.t[s].v[c] : (w0 * y.t[s].v[c] + w1 * y1.t[s].v[c]);
+          store<T, D>(q.sens + ((int64_t)j * NT + s) * p.n, i, ov);
+        }
+        ++j;
+      }
+      next_out = next_output_step<false>(p.out_step, j, p.n_out);
+    }
+    y = y1;
+  }
+}
+
 // ---- additive noise: the drift as a program, the diffusion as a table ---------------------------------------------------
 // Noise type "additive" (base_sde.py:101-102; the reference's ExAdditive, tests/problems.py:106-132): g depends on t only
 // and every batch row meets the same (d, m) matrix. The host evaluates the user's g at every stage time of the solve
@@ -1484,6 +1722,16 @@ template <typename T, int METHOD, int W, typename M = ProgModel<T, W>>
 static hipError_t launch_prog_w(const ProgArgs<T>& p, hipStream_t s) {
   if (nothing_to_do(p)) return hipSuccess;
   return launch_lanes(trajectory_prog_kernel<T, METHOD, W, M>, p.n / W, s, p);
+}
+
+// ... and with NT tangent planes per row (specialise.source_rows_sens); `sens`: (n_out, NT, rows, D)
+template <typename T, int METHOD, int D, int NT, typename M>
+static hipError_t launch_rows_sens(const ProgArgs<T>& p, void* sens, hipStream_t s) {
+  if (nothing_to_do(p)) return hipSuccess;
+  RowsSensArgs<T> q;
+  q.base = p;
+  q.sens = (T*)sens;
+  return launch_lanes(trajectory_rows_sens_kernel<T, METHOD, D, NT, M>, p.n / D, s, q);
 }
 
 template <typename T, int METHOD, template <typename, int> class M = ProgModel>

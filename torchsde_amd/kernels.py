@@ -1057,6 +1057,95 @@ def trajectory_prog_diag_differentiable(y0, programs, const_values, param_rows, 
                                    tuple(param_rows), y0, *params)
 
 
+# Budget for the sensitivities of a row-coupled solve, (n_out, NT, rows, d) in the state dtype: by the reasoning of the
+# perceptron kernels' `STATE_BYTES`, the one large array of a training step may take half of the device memory that is free
+# at forward time (None): the backward pass contracts it without a temporary of its size; a number fixes it
+# (tests/test_gpu_rows_grad.py).
+ROWS_SENS_BYTES = None
+
+
+def rows_sens_contract(gys, sens, d0, trainable, shapes):
+    """The backward pass of `_RowsTrajectoryFn` as torch reductions: `gys` (n_out + 1, rows, d) the cotangent of ys, `sens`
+    (n_out, NT, rows, d) the path-wise sensitivities of ys[1:], the first `d0` planes (d, or 0) those of y0's channels, the
+    rest one per trainable scalar, `trainable[k]` = (its source tensor's index, its flat element index there), `shapes` the
+    source tensors' shapes. Returns (grad y0 or None, [a gradient per source tensor]):
+        grad y0[r, c'] = gys[0][r, c'] + sum_{j, c} gys[j + 1][r, c] * sens[j, c', r, c]
+        grad scalar k  = sum_{j, r, c} gys[j + 1][r, c] * sens[j, d0 + k, r, c]
+    each scalar's gradient added into a zero tensor of its source's shape at its flat index."""
+    weighted = torch.einsum("jrc,jkrc->kr", gys[1:], sens)                    # (NT, rows); no temporary the size of `sens`
+    grad_y0 = gys[0] + weighted[:d0].t() if d0 else None
+    per_scalar = weighted[d0:].sum(dim=1)                                     # (number of trainable scalars,)
+    grads = []
+    for s, shape in enumerate(shapes):
+        numel = 1
+        for n in shape:
+            numel *= n
+        flat = torch.zeros(numel, dtype=sens.dtype, device=sens.device)
+        for k, (which, j) in enumerate(trainable):
+            if which == s:
+                flat[j] += per_scalar[k]
+        grads.append(flat.reshape(shape))
+    return grad_y0, grads
+
+
+class _RowsTrajectoryFn(torch.autograd.Function):
+    """Differentiable whole-trajectory solve of a small row-coupled system (recognise_rows.RecognisedRows): the forward launch
+    of the generated tangent unit (specialise.source_rows_sens) also writes the path-wise sensitivities of every output with
+    respect to the row's y0 and to the trainable scalars of the user's module, and the backward pass is `rows_sens_contract`:
+    a few reductions, no step stored or revisited."""
+
+    @staticmethod
+    def forward(ctx, compiled, schedule, bm, consts, trainable, y0_grad, y0, *sources):
+        from . import specialise
+        rows, d = y0.shape
+        y0c = _native.contiguous(y0.detach())
+        if y0c.data_ptr() % 16:
+            y0c = y0c.clone()
+        d0 = d if y0_grad else 0
+        ys = torch.empty((schedule.n_out + 1, rows, d), dtype=y0.dtype, device=y0.device)
+        sens = torch.empty((schedule.n_out, d0 + len(trainable), rows, d), dtype=y0.dtype, device=y0.device)
+        ys[0].copy_(y0c)
+        _, _, stream = _launch_env(y0c)
+        specialise.launch(compiled, schedule, bm, stream, ys[1:].data_ptr(), sens.data_ptr(), y0c.data_ptr(), rows, d,
+                          consts.data_ptr(), consts.numel())
+        ctx.save_for_backward(sens)
+        ctx.layout = (d0, tuple(trainable), [tuple(s.shape) for s in sources])
+        return ys
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gys):
+        sens, = ctx.saved_tensors
+        d0, trainable, shapes = ctx.layout
+        grad_y0, grads = rows_sens_contract(gys, sens, d0, trainable, shapes)
+        grads = [g if ctx.needs_input_grad[7 + s] else None for s, g in enumerate(grads)]
+        return (None,) * 6 + (grad_y0 if ctx.needs_input_grad[6] else None,) + tuple(grads)
+
+
+def trajectory_rows_differentiable(y0, found, method, schedule, bm):
+    """ys (n_out + 1, rows, d) with a grad_fn towards y0 and the source tensors of `found` (a differentiable
+    recognise_rows.RecognisedRows) through the generated tangent unit -- or None: the unit is not compiled yet (there is no
+    interpreter for such systems), or the sensitivities would not fit `ROWS_SENS_BYTES`. The caller stays stepwise."""
+    from . import specialise
+    rows, d = y0.shape
+    y0_grad = bool(y0.requires_grad)
+    consts = found.const_table()
+    _native.require_device(y0, consts)
+    if schedule.dtype != y0.dtype or consts.dtype != y0.dtype:
+        raise ValueError("the schedule and the constants must have the state dtype")
+    nt = (d if y0_grad else 0) + len(found.trainable)
+    budget = ROWS_SENS_BYTES
+    if budget is None:
+        budget = torch.cuda.mem_get_info(y0.device)[0] // 2
+    if schedule.n_out * nt * rows * d * y0.element_size() > budget:
+        return None
+    structure = found.structure()
+    key, compiled = specialise.lookup_rows_sens(structure, structure[1][1], y0.dtype, method, found.slots(), y0_grad, y0.device)
+    if compiled is None:
+        return None
+    return _RowsTrajectoryFn.apply(compiled, schedule, bm, consts, tuple(found.trainable), y0_grad, y0, *found.sources)
+
+
 def trajectory_mlp_diag(ys, y0, w1, b1, w2, b2, diff_rate, diff_shift, activation, diffusion, method, schedule, bm):
     """All steps of a diagonal SDE with a two-layer perceptron drift in one launch (``tsde_trajectory_mlp_diag``);
     writes ys[j] for the schedule's outputs (an output time inside a step is interpolated in the kernel with the

@@ -17,6 +17,11 @@ for such systems: the route exists once the generated unit is compiled (4 s, in 
 stepwise), and is trusted like every recognised route only after its first solve reproduced the stepwise one.
 
 Schemes: those of the program kernel that need no derivative of g -- Euler, midpoint, Heun, Euler-Heun, SRK.
+
+With autograd recording (`recognise_rows(..., differentiable=True)`, solvers._integrate_rows_with_grad) the same interpretation
+runs under `enable_grad` on a probe that requires grad, and every scalar constant remembers the tensor the user's code handed to
+its operator: `RecognisedRows.sources`, `.trainable`, `.slots()`. specialise.source_rows_sens then generates the same statements
+on scalars with tangents, and the launch writes the path-wise sensitivities of every output (kernels._RowsTrajectoryFn).
 """
 import torch
 from torch.utils._python_dispatch import TorchDispatchMode
@@ -44,7 +49,8 @@ class _Columns(TorchDispatchMode):
         self.flat = set()           # ids of tracked values of shape (rows,) (a column without its unit axis)
         self.scalar_like = set()    # ids of 0-d functions of t (they broadcast against either kind)
         self.made = {id(y), id(t)}  # ids of tensors whose storage was allocated during the interpretation
-        self.differentiable = False
+        self.differentiable = False # True: the kernel's GRADIENTS will stand for autograd through this code (recognise_rows)
+        self.sources = {}           # differentiable: id(a scalar constant) -> (the operand the code handed over, flat index)
 
     def track(self, tensor, cols, flat=False):
         want = (self.rows,) if flat else (self.rows, len(cols))
@@ -71,12 +77,20 @@ class _Columns(TorchDispatchMode):
             return [_const(float(x))] * k
         if torch.is_tensor(x):
             if x.numel() == 1:
-                return [_const(x.reshape(()))] * k
+                return [self.scalar_of(x, x.reshape(()), 0)] * k
             if x.dim() <= 2 and x.shape[-1] == k and x.numel() == k:
                 flat = x.reshape(-1)
-                return [_const(flat[j]) for j in range(k)]
+                return [self.scalar_of(x, flat[j], j) for j in range(k)]
             raise NotElementwise(f"an operand of shape {tuple(x.shape)} beside columns of the state")
         raise NotElementwise(f"an operand of type {type(x).__name__}")
+
+    def scalar_of(self, x, element, j):
+        """The constant `element` = element j of operand x. The slice is made below autograd and carries no graph; the
+        differentiable interpretation therefore remembers the operand itself -- a parameter, or what autograd saw the code
+        derive from parameters -- which still has its `grad_fn` here."""
+        if self.differentiable:
+            self.sources[id(element)] = (x, j)
+        return _const(element)
 
     def __torch_dispatch__(self, func, types, args=(), kwargs=None):
         kwargs = kwargs or {}
@@ -220,6 +234,9 @@ class _Columns(TorchDispatchMode):
         return self.track(out, self.elementwise(name, args, kwargs, k, out), flat=flat)
 
     def elementwise(self, name, args, kwargs, k, out):
+        if name in ("clamp", "clamp_min") and self.differentiable:
+            # (as the program route, recognise.py: torch's clamp passes the gradient AT the boundary, the kernels' relu does not)
+            raise NotElementwise("clamp with autograd recording: its backward passes the gradient at the boundary, relu's does not")
         if name in _UNARY and len(args) == 1:
             return [_Expr(name, (c,)) for c in self.columns_of(args[0], k)]
         if name == "softplus":
@@ -256,10 +273,31 @@ class RecognisedRows:
     perceptron = neural = timed = False
     exact = False
 
-    def __init__(self, f, g, d, dtype, device):
+    def __init__(self, f, g, d, dtype, device, sources=None):
         self.f, self.g, self.d, self.dtype, self.device = list(f), list(g), d, dtype, device
         self.consts = []            # scalar constants in order of first use: numbers, or 0-d tensors (live values)
         self.statements, self.outputs = self._linearise()
+        # the differentiable interpretation (`recognise_rows(..., differentiable=True)`): where the constants come from
+        self.sources = []           # the distinct operand tensors with requires_grad that constants were taken from
+        self.trainable = []         # the trainable scalars, in tangent-slot order: (index into `sources`, flat element index)
+        self.const_slot = {}        # index into `consts` -> index into `trainable`
+        self.untrainable = None     # why the constants cannot carry gradients, if they cannot
+        for k, c in enumerate(self.consts):
+            x, j = (sources or {}).get(id(c), (None, 0))
+            if x is None or not x.requires_grad:
+                continue
+            if not x.is_floating_point() or x.dtype != dtype or x.device != device:
+                self.untrainable = f"a trainable constant of dtype {x.dtype} on {x.device} beside a state of {dtype} on {device}"
+                continue
+            for s, have in enumerate(self.sources):
+                if have is x:
+                    break
+            else:
+                self.sources.append(x)
+                s = len(self.sources) - 1
+            if (s, j) not in self.trainable:
+                self.trainable.append((s, j))
+            self.const_slot[k] = self.trainable.index((s, j))
 
     def _linearise(self):
         """Every distinct node once, in evaluation order: [(name, op, operand names)], and the 2 d output names."""
@@ -309,6 +347,29 @@ class RecognisedRows:
     def spec(self):
         return ("program_rows", self.structure(), self.const_table(), self.d)
 
+    def slots(self):
+        """Per constant its tangent slot among the trainable scalars, or -1: part of the generated tangent unit's key."""
+        return tuple(self.const_slot.get(k, -1) for k in range(len(self.consts)))
+
+    def reaches(self, params):
+        """Whether every tensor of `params` that requires grad is reached through `sources` -- is one of them, or a leaf of
+        the graph autograd recorded on the way to one (as solvers._integrate_program_with_grad asks of its constants): a
+        parameter that is not would lose its gradient on the kernel route."""
+        reached = set()
+        for x in self.sources:
+            stack, seen = [x.grad_fn], set()
+            if x.is_leaf:
+                reached.add(id(x))
+            while stack:
+                fn = stack.pop()
+                if fn is None or id(fn) in seen:
+                    continue
+                seen.add(id(fn))
+                if hasattr(fn, "variable"):
+                    reached.add(id(fn.variable))
+                stack.extend(nxt for nxt, _ in fn.next_functions)
+        return all(id(p) in reached for p in params if p.requires_grad)
+
 
 def recognise_rows(sde, t, y0, rows=None, differentiable=False):
     """`RecognisedRows` for a diagonal-noise SDE whose f and g do arithmetic among the columns of the state, or NotElementwise."""
@@ -320,9 +381,14 @@ def recognise_rows(sde, t, y0, rows=None, differentiable=False):
         raise NotElementwise(f"a row-coupled system of more than {MAX_D} channels")
     probe = y0.detach()[:1].expand(rows, d).clone() if y0.shape[0] > 0 else torch.zeros(rows, d, dtype=y0.dtype, device=y0.device)
     t_probe = t.detach().clone()
+    if differentiable:
+        probe.requires_grad_(True)               # (so that a stop-gradient in the user's code shows: `_Columns.follow`)
     interp = _Columns(probe, t_probe, rows, d)
+    interp.differentiable = bool(differentiable)
     try:
-        with torch.no_grad(), interp:
+        # `differentiable`: autograd watches the user's own constant arithmetic, so that a constant which is derived from
+        # parameters carries its graph back to them (cf. recognise.recognise_program)
+        with (torch.enable_grad() if differentiable else torch.no_grad()), interp:
             f, g = sde.f_and_g(t_probe, probe)
     except NotElementwise:
         raise
@@ -333,7 +399,9 @@ def recognise_rows(sde, t, y0, rows=None, differentiable=False):
         cols = interp.cols.get(id(value)) if torch.is_tensor(value) else None
         if cols is None or id(value) in interp.flat or len(cols) != d or tuple(value.shape) != (rows, d):
             raise NotElementwise(f"the {name} is not a (rows, d) value assembled from columns of the state")
+        if differentiable and not value.requires_grad and any(c.mentions_state() for c in cols):
+            raise NotElementwise(f"a stop-gradient on a value derived from the state (the {name})")
         out.append(cols)
-    found = RecognisedRows(out[0], out[1], d, y0.dtype, y0.device)
+    found = RecognisedRows(out[0], out[1], d, y0.dtype, y0.device, interp.sources if differentiable else None)
     found._alive = interp.keep
     return found

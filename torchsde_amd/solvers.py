@@ -763,7 +763,8 @@ class BaseSDESolver:
             found = recognise.recognise_program(sde, ts[0], y0, sde.noise_type, differentiable=True)
             spec = found.spec(milstein)
         except recognise.NotElementwise:
-            return None
+            # channels that read each other: a small row-coupled system on its generated tangent unit
+            return self._integrate_rows_with_grad(y0, ts, ledger)
         rows = found.trainable_rows(None)
         if rows is None:
             return None
@@ -801,6 +802,67 @@ class BaseSDESolver:
                         reverify)
             return None
         return self._verify_with_grad(ledger, key, reverify, launch, y0, ts, "the program sensitivity kernel")
+
+    def _integrate_rows_with_grad(self, y0, ts, ledger):
+        """`_integrate_program_with_grad` for a small ROW-COUPLED system (recognise_rows.py) under the conditions of its
+        forward route -- diagonal noise, a scheme without the diffusion's derivative, d <= MAX_D: the generated tangent unit
+        (specialise.source_rows_sens; `tsde_specialised_rows_sens_launch`) carries d/dy0 of the row and one tangent per
+        trainable scalar of the user's module in registers; gradients land on the tensors the user's code handed to its
+        operators. A system over the size rule (specialise.rows_sens_refusal) stays stepwise, the reason in the book."""
+        from . import recognise, recognise_rows, specialise
+        sde = self.sde
+        code = self._program_code()
+        if (sde.noise_type != NOISE_TYPES.diagonal or code in (_native.TRAJ_MILSTEIN_ITO, _native.TRAJ_MILSTEIN_STRAT)
+                or y0.shape[1] > recognise_rows.MAX_D):
+            return None
+        if ledger.remembers("not_rows"):
+            return None     # (a training loop does not pay for the interpretation at every step; the reason is in the book)
+        try:
+            found = recognise_rows.recognise_rows(sde, ts[0], y0, differentiable=True)
+        except recognise.NotElementwise as e:
+            # (the forward route, which takes `detach` and `clamp`, may hold this code: the reason is filed apart from its book)
+            ledger.remember("not_rows")
+            ledger.note_autograd(f"as a row-coupled system: {e}")
+            return None
+        # every trainable parameter of the module must be reached through the constants' sources, or its gradient would be lost
+        if found.untrainable is not None:
+            ledger.note_autograd(found.untrainable)
+            return None
+        if not found.reaches(self._params()):
+            ledger.note_autograd("a trainable parameter of the module is not reached through the constants of drift and "
+                                 "diffusion: its gradient would be lost on the tangent kernel")
+            return None
+        ledger.note_autograd(None)
+        nt = specialise.rows_sens_tangents(found.d, found.slots(), y0.requires_grad)
+        if nt < 1:
+            return None
+        key = ledger.key(found, y0, "autograd", found.slots(), bool(y0.requires_grad))
+        verdict, reverify = ledger.verdict(key)
+        if verdict is None and not reverify:
+            too_large = specialise.rows_sens_refusal(found.d, nt, code, y0.dtype)
+            if too_large is not None:
+                ledger.file(key, too_large)
+                return None
+        launch = ("program_rows_differentiable", found)
+        if verdict is True:
+            return self._integrate_trajectory(launch, y0, ts)
+        if verdict is not None:
+            return None
+        try:
+            again = recognise_rows.recognise_rows(sde, ts[0], y0, rows=5, differentiable=True)
+        except recognise.NotElementwise:
+            return None
+        if (again.structure() != found.structure() or not torch.equal(again.const_table(), found.const_table())
+                or again.trainable != found.trainable or again.slots() != found.slots()
+                or len(again.sources) != len(found.sources)
+                or any(a is not b and (a.shape != b.shape or not torch.equal(a.detach(), b.detach()))
+                       for a, b in zip(again.sources, found.sources))):
+            ledger.file(key, "two interpretations of the same code (probes of 2 and 5 rows) gave different systems", reverify)
+            return None
+        ys = self._verify_with_grad(ledger, key, reverify, launch, y0, ts, "the row-coupled tangent kernel")
+        if ys is not None:
+            ledger.name_kernel(key, "tsde_specialised_rows_sens_launch")
+        return ys
 
     def _verify_with_grad(self, ledger, key, reverify, launch, y0, ts, what):
         """The verifying solve of a sensitivity-kernel route: both routes, compared and filed; the stepwise result (recorded
@@ -968,6 +1030,9 @@ class BaseSDESolver:
                                                         self._trajectory_code(), schedule_all, steps.out_step, bm,
                                                         out_w=steps.out_w)
         schedule = steps.schedule(y0.device, y0.dtype)
+        if kind == "program_rows_differentiable":
+            # (None: the generated unit is still compiling, or the sensitivities exceed their budget -- stepwise for now)
+            return K.trajectory_rows_differentiable(y0, coefficients[1], self._program_code(), schedule, bm)
         if kind == "program_differentiable":
             _, f_code, g_code, dg_code, const_values, rows_with_grad, scalar_noise = coefficients
             return K.trajectory_prog_diag_differentiable(y0, (f_code, g_code, dg_code), const_values, rows_with_grad,

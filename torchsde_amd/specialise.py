@@ -143,6 +143,9 @@ _ENTRY = {
                  "const void* gtab, int time_dependent", [_P, _P, _I64, _I64, _I64, _P, _INT, _P, _INT]),
     "rows": ("tsde_specialised_rows_launch", "void* ys, const void* y0, int64_t rows, int64_t d, const void* consts, int n_const",
              [_P, _P, _I64, _I64, _P, _INT]),
+    "rows_sens": ("tsde_specialised_rows_sens_launch",
+                  "void* ys, void* sens, const void* y0, int64_t rows, int64_t d, const void* consts, int n_const",
+                  [_P, _P, _P, _I64, _I64, _P, _INT]),
 }
 
 
@@ -431,3 +434,119 @@ def source_rows(structure, n_const, dtype, method):
 def lookup_rows(structure, n_const, dtype, method, device, wait=None):
     """(key, library or None) of a row-coupled system (`_find`)."""
     return _find(lambda: source_rows(structure, n_const, dtype, method), "rows", device, wait)
+
+
+# ---- ... and their path-wise sensitivities (csrc/trajectory.hip trajectory_rows_sens_kernel) ----------------------------------
+def rows_sens_tangents(d, slots, y0_grad):
+    """NT of a tangent unit: the row's d slots for y0 (if it needs a gradient), then one per trainable scalar."""
+    return (d if y0_grad else 0) + (max(slots) + 1 if slots and max(slots) >= 0 else 0)
+
+
+def _row_tangent_helpers():
+    """The slope rules of the elementwise programs (`_DUAL_HELPERS`, ProgSensModel::run) for `Tan<T, NT>`: the one table,
+    retyped."""
+    return _DUAL_HELPERS.replace("template <typename T>", "template <typename T, int NT>").replace("Dual<T>", "Tan<T, NT>")
+
+
+def source_rows_sens(structure, n_const, dtype, method, slots, y0_grad):
+    """The translation unit of a row-coupled system WITH tangents: the statements of `source_rows` in the same order, each
+    scalar node a value plus NT tangents (`Tan<T, NT>`) wherever the state or a trainable constant reaches it -- nodes they do
+    not reach stay plain `T`, statement for statement what `source_rows` emits. `slots[k]`: the tangent slot of constant k among
+    the trainable scalars, or -1; `y0_grad`: the state's channels carry the first d slots. The value part of every dual
+    operation is the plain statement's expression (trajectory.hip `Tan`, `_DUAL_HELPERS`), hence the same `ys`."""
+    (_, d, statements, outputs), _ = structure
+    slots = tuple(int(s) for s in slots)
+    d0 = d if y0_grad else 0
+    nt = rows_sens_tangents(d, slots, y0_grad)
+    if nt < 1:
+        raise ValueError("a tangent unit needs a gradient to carry")
+    names = [f"n{k}" for k in range(len(statements))]
+    needs = {name: set(o for o in operands if o.startswith("n")) for name, (op, operands) in zip(names, statements)}
+    dual = {}                    # statement name -> whether it carries tangents
+
+    def is_dual(o):
+        if o.startswith("x.v["):
+            return True
+        if o.startswith("c["):
+            k = int(o[2:-1])
+            return k < len(slots) and slots[k] >= 0
+        return dual.get(o, False)
+
+    def spell(o):
+        if o.startswith("x.v["):
+            return f"x{int(o[4:-1])}"
+        if o.startswith("c[") and is_dual(o):
+            return f"k{int(o[2:-1])}"
+        return o
+    for name, (op, operands) in zip(names, statements):
+        dual[name] = any(is_dual(o) for o in operands)
+
+    def body(outs):
+        wanted, stack = set(), [o for o in outs if o.startswith("n")]
+        while stack:
+            x = stack.pop()
+            if x in wanted:
+                continue
+            wanted.add(x)
+            stack.extend(needs.get(x, ()))
+        used = [(name, op, operands) for name, (op, operands) in zip(names, statements) if name in wanted]
+        leaves = [o for _, _, operands in used for o in operands] + list(outs)
+        lines = [f"    const N x{c} = x.channel({c});" for c in range(d) if f"x.v[{c}]" in leaves]
+        lines += [f"    const N k{k} = tan_seed<{d0 + slots[k]}, T, {nt}>(c[{k}]);" for k in range(len(slots))
+                  if slots[k] >= 0 and f"c[{k}]" in leaves]
+        for name, op, operands in used:
+            if not dual[name]:
+                lines.append(f"    const T {name} = {_ROW_OPS[op].format(*operands)};")
+            elif len(operands) == 1:
+                lines.append(f"    const N {name} = d_{op}({spell(operands[0])});")
+            else:
+                lines.append(f"    const N {name} = {_ROW_OPS[op].format(*[spell(o) for o in operands])};")
+        lines.append("    S r;")
+        lines += [f"    r.set({c}, {spell(o)});" for c, o in enumerate(outs)]
+        lines.append("    return r;")
+        return "\n".join(lines)
+    nc = max(1, n_const)
+    setup = f"""  static constexpr bool kStateSlots = {"true" if y0_grad else "false"};
+  TSDE_D void setup(const ProgArgs<T>& p, int64_t) {{
+    _Pragma("unroll") for (int k = 0; k < {nc}; ++k) c[k] = k < p.n_const ? p.consts[k] : (T)0;
+  }}
+"""
+    model = _row_tangent_helpers() + _model("template <typename T>\nstruct RowSensModel", f"S = RowTan<T, {d}, {nt}>",
+                                            f"  using N = Tan<T, {nt}>;\n  T c[{nc}];\n", setup,
+                                            {"f": body(list(outputs[:d])), "g": body(list(outputs[d:]))}, "const Vec<T, " + str(d) + ">&")
+    return _unit(f" (a row-coupled system with {nt} tangents)", model, "rows_sens", dtype, method,
+                 f"d != {d} || n_const > {nc} || sens == nullptr", "0",
+                 f"launch_rows_sens<T, METHOD, {d}, {nt}, RowSensModel<T>>(p, sens, s)")
+
+
+def lookup_rows_sens(structure, n_const, dtype, method, slots, y0_grad, device, wait=None):
+    """(key, library or None) of a row-coupled system's tangent unit (`_find`)."""
+    return _find(lambda: source_rows_sens(structure, n_const, dtype, method, slots, y0_grad), "rows_sens", device, wait)
+
+
+# Which systems take the tangent unit. A lane keeps d * (NT + 1) numbers per state and a scheme keeps several states alive
+# (SRK: the stages' drifts and diffusions); past a size the compiler spills them and the launch loses to the stepwise route.
+# Per scheme and dtype, a cap on d * (NT + 1) that lies below the first worst-case unit OF ANY d = 2 .. 8 -- a dense synthetic
+# system, every drift and diffusion channel reading every state channel and a trainable constant -- that compiles for gfx950
+# with scratch or spilled vector registers (tools/rows_sens_resource_usage.py, profiles/rows_sens_resource_usage.txt: every
+# admitted (d, NT) is listed there and fits); NT <= 16 throughout. float64 takes two registers per number. The narrow rows set
+# several float32 caps: the register allocator does worse at d = 5 and 7 than at 8 (SRK spills at 5 x 3 and not at 6 x 4).
+ROWS_SENS_MAX_TANGENTS = 16
+ROWS_SENS_CAP = {      # method code -> cap on d * (NT + 1) in (float32, float64)
+    _native.TRAJ_EULER: (84, 32), _native.TRAJ_MIDPOINT: (69, 32), _native.TRAJ_HEUN: (56, 16),
+    _native.TRAJ_EULER_HEUN: (55, 24), _native.TRAJ_SRK: (14, 16),
+}
+
+
+def rows_sens_refusal(d, nt, method, dtype):
+    """Why a system of d channels with nt tangents stays stepwise under this scheme, or None."""
+    cap = ROWS_SENS_CAP.get(int(method))
+    if cap is None:
+        return "no tangent kernel for this scheme"
+    cap = cap[0 if dtype == torch.float32 else 1]
+    if nt > ROWS_SENS_MAX_TANGENTS:
+        return f"{nt} tangents per row (y0's channels and the trainable scalars), more than {ROWS_SENS_MAX_TANGENTS}"
+    if d * (nt + 1) > cap:
+        return (f"{d} channels x ({nt} tangents + 1) = {d * (nt + 1)} numbers per state, more than the {cap} this scheme keeps "
+                "in registers")
+    return None

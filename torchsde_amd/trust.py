@@ -8,7 +8,9 @@ the verdict. The book lives on the user's SDE object, ``base.__dict__["_tsde_rec
 
 - "refused": {(Python-side state, wrapper chain, who): reason}, at most 16 entries
 - "trusted": {(structure, chain, solver name, sde_type, d, dtype, batch, *tags): True | reason}, at most 32 entries
-- "program", "uses_t": (chain, solver name) of code known to end as an expression program / to use t (solvers._interpret)
+- "program", "uses_t": (chain, solver name) of code known to end as an expression program / to use t (solvers._interpret);
+  "not_rows": of code the differentiable column interpretation does not hold (solvers._integrate_rows_with_grad);
+  "autograd": {(chain, solver name): why solves stay stepwise while autograd records}
 - "counter_rate": {key: {call counter: advance per step}}, "solves": {key: solves since the last check}, pruned with "trusted"
 """
 import torch
@@ -179,11 +181,20 @@ class Ledger:
         return self.book.get("counter_rate", {}).get(key)
 
     def remembers(self, finding):
-        """Whether this code was found to be `finding` ("program" or "uses_t") by this scheme before."""
+        """Whether this code was found to be `finding` ("program", "uses_t" or "not_rows") by this scheme before."""
         return self.book.get(finding) == (self.chain, self._solver_name)
 
     def remember(self, finding):
         self.book[finding] = (self.chain, self._solver_name)
+
+    def note_autograd(self, reason):
+        """Why this scheme's solves of the object stay stepwise while autograd records (None: no reason any more). Kept apart
+        from "refused": the forward route, under no_grad, may well hold the same code."""
+        notes = self.book.setdefault("autograd", {})
+        if reason is None:
+            notes.pop((self.chain, self._solver_name), None)
+        else:
+            notes[(self.chain, self._solver_name)] = reason
 
 
 def book_of(sde):
@@ -206,14 +217,20 @@ def describe(sde):
         structure, _, solver, sde_type, d, dtype, batch = key[:7]
         kind = ("perceptron drift" if structure[0][0] == "perceptron"
                 else f"expression program, {structure[0][1]} noise" if structure[0][0] == "program"
+                else f"row-coupled system of {structure[0][1]} channels" if structure[0][0] == "rows"
                 else f"f: {structure[0][0]}, g: {structure[1][0]}")
         timed = any("table" in part for part in structure if isinstance(part, tuple))
         route = ("trajectory kernel" + (" with per-stage-time coefficient rows" if timed else "")
                  + (" (sensitivity kernel: autograd)" if key[7:] == ("autograd",) else "")
+                 + (" (generated tangent unit: autograd, "
+                    f"{len(set(s for s in key[8] if s >= 0)) + (structure[0][1] if key[9] else 0)} tangents per row)"
+                    if structure[0][0] == "rows" and key[7:8] == ("autograd",) else "")
                  + (f" ({book['kernel'][key]})" if key in book.get("kernel", {}) else "")
                  + (" (derivative-free Milstein)" if "grad_free" in key[7:] else ""))
         lines.append(f"[{solver}, {sde_type}, batch = {batch}, d = {d}, {dtype}] {kind}: "
                      + (route if verdict is True else f"stays stepwise: {verdict}"))
     for (_, _, solver), reason in book["refused"].items():
         lines.append(f"[{solver}] stays stepwise: {reason}")
+    for (_, solver), reason in book.get("autograd", {}).items():
+        lines.append(f"[{solver}] with autograd recording stays stepwise: {reason}")
     return lines

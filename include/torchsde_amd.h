@@ -151,7 +151,8 @@ int tsde_step_diag(void* y1, const void* y0, const void* f, const void* g, int64
 int tsde_step_prod(void* y1, const void* y0, const void* f, const void* gp, int64_t n, double cf, double cg,
                    int dtype, void* stream);
 
-/* y1 = (y0 + cf*f) + cg*(g . dW)        g:(B,d,m), dW:(B,m); general / additive / scalar noise. */
+/* y1 = (y0 + cf*f) + cg*(g . dW)        g:(B,d,m), dW:(B,m); general / additive / scalar noise.
+ * B == 0 or d == 0: nothing to do, whatever the pointers (also tsde_step_general_w). 1 <= m <= 2048. */
 int tsde_step_general(void* y1, const void* y0, const void* f, const void* g, int64_t B, int64_t d, int64_t m,
                       double cf, double cg, const tsde_noise_t* noise, int dtype, void* stream);
 
@@ -260,7 +261,8 @@ int tsde_rheun_adj_b_diag(void* ay1, void* az1, void* af1, void* ag1, const void
 
 /* ---- adjoint, output ------------------------------------------------------------------------ */
 
-/* For each segment: out = ((s + sF*(F*cF)) + sG*(cG*G)) + sD*D   (absent terms skipped). */
+/* For each segment: out = ((s + sF*(F*cF)) + sG*(cG*G)) + sD*D   (absent terms skipped; segments with n <= 0 too).
+ * One launch per 24 non-empty segments, each of them a launch of its own to tsde_prof_begin(TSDE_KID_AUG_UPDATE, ...). */
 int tsde_aug_update(const tsde_seg_t* segs, int nseg, double cF, double cG, int dtype, void* stream);
 
 /* out = w0*ya + w1*yb */

@@ -205,6 +205,7 @@ int tsde_step_general(void* y1, const void* y0, const void* f, const void* g, in
 int tsde_step_general_w(void* y1, const void* y0, const void* f, const void* g, int64_t B, int64_t d, int64_t m,
                         double ca, double cf, double cg, int weight_mode, double cw, double cu, double rdt,
                         const tsde_noise_t* noise, int dtype, void* stream) {
+  if (B == 0 || d == 0) return 0;      // an empty batch has no operands to point at (and nothing to launch)
   if (const char* bad = weighted_step_problem(y1, y0, f, g, weight_mode, noise)) return bad_arg("tsde_step_general", bad);
   const hipStream_t s = (hipStream_t)stream;
   ProfScope p(TSDE_KID_STEP_GENERAL, s, true);
@@ -373,8 +374,21 @@ int tsde_aug_update(const tsde_seg_t* segs, int nseg, double cF, double cG, int 
   for (int i = 0; i < nseg; ++i) {
     if (segs[i].n > 0 && (!segs[i].out || !segs[i].s)) return bad_arg("tsde_aug_update", "segment without state");
   }
-  ProfScope p(TSDE_KID_AUG_UPDATE, s, true);
-  return fail(tsde::launch_aug_segments(dtype, segs, nseg, cF, cG, s), "tsde_aug_update");
+  // kAugMaxSeg segments go into one launch; a longer list (a module with more parameter tensors) takes several, each
+  // counted and timed as the launch it is
+  int done = 0;
+  while (done < nseg) {
+    if (segs[done].n <= 0) {
+      ++done;
+      continue;
+    }
+    ProfScope p(TSDE_KID_AUG_UPDATE, s, true);
+    int taken = 0;
+    const hipError_t e = tsde::launch_aug_segments(dtype, segs + done, nseg - done, cF, cG, s, &taken);
+    if (e != hipSuccess) return fail(e, "tsde_aug_update");
+    done += taken;
+  }
+  return 0;
 }
 
 int tsde_linear_interp(void* out, const void* ya, const void* yb, int64_t n, double w0, double w1, int dtype,

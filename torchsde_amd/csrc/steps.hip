@@ -794,33 +794,33 @@ hipError_t launch_srk_stage(int dtype, int stage, void* const out[3], const void
   });
 }
 
-hipError_t launch_aug_segments(int dtype, const tsde_seg_t* segs, int nseg, double cF, double cG, hipStream_t s) {
+// ONE launch: the leading segments of the list, up to kAugMaxSeg non-empty ones (and the empty ones among and right behind
+// them); `*taken` says how many entries that was. The entry point calls again for the rest, so that each launch is a
+// launch of its own to the profiler too (capi.hip: ProfScope arms one dispatch).
+hipError_t launch_aug_segments(int dtype, const tsde_seg_t* segs, int nseg, double cF, double cG, hipStream_t s, int* taken) {
   return by_dtype(dtype, [&](auto t) {
     using T = decltype(t);
+    AugTable<T> tb;
+    tb.nseg = 0;
+    tb.chunk_begin[0] = 0;
     int done = 0;
-    while (done < nseg) {
-      AugTable<T> tb;
-      tb.nseg = 0;
-      tb.chunk_begin[0] = 0;
-      while (done < nseg && tb.nseg < kAugMaxSeg) {
-        const tsde_seg_t& sg = segs[done++];
-        if (sg.n <= 0) continue;
-        const int k = tb.nseg++;
-        tb.seg[k] = AugSegOp<T>{(T*)sg.out, (const T*)sg.s, (const T*)sg.F, (const T*)sg.G, (const T*)sg.D,
-                                (T)cF,      (T)cG,          (T)sg.sF,       (T)sg.sG,       (T)sg.sD};
-        tb.n[k] = sg.n;
-        // chunks start at multiples of 4096 elements, so pointer alignment decides the vector path
-        tb.vec[k] = vec_ok(sg.n, sg.out, sg.s, sg.F, sg.G, sg.D) ? 1 : 0;
-        tb.chunk_begin[k + 1] = tb.chunk_begin[k] + (int32_t)((sg.n + kAugChunk - 1) / kAugChunk);
-      }
-      if (tb.nseg == 0) break;
-      const int total = tb.chunk_begin[tb.nseg];
-      const int grid = total < kMaxGrid ? total : kMaxGrid;
-      TSDE_LAUNCH(aug_multi_kernel<T>, dim3(grid), dim3(kBlock), 0, s, tb);
-      const hipError_t e = hipGetLastError();
-      if (e != hipSuccess) return e;
+    while (done < nseg && (tb.nseg < kAugMaxSeg || segs[done].n <= 0)) {
+      const tsde_seg_t& sg = segs[done++];
+      if (sg.n <= 0) continue;
+      const int k = tb.nseg++;
+      tb.seg[k] = AugSegOp<T>{(T*)sg.out, (const T*)sg.s, (const T*)sg.F, (const T*)sg.G, (const T*)sg.D,
+                              (T)cF,      (T)cG,          (T)sg.sF,       (T)sg.sG,       (T)sg.sD};
+      tb.n[k] = sg.n;
+      // chunks start at multiples of 4096 elements, so pointer alignment decides the vector path
+      tb.vec[k] = vec_ok(sg.n, sg.out, sg.s, sg.F, sg.G, sg.D) ? 1 : 0;
+      tb.chunk_begin[k + 1] = tb.chunk_begin[k] + (int32_t)((sg.n + kAugChunk - 1) / kAugChunk);
     }
-    return hipSuccess;
+    *taken = done;
+    if (tb.nseg == 0) return hipSuccess;
+    const int total = tb.chunk_begin[tb.nseg];
+    const int grid = total < kMaxGrid ? total : kMaxGrid;
+    TSDE_LAUNCH(aug_multi_kernel<T>, dim3(grid), dim3(kBlock), 0, s, tb);
+    return hipGetLastError();
   });
 }
 

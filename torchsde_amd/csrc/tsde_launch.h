@@ -218,7 +218,7 @@ hipError_t launch_milstein_gf_general_support(int dtype, void* yk, const void* y
                                               int64_t d, int64_t m, double dt, double sqrt_dt, int ito, hipStream_t s);
 hipError_t launch_milstein_gf_general_correction(int dtype, void* corr, const void* g, const void* gk, const void* I, int64_t B,
                                                  int64_t d, int64_t m, double sqrt_dt, hipStream_t s);
-hipError_t launch_aug_segments(int dtype, const tsde_seg_t* segs, int nseg, double cF, double cG, hipStream_t s);
+hipError_t launch_aug_segments(int dtype, const tsde_seg_t* segs, int nseg, double cF, double cG, hipStream_t s, int* taken);
 hipError_t launch_interp(int dtype, void* out, const void* ya, const void* yb, int64_t n, double w0, double w1, hipStream_t s);
 // rheun.hip
 hipError_t launch_heun_final(int dtype, void* y1, const void* y0, const void* f, const void* fp, const void* g, const void* gp,

@@ -1543,6 +1543,46 @@ __global__ void __launch_bounds__(kBlock) trajectory_rows_sens_kernel(const Rows
   }
 }
 
+// ---- row-coupled systems with a diffusion MATRIX: general, scalar and additive noise -----------------------------------
+// One lane per row, as `trajectory_prog_kernel` with W = D, but the row meets MN Brownian channels and its diffusion is a
+// (D, MN) matrix: y1 = (y0 + cf*f) + cg * sum_k g[i][k] dW[k], the stepwise route's order (steps.hip, the general-noise
+// contraction). The matrix never exists as an array: the generated model (specialise.source_rows_general) holds this step's
+// increments, `m.w`, and its `g<SLOT>(y)` IS the contraction -- per row i the sum over k in increasing k, straight-line, no
+// term for an entry that is structurally zero -- so that the schemes run through `scheme_step` with the unit as their noise
+// operand (g * 1 is g, bit for bit). The field is (rows, MN): row r meets elements r * MN .. r * MN + MN - 1 (scalar noise:
+// MN = 1, element r). Euler, midpoint, Heun, Euler-Heun: the schemes the reference has for general noise.
+// The argument block is `ProgArgs` as it is (consts: one scalar per constant; no programs, no scalar-noise flag): the number
+// of Brownian channels is the template argument MN, checked against the solve's m on the host (`launch_rows_general`).
+template <typename T, int METHOD, int D, int MN, typename M>
+__global__ void __launch_bounds__(kBlock) trajectory_rows_general_kernel(const ProgArgs<T> p) {
+  static_assert(METHOD == kEuler || METHOD == kMidpoint || METHOD == kHeun || METHOD == kEulerHeun,
+                "general noise: Euler, midpoint, Heun, Euler-Heun");
+  using V = Vec<T, D>;
+  const int64_t row = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int64_t i = row * D;
+  if (i >= p.n) return;
+  const Pack<T, D> y_init = load<T, D>(p.y0, i);
+  V y;
+#pragma unroll
+  for (int c = 0; c < D; ++c) y.v[c] = y_init.v[c];
+  M m;
+  m.setup(p, 0);
+  const NoiseKey key = launch_key(p.key, p.key_dev);
+  const uint64_t elem = key.elem0 + (uint64_t)row * (uint64_t)MN;
+  int j = 0;
+  int next_out = next_output_step<false>(p.out_step, 0, p.n_out);
+  for (int k = 0; k < p.n_steps; ++k) {
+    const StepRow<T> r = step_row<false>(p.rows + (int64_t)k * 8, p.cells, k);
+    T unused[MN];
+    // (MN = 4: the row's increments are ONE Philox quad -- `launch_rows_general` takes only shards that start on a quad)
+    draw_increment<T, MN, /*NEED_U=*/false, /*PAIRS=*/false>(PlainStepNoise(key, r.cell), r, elem, false, m.w, unused);
+    stage_times<T, METHOD>(r.t0(), r.dt, m.tslot);
+    const V y1 = scheme_step<T, METHOD, V, M, T>(y, m, (T)1, (T)0, r.dt, r.half_dt, r.rdt, r.sqrt_dt);
+    emit_outputs<false, D>(p, i, k, j, next_out, y.v, y1.v);
+    y = y1;
+  }
+}
+
 // ---- additive noise: the drift as a program, the diffusion as a table ---------------------------------------------------
 // Noise type "additive" (base_sde.py:101-102; the reference's ExAdditive, tests/problems.py:106-132): g depends on t only
 // and every batch row meets the same (d, m) matrix. The host evaluates the user's g at every stage time of the solve
@@ -1732,6 +1772,17 @@ static hipError_t launch_rows_sens(const ProgArgs<T>& p, void* sens, hipStream_t
   q.base = p;
   q.sens = (T*)sens;
   return launch_lanes(trajectory_rows_sens_kernel<T, METHOD, D, NT, M>, p.n / D, s, q);
+}
+
+// ... and with a (D, MN) diffusion matrix (specialise.source_rows_general): one lane per row, `m` must be the unit's MN
+template <typename T, int METHOD, int D, int MN, typename M>
+static hipError_t launch_rows_general(const ProgArgs<T>& p, int64_t m, hipStream_t s) {
+  if (m != MN || p.d != D) return hipErrorInvalidValue;
+  // MN = 4: `draw_increment` reads a row's increments as one Philox quad. The field of a (rows, 4) Brownian motion starts
+  // at element row_offset * 4, always on a quad; any other start is refused rather than drawn from the wrong elements
+  if (MN == 4 && p.key.elem0 % 4 != 0) return hipErrorInvalidValue;
+  if (nothing_to_do(p)) return hipSuccess;
+  return launch_lanes(trajectory_rows_general_kernel<T, METHOD, D, MN, M>, p.n / D, s, p);
 }
 
 template <typename T, int METHOD, template <typename, int> class M = ProgModel>

@@ -954,6 +954,27 @@ def trajectory_rows(ys, y0, structure, consts, method, schedule, bm):
     return ys
 
 
+def trajectory_rows_general(ys, y0, structure, consts, m, method, schedule, bm):
+    """All steps of a small ROW-COUPLED system with general, scalar or additive noise (recognise_rows.RecognisedRows with
+    `m` Brownian channels) in one launch: one lane per row, the diffusion matrix contracted with the row's m increments by the
+    system's generated model (specialise.source_rows_general, csrc/trajectory.hip trajectory_rows_general_kernel). Returns
+    `ys`, or None while the generated unit is not compiled yet (there is no interpreter for such systems: the caller stays
+    stepwise)."""
+    from . import specialise
+    _native.require_device(ys, y0, consts)
+    rows, d = _check_program_args(ys, y0, schedule, consts, per_channel=False)
+    if tuple(bm.shape) != (rows, int(m)) or structure[0][1:3] != (d, int(m)):
+        raise ValueError(f"a system of {structure[0][1:3]} (channels, Brownian channels) needs a state of (rows, d) and a "
+                         f"Brownian motion of (rows, m), got {tuple(y0.shape)} and {tuple(bm.shape)}")
+    key, compiled = specialise.lookup_rows_general(structure, structure[1][1], y0.dtype, method, y0.device)
+    if compiled is None:
+        return None
+    _, _, stream = _launch_env(y0)
+    specialise.launch(compiled, schedule, bm, stream, ys.data_ptr(), y0.data_ptr(), rows, d, consts.data_ptr(), consts.numel(),
+                      int(m))
+    return ys
+
+
 def trajectory_prog_additive(ys, y0, f_code, consts, g_table, m, method, schedule, bm):
     """All steps of an additive-noise SDE in one launch (``tsde_trajectory_prog_additive``): the drift an expression program
     (interpreted, or compiled at run time: `_compiled_or_interpreted`), the diffusion the table `g_table` -- (m, d), the

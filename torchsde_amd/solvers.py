@@ -450,11 +450,15 @@ class BaseSDESolver:
         # ... and additive noise: the drift a program, the diffusion tabulated at the scheme's stage times
         additive = (sde.noise_type == NOISE_TYPES.additive and self._additive_code() is not None
                     and not getattr(sde, "user_g_prod", False))
+        # ... and small row-coupled systems with a diffusion MATRIX (general, scalar, additive noise; recognise_rows with `m`):
+        # tried where the interpretations above end in a refusal
+        rows_general = self._rows_general_applies(y0)
         precision = self.options.get("matrix_precision", "f32")
         if precision not in ("f32", "bf16x3"):
             raise ValueError(f"Expected options['matrix_precision'] in ('f32', 'bf16x3'), got {precision!r}.")
         if (not recognise.ENABLED or not self.options.get("trajectory_kernel", True) or self.adaptive or self.stateful
-                or type(sde) is not ForwardSDE or sde.user_product or not (elementwise or networks or programs or additive)):
+                or type(sde) is not ForwardSDE or sde.user_product
+                or not (elementwise or networks or programs or additive or rows_general)):
             return None
         if self._tracks_grad(y0):
             return self._integrate_recognised_with_grad(y0, ts) if (elementwise or programs) else None
@@ -465,11 +469,27 @@ class BaseSDESolver:
         if ledger is None:
             return None
         start = {name: getattr(ledger.base, name) for name in ledger.counters}
-        ys = self._solve_recognised(ledger, start, y0, ts, bm, (elementwise, networks, programs, additive), precision)
+        ys = self._solve_recognised(ledger, start, y0, ts, bm, (elementwise, networks, programs, additive, rows_general),
+                                    precision)
         if ys is None:
             for name, value in start.items():        # (the probe calls of the interpretation are not steps of the solve)
                 setattr(ledger.base, name, value)
         return ys
+
+    def _rows_general_applies(self, y0):
+        """Whether a refusal of the other interpretations leaves the row kernel with a diffusion matrix to try: general, scalar
+        or additive noise, at most `MAX_D` channels and `MAX_M` Brownian channels, one of the schemes the reference has for
+        general noise (Euler, midpoint, Heun, Euler-Heun), the module's own f and g."""
+        from . import recognise_rows
+        sde, bm = self.sde, self._native_bm()
+        base = getattr(sde, "_base_sde", None)
+        return (sde.noise_type in (NOISE_TYPES.general, NOISE_TYPES.scalar, NOISE_TYPES.additive)
+                and self._program_code() in (_native.TRAJ_EULER, _native.TRAJ_MIDPOINT, _native.TRAJ_HEUN,
+                                             _native.TRAJ_EULER_HEUN)
+                and bm is not None and y0.dim() == 2 and y0.shape[1] <= recognise_rows.MAX_D
+                and len(bm.shape) == 2 and tuple(bm.shape) == (y0.shape[0], bm.shape[1]) and bm.shape[1] <= recognise_rows.MAX_M
+                and hasattr(base, "f") and hasattr(base, "g") and not hasattr(base, "g_prod")
+                and not getattr(sde, "user_g_prod", False))
 
     @staticmethod
     def _shift_sources(found):
@@ -509,7 +529,7 @@ class BaseSDESolver:
             found, spec, times = self._interpret(ledger, y0, ts, kinds, precision)
         except recognise.NotElementwise as e:
             return ledger.refuse(str(e))
-        if kinds[3] and tuple(bm.shape) != (y0.shape[0], found.m):
+        if (kinds[3] or spec[0] == "program_rows_general") and tuple(bm.shape) != (y0.shape[0], found.m):
             return None
         if spec[0] in ("neural", "neural_rheun") and (tuple(bm.shape) != (y0.shape[0], spec[4]) or y0.numel() >= 2 ** 30):
             return None
@@ -585,6 +605,33 @@ class BaseSDESolver:
         return stepwise
 
     def _interpret(self, ledger, y0, ts, kinds, precision):
+        """`_interpret_forms`, and where that ends in a refusal of a module with general, scalar or additive noise
+        (`kinds[4]`, `_rows_general_applies`) the last chance: a small row-coupled system whose diffusion is a (d, m) MATRIX
+        assembled from column arithmetic (recognise_rows.recognise_rows with `m`: one lane per row, the contraction with the
+        row's m increments generated and compiled at run time). The refusal keeps every earlier reason."""
+        from . import recognise, recognise_rows, specialise
+        reason = None
+        # (code known to end as such a system skips the other interpreters -- only while this solve can still take that route)
+        if any(kinds[:4]) and not (kinds[4] and ledger.remembers("rows_general")):
+            try:
+                return self._interpret_forms(ledger, y0, ts, kinds[:4], precision)
+            except recognise.NotElementwise as e:
+                if not kinds[4]:
+                    raise
+                reason = str(e)
+        prefix = "as a row-coupled system: " if reason is None else f"{reason}; as a row-coupled system: "
+        d, m = y0.shape[1], self.bm.shape[1]
+        over = specialise.rows_general_refusal(d, m, self._program_code(), y0.dtype)
+        if over is not None:
+            raise recognise.NotElementwise(prefix + over)
+        try:
+            found = recognise_rows.recognise_rows(self.sde, ts[0], y0, m=m)
+        except recognise.NotElementwise as e2:
+            raise recognise.NotElementwise(prefix + str(e2)) from None
+        ledger.remember("rows_general")
+        return found, found.spec(), None
+
+    def _interpret_forms(self, ledger, y0, ts, kinds, precision):
         """The interpreters of `_integrate_recognised` in turn, the first that holds the code wins: (found, spec, times) --
         `times` the stage times the coefficient tables are taken at, or None -- or NotElementwise with every reason.
         Additive noise: the drift a program, the diffusion tabulated at the scheme's stage times. Otherwise the single-function
@@ -682,6 +729,9 @@ class BaseSDESolver:
         if spec[0] == "program_rows":
             from . import recognise_rows
             return recognise_rows.recognise_rows(sde, ts[0], y0, rows=5).spec()
+        if spec[0] == "program_rows_general":
+            from . import recognise_rows
+            return recognise_rows.recognise_rows(sde, ts[0], y0, rows=5, m=spec[4]).spec()
         if spec[0] == "program_diagonal":
             milstein = self._program_code() in (_native.TRAJ_MILSTEIN_ITO, _native.TRAJ_MILSTEIN_STRAT)
             return recognise.recognise_program(sde, ts[0], y0, sde.noise_type, rows=5).spec(milstein)
@@ -1058,6 +1108,10 @@ class BaseSDESolver:
         ys[0].copy_(y0c)
         if kind == "program_rows":
             done = K.trajectory_rows(ys[1:], y0c, coefficients[1], coefficients[2], self._program_code(), schedule, bm)
+            return None if done is None else ys          # (None: the generated unit is still compiling -- stepwise for now)
+        if kind == "program_rows_general":
+            done = K.trajectory_rows_general(ys[1:], y0c, coefficients[1], coefficients[2], coefficients[4], self._program_code(),
+                                             schedule, bm)
             return None if done is None else ys          # (None: the generated unit is still compiling -- stepwise for now)
         if kind == "program_diagonal":
             K.trajectory_prog_diag(ys[1:], y0c, coefficients[1], coefficients[2], coefficients[3], coefficients[4],

@@ -146,6 +146,9 @@ _ENTRY = {
     "rows_sens": ("tsde_specialised_rows_sens_launch",
                   "void* ys, void* sens, const void* y0, int64_t rows, int64_t d, const void* consts, int n_const",
                   [_P, _P, _P, _I64, _I64, _P, _INT]),
+    "rows_general": ("tsde_specialised_rows_general_launch",
+                     "void* ys, const void* y0, int64_t rows, int64_t d, const void* consts, int n_const, int64_t m",
+                     [_P, _P, _I64, _I64, _P, _INT, _I64]),
 }
 
 
@@ -549,4 +552,83 @@ def rows_sens_refusal(d, nt, method, dtype):
     if d * (nt + 1) > cap:
         return (f"{d} channels x ({nt} tangents + 1) = {d * (nt + 1)} numbers per state, more than the {cap} this scheme keeps "
                 "in registers")
+    return None
+
+
+# ---- ... and row-coupled systems with a diffusion MATRIX (csrc/trajectory.hip trajectory_rows_general_kernel) ------------------
+def source_rows_general(structure, n_const, dtype, method):
+    """The translation unit of a row-coupled system with general, scalar or additive noise: `structure` =
+    RecognisedRows.structure() of `recognise_rows(..., m=m)`, outputs = d drift expressions, then the d * m entries of the
+    diffusion matrix row-major. The model is `source_rows`' statements plus a GENERATED CONTRACTION with the step's increments
+    `w` (the kernel writes them into the model before every step): per row i, `sum_k g_ik * w[k]` in increasing k, straight-line,
+    with no term for an entry that is the literal 0 -- the matrix never exists as an array, Heston costs three products per
+    stage. `g<SLOT>(x)` returns that vector, so `scheme_step` runs the schemes with the unit as their noise operand."""
+    (_, d, m, statements, outputs), _ = structure
+    names = [f"n{k}" for k in range(len(statements))]
+    needs = {name: set(o for o in operands if o.startswith("n")) for name, (op, operands) in zip(names, statements)}
+
+    def structural_zero(o):
+        return o.startswith("(T)") and float(o[3:]) == 0.0
+
+    def lines_for(outs):
+        wanted, stack = set(), [o for o in outs if o.startswith("n")]
+        while stack:
+            x = stack.pop()
+            if x in wanted:
+                continue
+            wanted.add(x)
+            stack.extend(needs.get(x, ()))
+        return [f"    const T {name} = {_ROW_OPS[op].format(*operands)};" for name, (op, operands) in zip(names, statements)
+                if name in wanted]
+    drift = list(outputs[:d])
+    f_body = lines_for(drift) + ["    V r;"] + [f"    r.v[{c}] = {o};" for c, o in enumerate(drift)] + ["    return r;"]
+    entries = list(outputs[d:])
+    live = [o for o in entries if not structural_zero(o)]
+    g_body = lines_for(live) + ["    V r;"]
+    for i in range(d):
+        total = None
+        for k in range(m):
+            o = entries[i * m + k]
+            if structural_zero(o):
+                continue
+            term = f"{o} * w[{k}]"
+            total = term if total is None else f"({total}) + {term}"
+        g_body.append(f"    r.v[{i}] = {total if total is not None else '(T)0'};")
+    g_body.append("    return r;")
+    nc = max(1, n_const)
+    setup = f"""  TSDE_D void setup(const ProgArgs<T>& p, int64_t) {{
+    _Pragma("unroll") for (int k = 0; k < {nc}; ++k) c[k] = k < p.n_const ? p.consts[k] : (T)0;
+  }}
+"""
+    model = _model("template <typename T>\nstruct RowGeneralModel", f"V = Vec<T, {d}>", f"  T c[{nc}];\n  T w[{m}];\n", setup,
+                   {"f": "\n".join(f_body), "g": "\n".join(g_body)}, "const T&")
+    return _unit(f" (a row-coupled system, {m} Brownian channels)", model, "rows_general", dtype, method,
+                 f"d != {d} || m != {m} || n_const > {nc}", "0",
+                 f"launch_rows_general<T, METHOD, {d}, {m}, RowGeneralModel<T>>(p, m, s)")
+
+
+def lookup_rows_general(structure, n_const, dtype, method, device, wait=None):
+    """(key, library or None) of a row-coupled system with a diffusion matrix (`_find`)."""
+    return _find(lambda: source_rows_general(structure, n_const, dtype, method), "rows_general", device, wait)
+
+
+# Which (d, m) take that unit. A lane keeps the row's d values, the m increments and, per stage, d drift values and the d sums of
+# the contraction; the entries of the matrix are consumed as they are made. Per scheme and dtype a cap on d * m that lies below
+# the first (d, m), d = 1 .. 8, m = 1 .. 8, whose DENSE worst case (tests/helpers_rows_general.DenseWorst: every entry reads
+# every channel, a constant of its own and t) compiles for gfx950 with scratch or spilled vector registers
+# (tools/rows_general_resource_usage.py, profiles/rows_general_resource_usage.txt: every pair is listed there).
+ROWS_GENERAL_CAP = {   # method code -> cap on d * m in (float32, float64)
+    _native.TRAJ_EULER: (64, 64), _native.TRAJ_MIDPOINT: (64, 64), _native.TRAJ_HEUN: (64, 64),
+    _native.TRAJ_EULER_HEUN: (64, 64),
+}
+
+
+def rows_general_refusal(d, m, method, dtype):
+    """Why a system of d channels and m Brownian channels stays stepwise under this scheme, or None."""
+    cap = ROWS_GENERAL_CAP.get(int(method))
+    if cap is None:
+        return "no row kernel with a diffusion matrix for this scheme"
+    cap = cap[0 if dtype == torch.float32 else 1]
+    if d * m > cap:
+        return f"{d} channels x {m} Brownian channels = {d * m} matrix entries, more than the {cap} this scheme keeps in registers"
     return None

@@ -10,6 +10,7 @@ the verdict. The book lives on the user's SDE object, ``base.__dict__["_tsde_rec
 - "trusted": {(structure, chain, solver name, sde_type, d, dtype, batch, *tags): True | reason}, at most 32 entries
 - "program", "uses_t": (chain, solver name) of code known to end as an expression program / to use t (solvers._interpret);
   "not_rows": of code the differentiable column interpretation does not hold (solvers._integrate_rows_with_grad);
+  "rows_general": of code known to end as a row-coupled system with a diffusion matrix (solvers._interpret);
   "autograd": {(chain, solver name): why solves stay stepwise while autograd records}
 - "counter_rate": {key: {call counter: advance per step}}, "solves": {key: solves since the last check}, pruned with "trusted"
 """
@@ -181,7 +182,7 @@ class Ledger:
         return self.book.get("counter_rate", {}).get(key)
 
     def remembers(self, finding):
-        """Whether this code was found to be `finding` ("program", "uses_t" or "not_rows") by this scheme before."""
+        """Whether this code was found to be `finding` ("program", "uses_t", "not_rows" or "rows_general") by this scheme before."""
         return self.book.get(finding) == (self.chain, self._solver_name)
 
     def remember(self, finding):
@@ -218,6 +219,8 @@ def describe(sde):
         kind = ("perceptron drift" if structure[0][0] == "perceptron"
                 else f"expression program, {structure[0][1]} noise" if structure[0][0] == "program"
                 else f"row-coupled system of {structure[0][1]} channels" if structure[0][0] == "rows"
+                else f"row-coupled system of {structure[0][1]} channels, {structure[0][2]} Brownian channels"
+                if structure[0][0] == "rows_general"
                 else f"f: {structure[0][0]}, g: {structure[1][0]}")
         timed = any("table" in part for part in structure if isinstance(part, tuple))
         route = ("trajectory kernel" + (" with per-stage-time coefficient rows" if timed else "")

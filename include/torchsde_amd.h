@@ -97,8 +97,18 @@ typedef struct tsde_seg {
  *                         a subnormal product carries an error of at most 2^-150 into the sums of the plain form and none
  *                         here, a few units in the last place of a state that small (2^-149 once it is subnormal). The
  *                         caller vouches for the bit: a wrong bit changes the rounding of a step and nothing else. Every
- *                         other entry point ignores it. */
+ *                         other entry point ignores it.
+ *   TSDE_TRAJ_PACE_WAVES  the waves of tsde_trajectory_affine_diag pace themselves: a wave runs at hardware priority 3 for
+ *                         the first half of its steps, at 2 up to three quarters, at 1 up to seven eighths and at 0 for the
+ *                         last eighth (tsde_wave_pace below gives the step counts), so that the waves that share a SIMD
+ *                         advance abreast and finish together instead of one after another with the launch's last wave
+ *                         alone on its SIMD. Scheduling only: the outputs are the same bytes with and without the bit.
+ *                         While such a launch runs, waves of OTHER kernels on the same compute units (priority 0) issue
+ *                         behind its waves of priority 1 to 3. Euler, midpoint and Heun, float32, values only, constant
+ *                         coefficients, one 16-byte group per lane (the forms measured faster paced); every other form
+ *                         and entry point ignores the bit. */
 #define TSDE_TRAJ_POW2_STEPS 1u
+#define TSDE_TRAJ_PACE_WAVES (1u << 1)
 typedef struct tsde_traj {
   const void* step_rows;   /* [n_steps][8], dtype */
   const uint32_t* cells;   /* [n_steps] */
@@ -116,6 +126,12 @@ const char* tsde_last_error(void);
 void tsde_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 /* Host-side: the 128-bit counter the kernels build for (quad, cell, node, stream). */
 void tsde_noise_counter(uint64_t quad, uint32_t cell, uint64_t node, uint32_t stream, uint32_t out[4]);
+/* Host-side: the wave pacing of a solve of `n_steps` steps (TSDE_TRAJ_PACE_WAVES), the kernel's own definition.
+ * tsde_wave_pace: out[0..2] = the step counts at which a wave's priority falls to 2, 1 and 0, out[3] = the step count of its
+ * first change under `flags` (-1: never -- the bit is not set). tsde_wave_pace_change: the change due at step `k` of such a
+ * solve -- *level = the priority from step k on; returns the step count of the next change, or -1. */
+void tsde_wave_pace(int32_t n_steps, uint32_t flags, int32_t out[4]);
+int32_t tsde_wave_pace_change(int32_t n_steps, int32_t k, int32_t* level);
 
 /* ---- Brownian source ------------------------------------------------------------------------ */
 

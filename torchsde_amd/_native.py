@@ -25,6 +25,7 @@ NOISE_DIAGONAL, NOISE_SCALAR, NOISE_GENERAL, NOISE_ADDITIVE = 0, 1, 2, 3
 TRAJ_EULER, TRAJ_MILSTEIN_ITO, TRAJ_MILSTEIN_STRAT, TRAJ_MIDPOINT, TRAJ_SRK, TRAJ_HEUN, TRAJ_EULER_HEUN = 0, 1, 2, 3, 4, 5, 6
 TRAJ_REVERSIBLE_HEUN = 7
 TRAJ_POW2_STEPS = 1      # tsde_traj_t.flags: every row's dt and sqrt(h) are powers of two (include/torchsde_amd.h)
+TRAJ_PACE_WAVES = 2      # tsde_traj_t.flags: the affine kernel's waves lower their priority as they advance
 TRAJ_MILSTEIN_ITO_GF, TRAJ_MILSTEIN_STRAT_GF = 8, 9      # derivative-free Milstein: `tsde_trajectory_mlp_general` only
 FN_CODES = {"identity": 0, "exp": 1, "sigmoid": 2, "tanh": 3, "softplus": 4, "sin": 5, "cos": 6, "poly3": 7}
 
@@ -106,6 +107,8 @@ SIGNATURES = {
     "tsde_last_error": (ctypes.c_char_p, []),
     "tsde_philox4x32_10": (None, [ctypes.POINTER(_c_u32), ctypes.POINTER(_c_u32), ctypes.POINTER(_c_u32)]),
     "tsde_noise_counter": (None, [_c_u64, _c_u32, _c_u64, _c_u32, ctypes.POINTER(_c_u32)]),
+    "tsde_wave_pace": (None, [_c_i32, _c_u32, ctypes.POINTER(_c_i32)]),
+    "tsde_wave_pace_change": (_c_i32, [_c_i32, _c_i32, ctypes.POINTER(_c_i32)]),
     "tsde_brownian_normals": (_c_int, [_c_ptr, _c_i64, _c_u64, _c_u64, _c_u32, _c_u64, _c_u32, _c_int, _c_ptr]),
     "tsde_brownian_query": (_c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_u64, _c_u64, _c_ptr, _c_i64, _c_i64, _c_dbl,
                                      _c_dbl, _c_ptr, _c_ptr, _c_int, _c_int, _c_int, _c_ptr, _c_int, _c_ptr]),

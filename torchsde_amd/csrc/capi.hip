@@ -117,6 +117,21 @@ void tsde_noise_counter(uint64_t quad, uint32_t cell, uint64_t node, uint32_t st
   out[3] = c.w;
 }
 
+void tsde_wave_pace(int32_t n_steps, uint32_t flags, int32_t out[4]) {
+  const tsde::WavePace w = tsde::wave_pace(n_steps);
+  out[0] = w.at[0];
+  out[1] = w.at[1];
+  out[2] = w.at[2];
+  out[3] = tsde::wave_pace_first(w, (flags & TSDE_TRAJ_PACE_WAVES) != 0);
+}
+
+int32_t tsde_wave_pace_change(int32_t n_steps, int32_t k, int32_t* level) {
+  int l;
+  const int32_t next = tsde::wave_pace_change(tsde::wave_pace(n_steps), k, l);
+  *level = l;
+  return next;
+}
+
 int tsde_brownian_normals(void* out, int64_t n, uint64_t entropy, uint64_t elem0, uint32_t cell, uint64_t node,
                           uint32_t stream_id, int dtype, void* stream) {
   const hipStream_t s = (hipStream_t)stream;

@@ -171,6 +171,10 @@ struct TrajArgs {
   int32_t n_steps, n_out;
   NoiseKey key;
   const uint64_t* key_dev;
+  uint32_t flags;           // TSDE_TRAJ_PACE_WAVES of `tsde_traj_t.flags` (appended: read by the paced forms only)
+#ifdef TSDE_WAVE_STAMPS
+  uint64_t* stamps;         // (waves, 4): start, end, HW_ID | XCC_ID << 32, 0 -- the diagnostic build only
+#endif
 };
 
 enum : int { kEuler = TSDE_TRAJ_EULER, kMilIto = TSDE_TRAJ_MILSTEIN_ITO, kMilStrat = TSDE_TRAJ_MILSTEIN_STRAT,
@@ -533,6 +537,38 @@ constexpr bool step_ahead_form() {
   return std::is_same<T, float>::value && W == 4 && !SENS && !TIMED && METHOD != kMidpoint && METHOD != kSrk;
 }
 
+#ifdef TSDE_WAVE_STAMPS
+// The diagnostic build of tools/wave_finish_times.hip: when a wave started and ended on the 100 MHz clock and where it ran
+// (HW_ID: SIMD, CU, SE; XCC_ID), one vector store by the wave's first active lane into a buffer nothing else reads. The
+// shipped library is built without the macro and holds no stamp.
+struct WaveStamp {
+  uint64_t t0;
+  TSDE_D WaveStamp() : t0(__builtin_amdgcn_s_memrealtime()) {}
+  TSDE_D void store(uint64_t* out) const {
+    const uint64_t t1 = __builtin_amdgcn_s_memrealtime();
+    const uint32_t hw = __builtin_amdgcn_s_getreg(4 | (31 << 11)), xcc = __builtin_amdgcn_s_getreg(20 | (31 << 11));
+    const int lane = threadIdx.x & 63;
+    if (lane != __builtin_amdgcn_readfirstlane(lane)) return;
+    const int64_t wave = (int64_t)blockIdx.x * (kBlock / 64) + threadIdx.x / 64;
+    typedef uint64_t u64x4 __attribute__((ext_vector_type(4)));
+    const u64x4 v = {t0, t1, (uint64_t)hw | ((uint64_t)xcc << 32), 0};
+    *reinterpret_cast<u64x4*>(out + wave * 4) = v;
+  }
+};
+#endif
+
+// The forms of the affine kernel whose waves pace themselves (`wave_pace`, tsde_common.h) when the schedule carries
+// TSDE_TRAJ_PACE_WAVES: the loop carries the step count of the next change of priority in a scalar register, as it carries
+// `next_out`, and pays one scalar compare per step; a change is a cold block. Chosen per form by the compiled loop (the vector
+// instructions, vector registers and scratch of the plain loop) and by the device (profiles/wave_pacing_ab.json): Euler,
+// midpoint and Heun, float32, one 16-byte group per lane, constant coefficients. Milstein (Ito) and SRK measured SLOWER paced
+// and keep the plain loop; Stratonovich Milstein, Euler-Heun, float64, W = 1, SENS and TIMED were not measured and are not paced.
+template <typename T, int METHOD, int W, bool SENS, bool TIMED>
+constexpr bool wave_paced_form() {
+  return std::is_same<T, float>::value && W == 4 && !SENS && !TIMED &&
+         (METHOD == kEuler || METHOD == kMidpoint || METHOD == kHeun);
+}
+
 // W = 4: a lane owns one 16-byte group (needs d % 4 == 0 so the group stays inside one row).
 // W = 1: a lane owns one element (any d; also used for small problems, where it exposes 4x the lanes).
 // SENS : carry the kSens path-wise sensitivities of every element and write them next to the outputs.
@@ -563,6 +599,9 @@ __global__ void __launch_bounds__(kBlock) trajectory_kernel(const TrajArgs<T> p)
   const int64_t lane = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   const int64_t i = lane * W;
   if (i >= p.n) return;
+#ifdef TSDE_WAVE_STAMPS
+  const WaveStamp stamp;
+#endif
   const int64_t col = i % p.d;
   const Pack<T, W> a = load<T, W>(p.a, col), c = load<T, W>(p.c, col);
   Pack<T, W> b, e;
@@ -587,6 +626,17 @@ __global__ void __launch_bounds__(kBlock) trajectory_kernel(const TrajArgs<T> p)
   int j = 0;
   int next_out = next_output_step<true>(p.out_step, 0, p.n_out);
   constexpr bool kAhead = step_ahead_form<T, METHOD, W, SENS, TIMED>();
+  constexpr bool kPaced = wave_paced_form<T, METHOD, W, SENS, TIMED>();
+  const WavePace pace = wave_pace(p.n_steps);
+  int next_pace = -1;                               // (kPaced only: the step count of the wave's next change of priority)
+  if constexpr (kPaced) {
+    next_pace = wave_pace_first(pace, (p.flags & TSDE_TRAJ_PACE_WAVES) != 0);
+    if (next_pace >= 0) {
+      int level = 3;
+      if (next_pace == 0) next_pace = wave_pace_change(pace, 0, level);   // (fewer than 2 steps: a change due at once)
+      set_wave_priority(level);
+    }
+  }
   StepData<T> ahead = step_data(p, key, 0);         // (kAhead only: dead code, and removed, in the other forms)
   for (int k = 0; k < p.n_steps; ++k) {
     const StepData<T> now = ahead;                  // (kAhead: what step k - 1 loaded)
@@ -683,7 +733,18 @@ __global__ void __launch_bounds__(kBlock) trajectory_kernel(const TrajArgs<T> p)
 #pragma unroll
       for (int q = 0; q < W; ++q) y[q] = y1[q];
     }
+    if constexpr (kPaced) {                         // (at the latch, where the `due` test stands: the loop's top stays as it was)
+      if (__builtin_expect(k + 1 == next_pace, 0)) {
+        asm volatile("" ::: "memory");              // (keeps this a branch, like the `due` block)
+        int level;
+        next_pace = wave_pace_change(pace, k + 1, level);
+        set_wave_priority(level);
+      }
+    }
   }
+#ifdef TSDE_WAVE_STAMPS
+  stamp.store(p.stamps);
+#endif
 }
 
 template <typename T, int METHOD, bool SENS, bool TIMED = false, bool LINEAR = false, bool POW2 = false>
@@ -732,6 +793,7 @@ hipError_t launch_trajectory_affine_diag(int dtype, void* ys, void* sens, const 
     p.c = (const T*)c;
     p.e = (const T*)e;
     p.cstride = cstride;
+    p.flags = tr->flags;
     if ((b == nullptr) != (e == nullptr)) return hipErrorInvalidValue;   // the linear form takes BOTH shifts as null
     if (b == nullptr && (cstride != 0 || sens)) return hipErrorInvalidValue;
     if (nothing_to_do(p)) return hipSuccess;

@@ -99,6 +99,51 @@ TSDE_D T uniform_load(const T* p, int64_t i) {
   return *(const __attribute__((address_space(4))) T*)(p + i);
 }
 
+// Wave pacing (TSDE_TRAJ_PACE_WAVES, include/torchsde_amd.h). A SIMD issues for the wave of highest priority first and among
+// equals for the oldest, so the resident waves of a long step loop do not advance abreast: they finish one after another and
+// the launch's last wave runs alone, at half the issue rate. A paced wave lowers its own priority as it advances -- 3 up to
+// `at[0]` completed steps, then 2, then 1, and 0 from `at[2]` on -- so the waves behind it catch up and a SIMD's waves reach
+// the last stretch together. `s_setprio` is a scalar instruction: no vector instruction, no register of the loop.
+//   at = n/2, n - n/4, n - n/8, each at most the one after it, the last at most n - 1: every wave ends at priority 0, and in
+//   a solve of fewer than 8 steps thresholds coincide and levels are skipped, never repeated or raised.
+struct WavePace {
+  int32_t at[3];
+};
+TSDE_HD WavePace wave_pace(int32_t n_steps) {
+  WavePace w;
+  w.at[2] = n_steps - n_steps / 8;
+  w.at[1] = n_steps - n_steps / 4;
+  w.at[0] = n_steps / 2;
+  const int32_t last = n_steps > 0 ? n_steps - 1 : 0;
+  if (w.at[2] > last) w.at[2] = last;
+  if (w.at[1] > w.at[2]) w.at[1] = w.at[2];
+  if (w.at[0] > w.at[1]) w.at[0] = w.at[1];
+  return w;
+}
+// The step count at which a wave's first change is due: -1, never, without the flag.
+TSDE_HD int32_t wave_pace_first(const WavePace& w, bool paced) { return paced ? w.at[0] : -1; }
+// The change due once k steps are complete (the loop tests `k + 1 == next` at its latch, where it tests for a due output):
+// the level to run at from step k on, and, returned, the step count of the next change (-1: none).
+TSDE_HD int32_t wave_pace_change(const WavePace& w, int32_t k, int& level) {
+  if (k >= w.at[2]) {
+    level = 0;
+    return -1;
+  }
+  if (k >= w.at[1]) {
+    level = 1;
+    return w.at[2];
+  }
+  level = 2;
+  return w.at[1];
+}
+// (the level is an immediate of the instruction: one site per level)
+TSDE_D void set_wave_priority(int level) {
+  if (level == 0) __builtin_amdgcn_s_setprio(0);
+  else if (level == 1) __builtin_amdgcn_s_setprio(1);
+  else if (level == 2) __builtin_amdgcn_s_setprio(2);
+  else __builtin_amdgcn_s_setprio(3);
+}
+
 // A scalar coefficient of a step kernel: a launch-time constant, or a word in DEVICE memory that an earlier kernel on
 // the stream wrote (adaptive stepping without a host round trip per attempt: the step size, dt/2, sqrt(dt), 1/dt and
 // the interpolation weights of an attempt are produced by the controller kernel, csrc/adaptive.hip). On the C ABI such

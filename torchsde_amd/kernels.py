@@ -594,6 +594,12 @@ def pow2_steps_enabled():
     return os.environ.get("TSDE_POW2_STEPS", "1") != "0"
 
 
+def wave_pace_enabled():
+    """The switch of tests and A/B runs: TSDE_WAVE_PACE=0 in the environment keeps TSDE_TRAJ_PACE_WAVES out of every schedule
+    made (the affine trajectory kernel's waves then keep the priority they start with)."""
+    return os.environ.get("TSDE_WAVE_PACE", "1") != "0"
+
+
 def pow2_steps(rows):
     """TSDE_TRAJ_POW2_STEPS of step rows in the state dtype: every dt (slot 0) and sqrt(h) (slot 4) an exact power of two
     inside the exponent ranges above, and slot 1 exactly dt/2."""
@@ -625,10 +631,14 @@ class TrajectorySchedule:
         s.n_steps, s.n_out = self.n_steps, self.n_out
         self.pow2_steps = pow2_steps(rows)           # (of the rows as the kernel reads them: in the state dtype)
         s.flags = _native.TRAJ_POW2_STEPS if self.pow2_steps else 0
-        self._struct = s
+        self._struct = s                             # (what is known about the rows)
+        self.pace_waves = wave_pace_enabled()
+        self._launch = _native.Traj.from_buffer_copy(s)   # ... and how to run them: what the entry points receive
+        if self.pace_waves:
+            self._launch.flags |= _native.TRAJ_PACE_WAVES
 
     def struct(self):
-        return ctypes.byref(self._struct)
+        return ctypes.byref(self._launch)
 
     _recent = collections.OrderedDict()      # (host contents, device, dtype) -> schedule; device tensors are read-only
 
@@ -639,7 +649,8 @@ class TrajectorySchedule:
         recent)."""
         key = (np.ascontiguousarray(step_rows).tobytes(), np.ascontiguousarray(cells).tobytes(),
                tuple(int(k) for k in out_step), tuple((float(a), float(b)) for a, b in out_w), str(device), dtype,
-               pow2_steps_enabled())     # (the bit itself is a function of the rows; the switch that clears it is not)
+               pow2_steps_enabled(),     # (the bit itself is a function of the rows; the switch that clears it is not)
+               wave_pace_enabled())
         hit = cls._recent.get(key)
         if hit is not None:
             cls._recent.move_to_end(key)
